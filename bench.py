@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Throughput bench of the hot path: training rays/s of the vectorised object-NeRF iteration.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets the workload up, runs W warm-up and K timed steps, writes the last timed step's outputs if
+--dump-outputs is given, and prints the line: nothing else.  Everything beyond the headline figure (the bf16 line, the
+measured MFMA peak, the other configurations and the native-shape frame, the PSNR block, the CPU baseline, the
+collectives timed alone, the share curve and the detail file by default) runs only with --full.
 
 One "step" = one complete training iteration of train.py:394-474: the stacked object networks of THIS rank (label
 statistics -> fused forward / loss / backward kernel -> gradient finalize -> AdamW) plus the shared background network
@@ -26,17 +31,24 @@ of the launcher and of the collectives' host path (tests/test_bench_launcher.py)
 
 dtype: the headline line is fp32 -- the reference's arithmetic (train.py:74, AMP off) and the only mode held to the
 1e-4 parity bar.  BASELINE.json's configs name bf16: the opt-in bf16-operand mode of the same step (fp32 accumulation,
-master weights, compositing and AdamW; PSNR-gated) is timed in the same run and reported as the `bf16_mode` object
+master weights, compositing and AdamW; PSNR-gated) is timed in a --full run and reported as the `bf16_mode` object
 (or as the headline with --dtype bf16).
 
 Prints ONE short JSON line (rank 0; < 4 KB, asserted: the driver parses it): the contract's keys, `roofline` = the dominant
-launch against the dense MFMA peak of its operand type (spec and measured; `traffic` = the RECORDED PMC bytes of the same
-launch, profiles/r06_counters.json), `cpu_baseline` = the oracle (the reference's op sequence in PyTorch on the host cores) at
-BASELINE.md section 3's metric shape, the PSNR delta of the trained model, a flat `summary` (the other BASELINE configurations'
-rays/s and ms per step, the native-shape frame) and `detail` = the path of the FULL report (--detail-out, default
-gpurun_out/bench_detail.json): `other_configs` (c3, configs[3]'s per-GPU share, configs[4]'s per-GPU share in fp16 without /
-with the feature loss, the mapping loop at the native shape), the `psnr` block, the per-shape CPU rows, `bf16_mode`.  A
-distributed run adds `dist_selftest` = the iteration's two collectives timed on their own.
+launch against the dense MFMA peak of its operand type (`traffic` = the RECORDED PMC bytes of the same launch,
+profiles/r06_counters.json; the measured peak with --full) and a flat `summary`.  With --full the line also carries
+`cpu_baseline` = the oracle (the reference's op sequence in PyTorch on the host cores) at BASELINE.md section 3's metric
+shape, the PSNR delta of the trained model, the other BASELINE configurations' rays/s and ms per step and the native-shape
+frame in `summary`, and `detail` = the path of the FULL report (--detail-out, default bench_out/bench_detail.json):
+`other_configs` (c3, configs[3]'s per-GPU share, configs[4]'s per-GPU share in fp16 without / with the feature loss, the
+mapping loop at the native shape), the `psnr` block, the per-shape CPU rows, `bf16_mode`.  A distributed --full run adds
+`dist_selftest` = the iteration's two collectives timed on their own.
+
+--dump-outputs DIR: after the timed steps, what the last of them computed on rank 0, as float32 .npy files in DIR:
+`obj_loss_terms` [K, 4] and `obj_params` [K, P] (the object networks after that step's AdamW), and with the background
+network `bg_loss_terms` [1, 4] and `bg_params` [1, P_bg].  An array larger than the dump budget is replaced by a fixed,
+seeded sample of its elements (`<name>_sample.npy`).  The inputs depend on the arguments only, so two builds run with the
+same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -108,14 +120,26 @@ def parse_args(argv=None):
     ap.add_argument("--other-steps", type=int, default=10, help="timed steps of each `other_configs` entry")
     ap.add_argument("--detail-out", default=None,
                     help="file the FULL report goes to (other_configs, psnr detail, native_frame, per-shape cpu rows, notes); "
-                         "default gpurun_out/bench_detail.json.  stdout carries ONE short line (< 4 KB) naming this file")
+                         "default with --full: bench_out/bench_detail.json, none without.  stdout carries ONE short line "
+                         "(< 4 KB) naming this file")
     ap.add_argument("--share-curve-out", default=None,
-                    help="also time the emulated 1 / 2 / 4 / 8-rank shares of c4 and c2 (fp32 and bf16, --steps each) and "
-                         "write the table to this file (profiles/r05_share_curve.json)")
+                    help="with --full: also time the emulated 1 / 2 / 4 / 8-rank shares of c4 and c2 (fp32 and bf16, "
+                         "--steps each) and write the table to this file (profiles/r05_share_curve.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the bf16 line, the measured MFMA peak, the other "
+                         "configurations and the native-shape frame, the PSNR block, the CPU baseline, the collectives "
+                         "timed alone (distributed runs); the --no-* switches above still apply.  Off: set-up, warm-up, "
+                         "the timed steps, --dump-outputs and the line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (loss terms, trained parameters) "
+                         "as float32 DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--dry-launch", action="store_true",
                     help="CPU form of the N-rank launch: gloo instead of RCCL, the iteration's two collectives on host "
                          "buffers, no kernels; the line carries \"dry_launch\": true and value 0")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.share_curve_out and not args.full:
+        ap.error("--share-curve-out is part of a --full run")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -496,11 +520,45 @@ class Workload:
                 "chunk_streams": getattr(getattr(self.obj_loop, "ws", None), "lanes", 1),
                 "background_rays_on_this_gpu": (self.bg_batches[0]["labels"].shape[1] if self.bg_loop is not None else 0)}
 
+    def outputs(self):
+        """What the last step handed its caller: the loss terms ShardedIteration.step returns and the parameters its
+        AdamW left in the arenas (padding columns dropped).  Call after timed(), which synchronised the device."""
+        out = {"obj_loss_terms": self.obj_loop.ws.loss_terms, "obj_params": self.arena.params[:, :self.arena.P]}
+        if self.bg_loop is not None:
+            out["bg_loss_terms"] = self.bg_loop.ws.loss_terms
+            out["bg_params"] = self.bg_loop.arena.params[:, :self.bg_loop.arena.P]
+        return out
+
     def free(self):
         import torch
         self.iteration = self.obj_loop = self.bg_loop = self.batches = self.bg_batches = self.arena = None
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(arrays: dict, out_dir: str, budget=DUMP_BUDGET_BYTES):
+    """arrays (name -> float32 tensor) -> out_dir/<name>.npy, float32.  Smallest first, each array takes at most an equal
+    share of what is left of the budget; one that does not fit is written as a fixed sample of its flattened elements
+    (seed 0, ascending indices; the same for every run of the same shapes) to <name>_sample.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left = budget
+    for i, (name, t) in enumerate(items):
+        share = left // (len(items) - i) // 4
+        flat = t.detach().reshape(-1)
+        if flat.numel() <= share:
+            a, fname = t.detach().cpu().numpy(), name
+        else:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), size=share, replace=False))
+            a, fname = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy(), name + "_sample"
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(out_dir, fname + ".npy"), a)
+        left -= a.nbytes
 
 
 OTHER_CONFIGS = [   # (key, base config, overrides, operand modes) -- timed after the headline by the default run
@@ -822,9 +880,11 @@ def main():
     w = Workload(cfgname, wl, args, dev, world, rank, mode)
     dt, kern_ms = w.timed(mode, args.steps, args.warmup, dist if use_dist else None)
     status = int(w.obj_loop.ws.status.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(w.outputs(), args.dump_outputs)
     # the opt-in bf16-operand mode beside the fp32 headline (same step, same batches)
     bf16_extra = None
-    if not mode and args.bf16_line:
+    if args.full and not mode and args.bf16_line:
         bf16_extra = w.timed(True, args.steps, args.warmup, dist if use_dist else None)
     per_rank = [w.K]
     coll = None
@@ -833,7 +893,7 @@ def main():
         pr[rank] = w.K
         dist.all_reduce(pr)
         per_rank = pr.tolist()
-        coll = collective_times(dev, dist)
+        coll = collective_times(dev, dist) if args.full else None
 
     if rank == 0:
         rays_per_step = w.rays_per_step()
@@ -851,7 +911,7 @@ def main():
             "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "config": cfg_block,
             "rays_per_sec_per_gpu": value / world,
-            "roofline": w.roofline(mode, kern_ms, with_peak=not args.no_peak),
+            "roofline": w.roofline(mode, kern_ms, with_peak=args.full and not args.no_peak),
         }
         if coll is not None:
             out["dist_selftest"] = coll
@@ -865,7 +925,7 @@ def main():
     Hd, feat = w.Hd, w.feat
     w.free()
     if rank == 0:
-        if world == 1 and default_line and not args.no_other_configs:
+        if world == 1 and args.full and default_line and not args.no_other_configs:
             out["other_configs"] = other_configs(args, dev)
             # (the emulated 1 / 2 / 4 / 8-rank share table is NOT part of the default run: --share-curve-out)
             for key, fn in (("native_frame", lambda: native_frame(dev)), ("native_frame_bf16", lambda: native_frame(dev, True))):
@@ -878,7 +938,7 @@ def main():
             with open(args.share_curve_out, "w") as f:
                 json.dump(sc, f, indent=1)
             out["share_curve_file"] = args.share_curve_out
-        if world == 1 and not args.no_psnr and Hd == 32:
+        if world == 1 and args.full and not args.no_psnr and Hd == 32:
             ps = psnr_block(dev, args.psnr_seeds, with_bf16=args.bf16_line or mode is True, with_fp16=mode == "fp16")
             if ps is not None:
                 out["psnr"] = ps
@@ -889,12 +949,14 @@ def main():
                 out["psnr_delta_ci95_db"] = ps["iter300"][key]["ci95_db"]
                 out["psnr_delta_iter50_db"] = ps["iter50"][key]["mean_delta_db"]
                 out["psnr_delta_iter50_ci95_db"] = ps["iter50"][key]["ci95_db"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(feat)
         # what the line's figures mean has changed before (round 4: psnr_delta_db became the 300-iteration ensemble figure,
         # kernel_ms moved inside the timed steps); versioned since round 5, whose changes are listed here
-        out["metric_version"] = 6
-        out["metric_changes"] = ("v6: stdout carries a fixed short line (< 4 KB: contract keys, flat roofline / cpu_baseline / "
+        out["metric_version"] = 7
+        out["metric_changes"] = ("v7: a run without --full times the headline only (no bf16 line, measured peak, other "
+                                 "configurations, PSNR, CPU baseline or detail file); --full is v6's default run.  "
+                                 "v6: stdout carries a fixed short line (< 4 KB: contract keys, flat roofline / cpu_baseline / "
                                  "summary); this full report is the --detail-out file; the emulated share table left the "
                                  "default run (--share-curve-out).  v5: objnerf_train_step applies AdamW in its last launch, so roofline.kernel_ms (HIP events "
                                  "around objnerf_train_step, inside the timed steps) now includes the optimiser; the "
@@ -930,7 +992,7 @@ def main():
             summ["cpu_baseline_rays_per_s"] = out["cpu_baseline"]["value"]
         out["summary"] = summ
         sys.stdout.flush()
-        emit(out, json_fd, args.detail_out or os.path.join(ROOT, "gpurun_out", "bench_detail.json"))
+        emit(out, json_fd, args.detail_out or (os.path.join(ROOT, "bench_out", "bench_detail.json") if args.full else None))
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -112,3 +112,37 @@ def test_detail_file_holds_the_full_report(tmp_path):
     assert line["detail"] == path
     with open(path) as f:
         assert json.load(f) == full
+
+
+def test_dump_outputs_writes_float32_within_budget(tmp_path):
+    """--dump-outputs: every array as float32 <name>.npy; one that does not fit its share of the budget becomes a fixed,
+    seeded sample (<name>_sample.npy) that is the same from call to call."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"small": torch.randn(3, 4, generator=g), "big": torch.randn(50, 1000, generator=g)[:, :700]}
+    budget = 4 * (12 + 2000)
+    for d in ("a", "b"):
+        bench.dump_outputs(arrays, str(tmp_path / d), budget=budget)
+    assert sorted(os.listdir(tmp_path / "a")) == ["big_sample.npy", "small.npy"]
+    small = np.load(tmp_path / "a" / "small.npy")
+    assert small.dtype == np.float32 and np.array_equal(small, arrays["small"].numpy())
+    big = np.load(tmp_path / "a" / "big_sample.npy")
+    assert big.dtype == np.float32 and big.shape == (2000,)
+    assert np.isin(big, arrays["big"].numpy()).all()
+    assert np.array_equal(big, np.load(tmp_path / "b" / "big_sample.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= budget + 2 * 128
+    bench.dump_outputs(arrays, str(tmp_path / "c"))
+    assert np.array_equal(np.load(tmp_path / "c" / "big.npy"), arrays["big"].numpy())
+
+
+def test_extras_need_full():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert bench.parse_args(["--full", "--share-curve-out", "x.json"]).full
+    r = _run("--share-curve-out", "x.json")
+    assert r.returncode != 0 and r.stdout.strip() == "" and "--full" in r.stderr

@@ -4,13 +4,11 @@ fixtures produced by RUNNING the reference (tests/golden/make_golden.py g12 / g1
 * G12: sceneObject.__init__ / append_keyframe / prune_keyframe (vmap.py:29-257) and the per-object state map of
   train.py:197-205, replayed frame by frame: kf_id_dict order, lastest_kf_queue, kf_pointer, n_keyframes, use_frame
   after every frame, the candidates offered to random.choice, and the final keyframe buffers.
-* G13: the checkpoint file the reference writes (vmap.py:556-576) loads here; and -- in the build container only,
-  where /root/reference exists -- a file written here loads through the reference's own load_checkpoints
-  (vmap.py:579-602, load_state_dict(strict)).
+* G13: the checkpoint file the reference writes (vmap.py:556-576) loads here; G13B: a file written here carries what
+  the reference's own load_checkpoints (vmap.py:579-602, load_state_dict(strict)) read from it when it was run on it.
 """
 import os
 import random
-import sys
 
 import numpy as np
 import pytest
@@ -174,15 +172,8 @@ def test_reference_written_checkpoint_renders_like_reference_g13(golden, dev):
     assert float((clip.cpu() - T(g["clip"])).abs().max()) < 1e-4
 
 
-REF = "/root/reference/objnerf"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference checkout (build container only)")
-def test_checkpoint_written_here_loads_in_reference(tmp_path, monkeypatch):
-    """The other direction, executed with the reference's own code: sceneObject.save_checkpoints here ->
-    the reference's sceneObject.load_checkpoints (strict load_state_dict on its own OccupancyMap / UniDirsEmbed)."""
-    sys.path.insert(0, os.path.join(GOLDEN))
-    import make_golden as MG                       # imports the reference modules with the GUI packages stubbed
+def object_written_here(out_dir):
+    """The object fixture G13B was recorded with, saved by sceneObject.save_checkpoints into out_dir -> (object, file)."""
     torch.manual_seed(77)
     so = _blank_object(obj_id=9)
     with torch.no_grad():
@@ -190,19 +181,28 @@ def test_checkpoint_written_here_loads_in_reference(tmp_path, monkeypatch):
     so.clip_feat = np.random.RandomState(1).randn(2, 512).astype(np.float32)
     so.caption_feat = np.random.RandomState(2).randn(2, 384).astype(np.float32)
     so.set_semantic(11)
-    so.save_checkpoints(str(tmp_path), epoch=3)
-    path = os.path.join(str(tmp_path), "obj_9.pth")
+    so.save_checkpoints(str(out_dir), epoch=3)
+    return so, os.path.join(str(out_dir), "obj_9.pth")
+
+
+def test_checkpoint_written_here_loads_in_reference(tmp_path, golden):
+    """The other direction: sceneObject.save_checkpoints here -> the reference's own sceneObject.load_checkpoints
+    (vmap.py:579-602: strict load_state_dict on its own OccupancyMap / UniDirsEmbed), as fixture G13B recorded it when the
+    reference loaded this very file (tests/golden/make_g13b_ref_load.py): every checkpoint entry it reads is there, the
+    two state dicts carry exactly its modules' parameter names with their shapes, and their values are the ones its
+    modules held after the load -- bit for bit the parameters of the object saved here."""
+    g = golden("g13b_ref_load")
+    so, path = object_written_here(tmp_path)
     assert os.path.exists(path)
-    # the reference runs torch 2.0.1, where torch.load unpickles numpy arrays by default
-    _load = torch.load
-    monkeypatch.setattr(MG.ref_vmap.torch, "load", lambda f, *a, **k: _load(f, *a, weights_only=False, **k))
-    cfg = MG.make_cfg(hidden=32, scale=2.0)
-    import types
-    ref_self = types.SimpleNamespace(trainer=MG.ref_trainer.Trainer(cfg), training_device="cpu")
-    assert MG.ref_vmap.sceneObject.load_checkpoints(ref_self, path) is True
-    for p_ref, p in zip(ref_self.trainer.fc_occ_map.parameters(), so.trainer.fc_occ_map.parameters()):
-        assert torch.equal(p_ref.detach(), p.detach().cpu())
-    assert torch.equal(ref_self.trainer.pe.B_layer.weight.detach(), so.trainer.pe.B_layer.weight.detach().cpu())
-    assert list(ref_self.trainer.fc_occ_map.state_dict().keys()) == list(so.trainer.fc_occ_map.state_dict().keys())
-    assert (ref_self.obj_id, ref_self.semantic_id, float(ref_self.trainer.obj_scale)) == (9, 11, 2.0)
-    assert np.array_equal(ref_self.clip_feat, so.clip_feat)
+    ck = torch.load(path, weights_only=False)      # (the reference runs torch 2.0.1: numpy arrays unpickle by default)
+    assert all(k in ck for k in g["read"].tolist()) and "clip_feat" in g["read"].tolist()
+    for entry, tag, mod in (("FC_state_dict", "fc", so.trainer.fc_occ_map), ("PE_state_dict", "pe", so.trainer.pe)):
+        sd, here = ck[entry], mod.state_dict()
+        assert list(sd.keys()) == g[f"{tag}_keys"].tolist() == list(here.keys())    # no missing, no unexpected entries
+        for i, (k, v) in enumerate(sd.items()):
+            ref = torch.from_numpy(np.array(g[f"{tag}{i}"]))      # (0-d entries stay 0-d)
+            assert v.shape == ref.shape and torch.equal(v.detach().cpu(), ref), k
+            assert torch.equal(here[k].detach().cpu(), ref), k
+    assert (ck["obj_id"], ck["semantic_id"], float(ck["obj_scale"])) == tuple(g["meta"].tolist()) == (9, 11, 2.0)
+    assert np.array_equal(g["clip_feat"], so.clip_feat) and np.array_equal(ck["clip_feat"], so.clip_feat)
+    assert np.array_equal(g["caption_feat"], so.caption_feat) and np.array_equal(ck["caption_feat"], so.caption_feat)

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof3
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-psnr --no-peak --no-other-configs"
+Q="--no-cpu-baseline --no-psnr --no-peak --no-other-configs --full"
 P="--no-bg --no-bf16-line --steps 3 --warmup 1 $Q"
 C5="--config c5 --dtype fp16 --objects 8 --no-bg --no-bf16-line --steps 2 --warmup 1 $Q"
 T="timeout 600"

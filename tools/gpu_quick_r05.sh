@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/quick5
 mkdir -p $OUT
 cd $R
-Q="--no-cpu-baseline --no-psnr --no-peak --no-other-configs"
+Q="--no-cpu-baseline --no-psnr --no-peak --no-other-configs --full"
 for m in "" "--bf16"; do for s in "--metric" ""; do echo "bg_trace $s $m: $(STEPS=200 python3 tools/bg_trace.py $s $m | tail -1)"; done; done 2>&1 | grep -v amdgpu.ids | tee $OUT/bg_trace.txt
 timeout 300 python3 bench.py --steps 100 --warmup 20 $Q > $OUT/bench_default.json 2>/dev/null
 timeout 300 python3 bench.py --steps 100 --warmup 20 --no-pipeline $Q > $OUT/bench_default_nopipe.json 2>/dev/null

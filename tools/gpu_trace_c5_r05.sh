@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/trace5c5
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-psnr --no-peak --no-other-configs"
+Q="--no-cpu-baseline --no-psnr --no-peak --no-other-configs --full"
 run() {   # name, bench args
   local n=$1; shift 1
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t_$n -o s -- python3 $R/bench.py "$@" $Q > $OUT/bench_$n.json 2> $OUT/bench_$n.err

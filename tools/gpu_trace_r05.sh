@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/trace5
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-psnr --no-peak --no-other-configs"
+Q="--no-cpu-baseline --no-psnr --no-peak --no-other-configs --full"
 run() {   # name, anchor, bench args
   local n=$1 a=$2; shift 2
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t_$n -o s -- python3 $R/bench.py "$@" $Q > $OUT/bench_$n.json 2> $OUT/bench_$n.err
