@@ -1,6 +1,6 @@
 // Layer-wise training iteration for ANY hidden width (multiple of 32): the shared background network
 // (hidden 128, train.py:447-463) and the hidden-256 stress configuration.  The hidden-32 object networks
-// use the fused kernel in objnerf_train.hip; wider networks do not fit one CU's LDS / registers, so this
+// use the fused kernel in objnerf_train32.hip; wider networks do not fit one CU's LDS / registers, so this
 // path materialises activations in the caller's workspace and runs the contraction as batched fp32 MFMA
 // GEMMs (v_mfma_f32_16x16x4_f32, 64x64x16 tiles), with the reference's op order:
 //   embedding.py:46-55 -> model.py:61-103 -> loss.py:5-103 (objnerf_step_batch_loss) -> reverse.

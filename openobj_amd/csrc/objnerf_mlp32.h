@@ -1,9 +1,9 @@
 // Per-object MLP (hidden = 32), fp32, second generation of the register-resident MFMA chain (gfx950).
 //
-// What changed against objnerf_mlp.h (which the bf16 kernel still uses) and why -- tools/ubench_alu.hip measured that a
-// v_mfma_f32_16x16x4_f32 occupies the SIMD's vector ALU for its whole 32 cycles (VALU work of either wave of the SIMD
-// does not overlap it), so the fused kernel's time is  34 * #MFMA + ~3..5 * #VALU  cycles and every VALU instruction
-// and every non-algorithmic MFMA counts:
+// What changed against the first-generation chain (since removed; objnerf_mlp.h keeps the block type and the arena
+// layout the two shared) and why -- tools/ubench_alu.hip measured that a v_mfma_f32_16x16x4_f32 occupies the SIMD's
+// vector ALU for its whole 32 cycles (VALU work of either wave of the SIMD does not overlap it), so the fused kernel's
+// time is  34 * #MFMA + ~3..5 * #VALU  cycles and every VALU instruction and every non-algorithmic MFMA counts:
 //
 //  * DIRECTION-OWNER positional encoding.  Lane group g of a sample owns directions j = 4 i + g (slot i = 0..5) in ALL
 //    six octaves.  The reference's argument fp32(fp32(p 2^f) pi) equals 2^f fp32(p pi) exactly, so one double-float

@@ -1,18 +1,18 @@
-// Fused training iteration + point evaluation for K stacked hidden-32 object networks (gfx950).
+// Hidden-32 training step and point evaluation (gfx950): the C entry points, the step's workspace and the kernels
+// around the fused training kernel.
 //
 // Replaces, for cfg.training_strategy == "hip", the reference's per-iteration op sequence
-//   vmap(pe_model) -> vmap(fc_model) -> loss.step_batch_loss -> backward          (train.py:424-472)
-// with ONE kernel.  A 512-thread workgroup (8 waves, two per SIMD so one wave's VALU work overlaps the
-// other's MFMAs) owns one object's weights in LDS and sweeps that object's rays in tiles of 128 samples
-// (whole rays).  Per tile:
-//   1. every wave embeds 16 samples and runs the MLP forward chain on MFMA, activations in registers;
-//   2. sigma / rgb go to LDS, a wave per ray-group composites (segmented wave scans), evaluates the
-//      masked losses of loss.py and writes d(loss)/d(sigma,rgb) back in place;
-//   3. every wave back-propagates its 16 samples in registers (dgrad), transposes (d_out, input) pairs
-//      through LDS and the eight waves share the weight-gradient MFMAs (two 16x16 tiles each per layer
-//      group), accumulating in registers across the whole sweep.
-// Each workgroup then writes one partial-gradient slab; finalize_kernel sums the slabs (no atomics on
-// global memory, bit-reproducible run to run).
+//   vmap(pe_model) -> vmap(fc_model) -> loss.step_batch_loss -> backward          (train.py:424-472).
+// objnerf_train_step sends other widths, longer rays and the layer-wise / fp16 modes to objnerf_generic.hip and
+// objnerf_train256.hip.  A hidden-32 step with S <= 64 runs
+//   * with the feature loss, feat_pre_kernel (or a GEMM + feat_rowstats_kernel): the 512-d head's per-ray inputs;
+//   * the fused training kernel: launch_train32 (fp32, objnerf_train32.hip) or launch_train_bf16 (bf16,
+//     objnerf_train_bf16.hip / objnerf_bf16v2_body.h), one partial-gradient slab per workgroup;
+//   * with the feature loss, feat_post_kernel (or feat_scale_kernel + two split-K GEMMs) and, unless finalize_kernel
+//     folds it in, feat_finish_kernel: the 512-d head's gradient;
+//   * finalize_kernel: sums the slabs (no atomics on global memory, bit-reproducible run to run), the loss terms and
+//     the status word, and steps AdamW when an optimiser is attached.
+// eval_kernel is the forward of objnerf_eval_points / objnerf_mlp_forward.
 #include <mutex>
 #include "objnerf_mlp32.h"
 #include "objnerf_train_common.h"
@@ -30,778 +30,6 @@ struct EvalDev {
   float* alpha; float* color; float* hfeat;
   Layout L;
 };
-
-// stg[(rowbase + 16 tt + 4 g + r)][16 w + c] = v  for a 32-feature block / a 16-feature tile
-__device__ __forceinline__ void store_T32(float* stg_lane, const int rowbase, const T32& v) {
-#pragma unroll
-  for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) stg_lane[(rowbase + 16 * tt + r) * STG_LD] = v.t[tt][r];
-}
-__device__ __forceinline__ void store_T16(float* stg_lane, const int rowbase, const f32x4& v) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) stg_lane[(rowbase + r) * STG_LD] = v[r];
-}
-
-// D[out 0..31][in 16 cols] += sum_s dT[out][s] * aT[in][s] over the 128 staged samples.
-// The contraction index is free to permute: MFMA k-slot (step st, lane group g) takes sample 32 g + st, so a
-// lane walks CONSECUTIVE samples and fetches two steps per ds_read_b64 (8-byte aligned with the 130-float
-// row stride; 2c + 32g + st covers all 64 banks -> conflict-free).  dT / aT point at &stg[(row0 + c) * LD + 32 g].
-__device__ __forceinline__ void wgrad_pair(f32x4& acc0, f32x4& acc1, const float* dT, const float* aT) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  dT = (const float*)__builtin_assume_aligned(dT, 8);     // row pitch 520 B, 32 g and st even: 8-byte aligned
-  aT = (const float*)__builtin_assume_aligned(aT, 8);
-#pragma unroll 8
-  for (int st = 0; st < 32; st += 2) {
-    const f32x2 b = *reinterpret_cast<const f32x2*>(aT + st);
-    const f32x2 a0 = *reinterpret_cast<const f32x2*>(dT + st);
-    const f32x2 a1 = *reinterpret_cast<const f32x2*>(dT + 16 * STG_LD + st);
-    acc0 = OBJ_MFMA(a0[0], b[0], acc0);
-    acc1 = OBJ_MFMA(a1[0], b[0], acc1);
-    acc0 = OBJ_MFMA(a0[1], b[1], acc0);
-    acc1 = OBJ_MFMA(a1[1], b[1], acc1);
-  }
-}
-
-__device__ __forceinline__ void write_pair(float* slab, const f32x4& a0, const f32x4& a1, const int c, const int g,
-                                           const int ct, const int w_off, const int ncols, const int b_off) {
-  const int col = 16 * ct + c;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int o0 = 4 * g + r, o1 = 16 + 4 * g + r;
-    if (col < ncols) {
-      slab[w_off + o0 * ncols + col] = a0[r];
-      slab[w_off + o1 * ncols + col] = a1[r];
-    } else if (col == ncols && b_off >= 0) {
-      slab[b_off + o0] = a0[r];
-      slab[b_off + o1] = a1[r];
-    }
-  }
-}
-
-// Diagnostic build (-DPHASE_TIMING): per-wave s_memtime deltas of each phase of workgroup 0, read back with
-// objnerf_debug_phase() (tools/phase_timing.py).  Not part of the product library.
-#ifdef PHASE_TIMING
-__device__ unsigned long long g_phase[8][24];
-#define PT_INIT() unsigned long long pt_acc[18]; for (int i_ = 0; i_ < 18; ++i_) pt_acc[i_] = 0; \
-  unsigned long long pt_t0 = __builtin_amdgcn_s_memtime()
-#define PT(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pt_acc[i] += t_ - pt_t0; pt_t0 = t_; } while (0)
-#define PT_FLUSH() do { if (blockIdx.x == 0 && lane == 0) for (int i_ = 0; i_ < 18; ++i_) g_phase[w][i_] = pt_acc[i_]; } while (0)
-#else
-#define PT_INIT() do {} while (0)
-#define PT(i) do {} while (0)
-#define PT_FLUSH() do {} while (0)
-#endif
-
-// keeps the instruction scheduler from pulling the sincos of later embedding tiles ahead of the current one
-// (which overlaps nicely but needs ~50 more live registers and spills the persistent accumulators)
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-
-#define TILE_SYNC() __syncthreads()
-
-// ------------------------------------------------------------------------------------------------
-constexpr int X1N = 6, X2N = 3;       // 16-wide embedding tiles of the two input blocks (96 and 48 padded entries)
-template <bool FEAT, bool MASKS>
-__global__ __launch_bounds__(NTHR) void train_fused_kernel(const TrainDev a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, g = lane >> 4;
-  const int k = blockIdx.x / a.G, gi = blockIdx.x % a.G;
-  constexpr int WF = FEAT ? W_FLOATS_FEAT : W_FLOATS_NOFEAT;
-  float* s_alpha = lds + WF;
-  float* s_col = s_alpha + TS;
-  float* stg = lds + WF + SM_FLOATS;
-
-  stage_weights(lds, a.params + (long)k * a.p_stride, a.L, FEAT, tid, NTHR);
-  for (int i = tid; i < STG_ROWS * STG_LD; i += NTHR) stg[i] = 0.0f;
-  __syncthreads();
-
-  const float scale = a.scale[k];
-  const int S = a.S, R = a.R, TR = a.TR;
-  const float n1 = (float)a.counts[2 * k], n2 = (float)a.counts[2 * k + 1];
-  int bflag0, bflag1;
-  batch_flags(a, bflag0, bflag1);
-  const float inv1 = bflag0 ? 0.0f : 1.0f / (n1 + 1e-10f);
-  const float inv2 = bflag1 ? 0.0f : 1.0f / (n2 + 1e-10f);
-
-  // persistent gradient accumulators
-  f32x4 accA0 = zero4(), accA1 = zero4(), accB0 = zero4(), accB1 = zero4(), accC0 = zero4(), accC1 = zero4();
-  // row-wise sums over samples: slot s of a register = lane s of each lane group; feature of slot s (< 8) is
-  // 16 (s >> 2) + 4 g + (s & 3); lanes 8..15 carry a second quantity
-  float gS0 = 0.f;   // [0..7] d W_alpha   | [8..15] d W_oc[0]
-  float gS1 = 0.f;   // [0..7] d W_oc[1]   | [8..15] d W_oc[2]
-  float gS2 = 0.f;   // [0..7] d b_mid1    | [8..15] d b_mid2
-  float g_ba = 0.f, g_boc0 = 0.f, g_boc1 = 0.f, g_boc2 = 0.f;
-  f32x4 accT0 = zero4(), accT1 = zero4();   // d B: rows j = 4g + r (accT1: 16 + 4g + r), column x = c < 3
-  float l_d = 0.f, l_c = 0.f, l_o = 0.f, l_f = 0.f;
-  f32x4 accF0 = zero4(), accF1 = zero4();
-
-
-
-  // Loop-invariant per-lane LDS addresses must NOT be hoisted out of the tile loop: there are dozens of them
-  // and they end up spilled to scratch, each reload a serialised ~500-cycle stall.  Inside the loop the lane
-  // coordinates (c, g) and every per-lane LDS pointer are macros over an opaque copy of the lane id that is
-  // re-defined at each phase boundary, so addresses are recomputed (a few VALU ops) next to their use.
-  int lane_l = lane;
-#define RELAUNDER() asm volatile("" : "+v"(lane_l))
-#define c (lane_l & 15)
-#define g (lane_l >> 4)
-#define wt_fl (lds + OFF_FL + (4 * g) * ST_CL + c)
-#define stg_lane (stg + (4 * g) * STG_LD + 16 * w + c)
-#define lane_rd (stg + c * STG_LD + 32 * g)
-#define wt_in (lds + OFF_IN + (4 * g) * ST_IN + c)
-#define wt_m1 (lds + OFF_M1 + (4 * g) * ST_M + c)
-#define wt_cat (lds + OFF_CAT + (4 * g) * ST_CAT + c)
-#define wt_m2 (lds + OFF_M2 + (4 * g) * ST_M + c)
-#define wt_cl (lds + OFF_CL + (4 * g) * ST_CL + c)
-  // sample position of (tile, slot); issued one tile ahead (phase C) so that the HBM latency is off the tile's
-  // critical path
-  auto fetch_point = [&](const int tile_, const int slot_, float& x, float& y, float& z_) {
-    const int q_ = slot_ / a.S, si_ = slot_ - q_ * a.S;
-    const int ray_ = tile_ * a.TR + q_;
-    x = 0.f; y = 0.f; z_ = 0.f;
-    if (tile_ < a.NT && q_ < a.TR && ray_ < a.R) {
-      const long rr = (long)k * a.R + ray_;
-      if (a.pts) {
-        const float* p = a.pts + (rr * a.S + si_) * 3;
-        x = p[0]; y = p[1]; z_ = p[2];
-      } else {
-        const float zz = a.z[rr * a.S + si_];
-        const float* o = a.origins + rr * 3;
-        const float* d = a.dirs + rr * 3;
-        x = (o[0] + d[0] * zz) - a.obj_center;   // vmap.py:548-551 (two roundings: -ffp-contract=off)
-        y = (o[1] + d[1] * zz) - a.obj_center;
-        z_ = (o[2] + d[2] * zz) - a.obj_center;
-      }
-    }
-  };
-  const bool rows_mode = seg_is_rows(a.S);
-  const SegRows seg_rows = SegRows::make(rows_mode ? a.S : 64, lane);
-  float nx, ny, nz;
-  fetch_point(gi, 16 * w + lane_l % 16, nx, ny, nz);
-  PT_INIT();
-  for (int tile = gi; tile < a.NT; tile += a.G) {
-    asm volatile("" ::: "memory");   // keep the LDS weight reads inside the loop (no LICM into registers)
-    RELAUNDER();
-    const int ray0 = tile * TR;
-    // ---------------------------------------------------------------- 1. forward
-    const int slot = 16 * w + c;
-    const int q = slot / S;
-    const int ray = ray0 + q;
-    const bool valid = (q < TR) && (ray < R);
-    const float px = nx, py = ny, pz = nz;       // fetched during the previous tile's phase C
-    Pe pe;
-    pe_project(lds, g, px, py, pz, scale, pe);
-    PT(0);
-    Acts act;
-    Heads hd;
-    {
-      Emb e;                          // forward-only: the backward re-creates the embedding tile by tile
-      embed(e, pe, g);
-      PT(1);
-      mlp_forward<FEAT>(lds, c, g, e, act, hd);
-    }
-    PT(2);
-    if (MASKS) {                      // test hook: ReLU branch bits of this lane's sample
-      uint8_t* dst = a.relu_masks + (((long)k * R + (valid ? ray : 0)) * S + (slot - q * S)) * 24;
-      write_relu_mask(dst, 0, lane >> 4, act.h1, valid);
-      write_relu_mask(dst, 1, lane >> 4, act.h2, valid);
-      write_relu_mask(dst, 2, lane >> 4, act.h3, valid);
-      write_relu_mask(dst, 3, lane >> 4, act.h4, valid);
-      write_relu_mask(dst, 4, lane >> 4, act.hc, valid);
-      if (FEAT) write_relu_mask(dst, 5, lane >> 4, act.hf, valid);
-    }
-    if (g == 0) {
-      s_alpha[slot] = hd.alpha;
-      s_col[slot] = hd.col[0];
-      s_col[TS + slot] = hd.col[1];
-      s_col[2 * TS + slot] = hd.col[2];
-    }
-    if (FEAT) {
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) stg[slot * HF_LD + 16 * tt + 4 * g + r] = act.hf.t[tt][r];
-      for (int i = tid; i < 32 * 32 + 33; i += NTHR) {       // this object's Gram matrix (+ wb, bb) for the tile
-        const float v = a.gram[(long)k * GRAM + i];
-        if (i < 1024) stg[OFF_GBUF + (i >> 5) * 33 + (i & 31)] = v;
-        else stg[OFF_GBUF + 32 * 33 + (i - 1024)] = v;
-      }
-    }
-    // ray inputs of this wave's compositing pass, requested BEFORE the barrier so their latency hides behind it
-    auto ray_inputs = [&](const int ps_, float& zz_, float& gtd_, float& gr_, float& gg_, float& gb_, int& lab_) {
-      const int rpp_ = 64 / S;
-      const int ql_ = lane / S, pos_ = lane - ql_ * S;
-      const int qq_ = ps_ * rpp_ + ql_;
-      const int rayq_ = ray0 + qq_;
-      zz_ = 0.f; gtd_ = 0.f; gr_ = 0.f; gg_ = 0.f; gb_ = 0.f; lab_ = 2;
-      if ((ql_ < rpp_) && (qq_ < TR) && (rayq_ < R)) {
-        const long rr = (long)k * R + rayq_;
-        zz_ = a.z[rr * S + pos_];
-        gtd_ = a.gt_depth[rr];
-        gr_ = a.gt_rgb[rr * 3]; gg_ = a.gt_rgb[rr * 3 + 1]; gb_ = a.gt_rgb[rr * 3 + 2];
-        lab_ = a.labels[rr];
-      }
-    };
-    float pf_zz = 0.f, pf_gtd = 0.f, pf_gr = 0.f, pf_gg = 0.f, pf_gb = 0.f;
-    int pf_lab = 2;
-    if (w * (64 / S) < TR) ray_inputs(w, pf_zz, pf_gtd, pf_gr, pf_gg, pf_gb, pf_lab);
-    // feature term: (u[hh], beta, |g|, label) of ray pair (qb, half) -- same idea, first pair of the pass
-    auto feat_inputs = [&](const int ps_, const int qb_, float& uh_, float& beta_, float& ngv_, int& lab_) {
-      const int rpp_ = 64 / S;
-      const int ql2_ = qb_ + (lane >> 5);
-      const int qq2_ = ps_ * rpp_ + ql2_;
-      const int ray2_ = ray0 + qq2_;
-      uh_ = 0.f; beta_ = 0.f; ngv_ = 1.f; lab_ = 2;
-      if ((ql2_ < rpp_) && (qq2_ < TR) && (ray2_ < R)) {
-        const long rr2_ = (long)k * R + ray2_;
-        uh_ = a.rayin[rr2_ * RAYIN + (lane & 31)];
-        beta_ = a.rayin[rr2_ * RAYIN + 32];
-        ngv_ = a.rayin[rr2_ * RAYIN + 33];
-        lab_ = (int)a.labels[rr2_];
-      }
-    };
-    float pf_uh = 0.f, pf_beta = 0.f, pf_ngv = 1.f;
-    int pf_lab2 = 2;
-    if (FEAT && S == 64) {
-      if (valid) {        // every wave takes part in its ray's feature term (below)
-        const long rr2_ = (long)k * R + ray;
-        pf_uh = a.rayin[rr2_ * RAYIN + (lane_l & 31)];
-        pf_beta = a.rayin[rr2_ * RAYIN + 32];
-        pf_ngv = a.rayin[rr2_ * RAYIN + 33];
-        pf_lab2 = (int)a.labels[rr2_];
-      }
-    } else if (FEAT && w * (64 / S) < TR) feat_inputs(w, 0, pf_uh, pf_beta, pf_ngv, pf_lab2);
-    TILE_SYNC();
-    RELAUNDER();
-    PT(3);
-    // ---------------------------------------------------------------- 2. composite + loss (loss.py:27-101)
-    auto composite_passes = [&](const auto& sg) {
-      const int rpp = 64 / S;                       // rays per wave pass
-      const int npass = (TR + rpp - 1) / rpp;
-      for (int ps = w; ps < npass; ps += NWAVE) {
-        const int ql = lane / S, pos = lane - ql * S;
-        const int qq = ps * rpp + ql;
-        const int rayq = ray0 + qq;
-        const bool on = (ql < rpp) && (qq < TR) && (rayq < R);
-        const int sl = qq * S + pos;
-        float al = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, zz = pf_zz;
-        float gtd = pf_gtd, gr = pf_gr, gg = pf_gg, gb = pf_gb;
-        int lab = pf_lab;
-        if (ps != w) ray_inputs(ps, zz, gtd, gr, gg, gb, lab);      // (only when a tile has more than 8 passes)
-        if (on) { al = s_alpha[sl]; c0 = s_col[sl]; c1 = s_col[TS + sl]; c2 = s_col[2 * TS + sl]; }
-        const float occ = on ? sigmoid_acc(al) : 0.0f;               // render_rays.py:13
-        const float fr = on ? (1.0f - occ) + 1e-10f : 1.0f;          // render_rays.py:38
-        const float Pinc = sg.scan_mul(fr, pos);
-        float T = __shfl_up(Pinc, 1, 64);
-        if (pos == 0) T = 1.0f;
-        const float wgt = occ * T;                                   // render_rays.py:43
-        const float D = sg.total_add(wgt * zz, pos);       // loss.py:31
-        const float O = sg.total_add(wgt, pos);            // loss.py:35
-        const float C0 = sg.total_add(wgt * c0, pos);      // loss.py:34
-        const float C1 = sg.total_add(wgt * c1, pos);
-        const float C2 = sg.total_add(wgt * c2, pos);
-        const float dz = zz - D;
-        const float V = sg.total_add(wgt * (dz * dz), pos);  // loss.py:32-33
-        const float m1 = (lab == 1) ? 1.0f : 0.0f;                   // mask_sem & mask_obj
-        const float m2 = (lab != 2) ? 1.0f : 0.0f;                   // mask_sem
-        const float tgt = (lab != 0) ? 1.0f : 0.0f;                  // mask_obj.float()
-        const float info = 1.0f / (sqrtf(V) + 1e-4f);                // render_rays.py:96-100
-        const float rd = D - gtd, r0 = C0 - gr, r1 = C1 - gg, r2 = C2 - gb, ro = O - tgt;
-        auto sgn = [](float x) { return x > 0.f ? 1.0f : (x < 0.f ? -1.0f : 0.0f); };
-        const float gD = m1 * sgn(rd) * info * inv1;
-        const float gC0 = a.color_scaling * m1 * sgn(r0) * inv1;
-        const float gC1 = a.color_scaling * m1 * sgn(r1) * inv1;
-        const float gC2 = a.color_scaling * m1 * sgn(r2) * inv1;
-        const float gO = a.opacity_scaling * m2 * sgn(ro) * inv2;
-        if (on && pos == 0) {
-          l_d += m1 * fabsf(rd) * info * inv1;
-          l_c += m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-          l_o += m2 * fabsf(ro) * inv2;
-        }
-        float dw = gD * zz + gO + gC0 * c0 + gC1 * c1 + gC2 * c2;
-        if (FEAT) {
-          // ---- feature-distillation term (loss.py:82-99) with the linear 512-d head hoisted past the
-          // compositing: F = W_of fh + b_of O,  fh = sum_s w_s hf_s.  cos(F, g) only needs
-          //   F.g = fh.u + O beta,   |F|^2 = fh^T G fh + 2 O wb.fh + O^2 bb     (u, beta, G, wb, bb precomputed)
-          float* s_w = stg + OFF_SW;
-          float* s_gfh = stg + OFF_GFH;
-          float* s_gof = stg + OFF_GOF;
-          float* s_fhb = stg + OFF_FHB + 64 * w;
-          const float* Gb = stg + OFF_GBUF;
-          if (on) s_w[sl] = wgt;
-          if (on && pos == 0) s_gof[16 + qq] = O;
-          __builtin_amdgcn_wave_barrier();
-          asm volatile("" ::: "memory");
-          const int half = lane >> 5, hh = lane & 31;
-          for (int qb = 0; qb < rpp; qb += 2) {
-            const int ql2 = qb + half;
-            const int qq2 = ps * rpp + ql2;
-            const int ray2 = ray0 + qq2;
-            const bool on2 = (ql2 < rpp) && (qq2 < TR) && (ray2 < R);
-            const long rr2 = (long)k * R + (on2 ? ray2 : 0);
-            float fh = 0.f;
-            if (rpp == 1) {
-              // one ray per pass (S = 33..64): both 32-lane halves work on it, half the samples each
-              const bool on1 = (qb < rpp) && (ps * rpp + qb < TR) && (ray0 + ps * rpp + qb < R);
-              const int q1 = ps * rpp + qb;
-              if (on1) {
-                // four independent partial sums: the LDS reads of several steps are in flight together
-                float f0 = 0.f, f1 = 0.f, f2 = 0.f, f3 = 0.f;
-                const float* wp = s_w + q1 * S;
-                const float* hp = stg + (q1 * S) * HF_LD + hh;
-                int s2 = half;
-                for (; s2 + 6 < S; s2 += 8) {
-                  f0 = fmaf(wp[s2], hp[s2 * HF_LD], f0);
-                  f1 = fmaf(wp[s2 + 2], hp[(s2 + 2) * HF_LD], f1);
-                  f2 = fmaf(wp[s2 + 4], hp[(s2 + 4) * HF_LD], f2);
-                  f3 = fmaf(wp[s2 + 6], hp[(s2 + 6) * HF_LD], f3);
-                }
-                for (; s2 < S; s2 += 2) f0 = fmaf(wp[s2], hp[s2 * HF_LD], f0);
-                fh = (f0 + f1) + (f2 + f3);
-              }
-              fh += __shfl_xor(fh, 32, 64);
-            } else if (on2) {
-              for (int s2 = 0; s2 < S; ++s2) fh = fmaf(s_w[qq2 * S + s2], stg[(qq2 * S + s2) * HF_LD + hh], fh);
-            }
-            s_fhb[half * 32 + hh] = fh;
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("" ::: "memory");
-            float Gfh = 0.f;
-#pragma unroll 8
-            for (int h2 = 0; h2 < 32; ++h2) Gfh = fmaf(Gb[hh * 33 + h2], s_fhb[half * 32 + h2], Gfh);
-            const float wbh = Gb[32 * 33 + hh], bb = Gb[32 * 33 + 32];
-            float uh = pf_uh, beta = pf_beta, ngv = pf_ngv;
-            int lab2 = pf_lab2;
-            if (ps != w || qb != 0) feat_inputs(ps, qb, uh, beta, ngv, lab2);
-            const float O2 = on2 ? s_gof[16 + qq2] : 0.f;
-            const float fu = wave_sum32(fh * uh), fGf = wave_sum32(fh * Gfh), fwb = wave_sum32(fh * wbh);
-            const float dotFg = fu + O2 * beta;
-            const float nF2 = fmaxf(fGf + 2.0f * O2 * fwb + O2 * O2 * bb, 0.0f);
-            const float nF = fmaxf(sqrtf(nF2), 1e-8f), ngc = fmaxf(ngv, 1e-8f);
-            const float cosv = dotFg / (nF * ngc);
-            const float mm1 = (lab2 == 1) ? 1.0f : 0.0f;
-            const float gam = -a.feat_scaling * mm1 * inv1;         // d total / d cos
-            const float ar = gam / (nF * ngc), cr = -gam * cosv / (nF * nF);
-            if (on2) {
-              if (hh == 0) {
-                l_f += mm1 * (1.0f - cosv) * inv1;
-                s_gof[qq2] = ar * beta + cr * (fwb + O2 * bb);       // d total / d opacity (feature part)
-                a.rayfeat[rr2 * RAYFEAT + 32] = O2;      // layout (fh[32], O, a, c): [fh | O] is a GEMM operand
-                a.rayfeat[rr2 * RAYFEAT + 33] = ar;
-                a.rayfeat[rr2 * RAYFEAT + 34] = cr;
-              }
-              s_gfh[qq2 * 32 + hh] = ar * uh + cr * (Gfh + O2 * wbh);   // d total / d fh
-              a.rayfeat[rr2 * RAYFEAT + hh] = fh;
-            }
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("" ::: "memory");
-          }
-          if (on) {
-            float dwf = s_gof[qq];
-#pragma unroll 8
-            for (int h2 = 0; h2 < 32; ++h2) dwf = fmaf(s_gfh[qq * 32 + h2], stg[sl * HF_LD + h2], dwf);
-            dw += dwf;
-          }
-        }
-        const float qv = dw * wgt;
-        const float suf = sg.rscan_add(qv, pos) - qv;            // sum_{j>i} dL/dw_j * w_j
-        const float docc = dw * T - suf / fr;
-        if (on) {                                                    // in place: this lane owns slot sl
-          s_alpha[sl] = 10.0f * (docc * occ * (1.0f - occ));         // d / d raw alpha (model.py:88)
-          s_col[sl] = gC0 * wgt * c0 * (1.0f - c0);                  // d / d raw colour (pre-sigmoid)
-          s_col[TS + sl] = gC1 * wgt * c1 * (1.0f - c1);
-          s_col[2 * TS + sl] = gC2 * wgt * c2 * (1.0f - c2);
-        }
-      }
-    };
-    if (FEAT && S == 64) {
-      // 64 samples per ray (the north-star shape): the feature term's reductions over samples and hidden features
-      // are spread over all 8 waves instead of running on the two compositing waves (3 extra barriers, a much
-      // shorter critical path).  Wave w holds samples 16w..16w+15 of ray w >> 2.  Same arithmetic as the
-      // general path above.
-      const SegRows& sg = seg_rows;
-      float* s_w = stg + OFF_SW;
-      float* s_gfh = stg + OFF_GFH;
-      float* s_gof = stg + OFF_GOF;
-      float* s_part = s_gfh + 192;          // [NWAVE][32] partial composited features (s_gfh holds 2 rays here)
-      float* s_dwf = s_gfh + 64;            // [128]
-      const int pos = lane_l;
-      const int sl = w * 64 + pos;
-      const bool on = (w < TR) && (ray0 + w < R);
-      float occ = 0.f, fr = 1.f, T = 1.f, wgt = 0.f, dw = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, gC0 = 0.f, gC1 = 0.f, gC2 = 0.f;
-      if (w < TR) {
-        const float zz = pf_zz;
-        float al = 0.f;
-        if (on) { al = s_alpha[sl]; c0 = s_col[sl]; c1 = s_col[TS + sl]; c2 = s_col[2 * TS + sl]; }
-        occ = on ? sigmoid_acc(al) : 0.0f;
-        fr = on ? (1.0f - occ) + 1e-10f : 1.0f;
-        const float Pinc = sg.scan_mul(fr, pos);
-        T = __shfl_up(Pinc, 1, 64);
-        if (pos == 0) T = 1.0f;
-        wgt = occ * T;
-        const float D = sg.total_add(wgt * zz, pos);
-        const float O = sg.total_add(wgt, pos);
-        const float C0 = sg.total_add(wgt * c0, pos);
-        const float C1 = sg.total_add(wgt * c1, pos);
-        const float C2 = sg.total_add(wgt * c2, pos);
-        const float dz = zz - D;
-        const float V = sg.total_add(wgt * (dz * dz), pos);
-        const float m1 = (pf_lab == 1) ? 1.0f : 0.0f;
-        const float m2 = (pf_lab != 2) ? 1.0f : 0.0f;
-        const float tgt = (pf_lab != 0) ? 1.0f : 0.0f;
-        const float info = 1.0f / (sqrtf(V) + 1e-4f);
-        const float rd = D - pf_gtd, r0 = C0 - pf_gr, r1 = C1 - pf_gg, r2 = C2 - pf_gb, ro = O - tgt;
-        auto sgn = [](float x) { return x > 0.f ? 1.0f : (x < 0.f ? -1.0f : 0.0f); };
-        const float gD = m1 * sgn(rd) * info * inv1;
-        gC0 = a.color_scaling * m1 * sgn(r0) * inv1;
-        gC1 = a.color_scaling * m1 * sgn(r1) * inv1;
-        gC2 = a.color_scaling * m1 * sgn(r2) * inv1;
-        const float gO = a.opacity_scaling * m2 * sgn(ro) * inv2;
-        if (on && pos == 0) {
-          l_d += m1 * fabsf(rd) * info * inv1;
-          l_c += m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-          l_o += m2 * fabsf(ro) * inv2;
-          s_gof[16 + w] = O;
-        }
-        dw = gD * zz + gO + gC0 * c0 + gC1 * c1 + gC2 * c2;
-        if (on) s_w[sl] = wgt;
-      }
-      __syncthreads();
-      {
-        const float wv = valid ? s_w[slot] : 0.0f;
-        float v8[8];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v8[4 * tt + r] = wv * stg[slot * HF_LD + 16 * tt + 4 * g + r];
-        const float psum = slot_sums8(v8, c);
-        if (c < 8) s_part[w * 32 + 16 * ((c & 7) >> 2) + 4 * g + (c & 3)] = psum;
-      }
-      __syncthreads();
-      {
-        float* s_fhb = stg + OFF_FHB + 64 * w;
-        const float* Gb = stg + OFF_GBUF;
-        const int half = lane_l >> 5, hh = lane_l & 31;
-        const int w0 = w & ~3;
-        const float fh = valid ? (s_part[w0 * 32 + hh] + s_part[(w0 + 1) * 32 + hh]) +
-                                 (s_part[(w0 + 2) * 32 + hh] + s_part[(w0 + 3) * 32 + hh]) : 0.0f;
-        if (half == 0) s_fhb[hh] = fh;
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("" ::: "memory");
-        float Gp = 0.f;
-#pragma unroll
-        for (int h2 = 0; h2 < 16; ++h2) Gp = fmaf(Gb[hh * 33 + 16 * half + h2], s_fhb[16 * half + h2], Gp);
-        const float Gfh = Gp + __shfl_xor(Gp, 32, 64);
-        const float wbh = Gb[32 * 33 + hh], bb = Gb[32 * 33 + 32];
-        const float uh = pf_uh, beta = pf_beta, ngv = pf_ngv;
-        const float O2 = valid ? s_gof[16 + q] : 0.f;
-        const float fu = wave_sum32(fh * uh), fGf = wave_sum32(fh * Gfh), fwb = wave_sum32(fh * wbh);
-        const float dotFg = fu + O2 * beta;
-        const float nF2 = fmaxf(fGf + 2.0f * O2 * fwb + O2 * O2 * bb, 0.0f);
-        const float nF = fmaxf(sqrtf(nF2), 1e-8f), ngc = fmaxf(ngv, 1e-8f);
-        const float cosv = dotFg / (nF * ngc);
-        const float mm1 = (pf_lab2 == 1) ? 1.0f : 0.0f;
-        const float gam = -a.feat_scaling * mm1 * inv1;
-        const float ar = gam / (nF * ngc), cr = -gam * cosv / (nF * nF);
-        const float gfh = ar * uh + cr * (Gfh + O2 * wbh);
-        const float gof = ar * beta + cr * (fwb + O2 * bb);
-        if (valid && (w & 3) == 0 && half == 0) {
-          const long rr2 = (long)k * R + ray;
-          if (hh == 0) {
-            l_f += mm1 * (1.0f - cosv) * inv1;
-            a.rayfeat[rr2 * RAYFEAT + 32] = O2;
-            a.rayfeat[rr2 * RAYFEAT + 33] = ar;
-            a.rayfeat[rr2 * RAYFEAT + 34] = cr;
-          }
-          s_gfh[q * 32 + hh] = gfh;
-          a.rayfeat[rr2 * RAYFEAT + hh] = fh;
-        }
-        if (half == 0) s_fhb[32 + hh] = gfh;
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("" ::: "memory");
-        float dp = 0.f;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            dp = fmaf(s_fhb[32 + 16 * tt + 4 * g + r], stg[slot * HF_LD + 16 * tt + 4 * g + r], dp);
-        const float dwf = xgroup_sum(dp) + gof;
-        if (g == 0 && valid) s_dwf[slot] = dwf;
-      }
-      __syncthreads();
-      if (w < TR) {
-        if (on) dw += s_dwf[sl];
-        const float qv = dw * wgt;
-        const float suf = sg.rscan_add(qv, pos) - qv;
-        const float docc = dw * T - suf / fr;
-        if (on) {
-          s_alpha[sl] = 10.0f * (docc * occ * (1.0f - occ));
-          s_col[sl] = gC0 * wgt * c0 * (1.0f - c0);
-          s_col[TS + sl] = gC1 * wgt * c1 * (1.0f - c1);
-          s_col[2 * TS + sl] = gC2 * wgt * c2 * (1.0f - c2);
-        }
-      }
-    } else if (rows_mode) composite_passes(seg_rows); else composite_passes(SegGeneric{S});
-    PT(4);
-    TILE_SYNC();
-    RELAUNDER();
-    PT(5);
-    // ---------------------------------------------------------------- 3. backward
-    const float da = valid ? s_alpha[slot] : 0.0f;
-    const float dc0 = valid ? s_col[slot] : 0.0f;
-    const float dc1 = valid ? s_col[TS + slot] : 0.0f;
-    const float dc2 = valid ? s_col[2 * TS + slot] : 0.0f;
-    if (g == 0) { g_ba += da; g_boc0 += dc0; g_boc1 += dc1; g_boc2 += dc2; }
-    // The sincos of the embedding is RE-computed below: hide ps from CSE, otherwise the compiler keeps every
-    // forward cos value live across the whole backward pass.
-#pragma unroll
-    for (int j = 0; j < OBJ_NDIR; ++j) asm volatile("" : "+v"(pe.ps[j]));
-    float dps[OBJ_NDIR];
-#pragma unroll
-    for (int j = 0; j < OBJ_NDIR; ++j) dps[j] = 0.f;
-
-    // ---- phase A: heads, colour layer, (feature layer,) mid2
-    T32 d_hf = zero32();
-    if (FEAT) {
-      const float wv = valid ? stg[OFF_SW + slot] : 0.0f;
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float gv = valid ? stg[OFF_GFH + q * 32 + 16 * tt + 4 * g + r] : 0.0f;
-          d_hf.t[tt][r] = act.hf.t[tt][r] > 0.0f ? wv * gv : 0.0f;
-        }
-      // (rows 80..95, where s_w / gfh live, are not touched by the phase-A staging below)
-    }
-    T32 d_hc, d_h4;
-    float pa_[8], pb_[8], pc_[8], pd_[8];       // head-weight gradient products, summed over the samples below
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * tt + 4 * g + r;
-        const int s = 4 * tt + r;
-        const float hv = act.hc.t[tt][r];
-        pa_[s] = da * act.h4.t[tt][r];
-        pb_[s] = dc0 * hv;
-        pc_[s] = dc1 * hv;
-        pd_[s] = dc2 * hv;
-        const float dv = fmaf(lds[OFF_WOC + 2 * H + row], dc2, fmaf(lds[OFF_WOC + H + row], dc1, lds[OFF_WOC + row] * dc0));
-        d_hc.t[tt][r] = hv > 0.0f ? dv : 0.0f;
-        d_h4.t[tt][r] = lds[OFF_WA + row] * da;
-      }
-    // group A staging: [h4 | x2] rows 0..79, h3 rows 96..127, d_hc rows 128.., d_h4pre rows 160..
-    gS0 += slot_sums16(pa_, pb_, c);
-    gS1 += slot_sums16(pc_, pd_, c);
-    asm volatile("" : "+v"(gS0), "+v"(gS1));
-    store_T32(stg_lane, 0, act.h4);
-    store_T32(stg_lane, 96, act.h3);
-    store_T32(stg_lane, 128, d_hc);
-    mma_bwd32<ST_CL>(d_h4, wt_cl, 0, d_hc);
-    if (FEAT) mma_bwd32<ST_CL>(d_h4, wt_fl, 0, d_hf);
-    d_h4 = relu_mask32(d_h4, act.h4);
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) pa_[4 * tt + r] = d_h4.t[tt][r];
-    {
-      const float sv = slot_sums8(pa_, c);
-      gS2 += (c >= 8) ? sv : 0.0f;
-      asm volatile("" : "+v"(gS2));
-    }
-    store_T32(stg_lane, 160, d_h4);
-    // PE backward, x2 part, one 16-row tile at a time
-#pragma unroll
-    for (int T = 0; T < X2N; ++T) {
-      f32x4 d_x = zero4();
-      mma_bwd16<ST_CL>(d_x, wt_cl, 32 + 16 * T, d_hc);
-      if (FEAT) mma_bwd16<ST_CL>(d_x, wt_fl, 32 + 16 * T, d_hf);
-      store_T16(stg_lane, 32 + 16 * T, pe_x2_tile_fb(pe, T, g, d_x, dps));
-    }
-    T32 d_h3 = zero32();
-    mma_bwd32<ST_M>(d_h3, wt_m2, 0, d_h4);
-    d_h3 = relu_mask32(d_h3, act.h3);
-    PT(6);
-    TILE_SYNC();
-    RELAUNDER();
-    PT(7);
-    if (w < 7) {
-      const int dTr = (w < 5) ? 128 : 160;
-      const int aTr = (w < 5) ? 16 * w : 96 + 16 * (w - 5);
-      wgrad_pair(accA0, accA1, lane_rd + dTr * STG_LD, lane_rd + aTr * STG_LD);
-    }
-    PT(8);
-    TILE_SYNC();
-    RELAUNDER();
-    PT(9);
-    if (FEAT) {             // feature layer weight gradient: same inputs [h4 | x2], d_hf in place of d_hc
-      store_T32(stg_lane, 128, d_hf);
-      TILE_SYNC();
-    RELAUNDER();
-      if (w < 5) wgrad_pair(accF0, accF1, lane_rd + 128 * STG_LD, lane_rd + (16 * w) * STG_LD);
-      TILE_SYNC();
-    RELAUNDER();
-    }
-    // ---- phase B: cat layer.  [h2 | x1] rows 0..127, d_h3pre rows 128..
-    store_T32(stg_lane, 0, act.h2);
-    store_T32(stg_lane, 128, d_h3);
-    T32 d_h2 = zero32();
-    mma_bwd32<ST_CAT>(d_h2, wt_cat, 0, d_h3);
-    d_h2 = relu_mask32(d_h2, act.h2);
-    float pa2_[8];
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) pa2_[4 * tt + r] = d_h2.t[tt][r];
-    {
-      const float sv = slot_sums8(pa2_, c);
-      gS2 += (c < 8) ? sv : 0.0f;
-      asm volatile("" : "+v"(gS2));
-    }
-    T32 d_h1 = zero32();
-    mma_bwd32<ST_M>(d_h1, wt_m1, 0, d_h2);
-    d_h1 = relu_mask32(d_h1, act.h1);
-    // PE backward, x1 part: d x1 tile = cat^T d_h3 + in^T d_h1, consumed tile by tile
-#pragma unroll
-    for (int T = 0; T < X1N; ++T) {
-      f32x4 d_x = zero4();
-      mma_bwd16<ST_CAT>(d_x, wt_cat, 32 + 16 * T, d_h3);
-      mma_bwd16<ST_IN>(d_x, wt_in, 16 * T, d_h1);
-      store_T16(stg_lane, 32 + 16 * T, pe_x1_tile_fb(pe, T, g, d_x, dps));
-    }
-    PT(10);
-    // d ps[i] of lane group g belongs to direction j = (i + 4g) mod 21, doubled when it wrapped into the next
-    // octave.  The four groups of a sample are summed ON THE MATRIX CORE: one 16x16x4 MFMA per register i with
-    // B = d ps[i] (k = lane group, n = sample) and a 0/1/2 selection matrix A[row][k] = [row == j(i, k)] * factor
-    // scatters the four values into rows j of a 32-row d-projection tile (exact: products by 0, 1, 2).  No LDS
-    // atomics (ds_add_f32 retires ~1 lane/clk for the whole CU: 8 waves x 21 of them cost ~10 % of the kernel).
-    {
-      T32 dpj = zero32();
-#pragma unroll
-      for (int i = 0; i < OBJ_NDIR; ++i) {
-        bool need[2] = {false, false};
-#pragma unroll
-        for (int gg = 0; gg < 4; ++gg) {
-          const int mm = 4 * gg + i;
-          need[((i > 8 && mm >= OBJ_NDIR) ? mm - OBJ_NDIR : mm) >> 4] = true;
-        }
-        const int m = 4 * g + i;
-        const bool wrap = (i > 8) && (m >= OBJ_NDIR);
-        const int j = wrap ? m - OBJ_NDIR : m;
-        const float f = wrap ? 2.0f : 1.0f;
-        if (need[0]) dpj.t[0] = OBJ_MFMA((j == c) ? f : 0.0f, dps[i], dpj.t[0]);
-        if (need[1]) dpj.t[1] = OBJ_MFMA((j - 16 == c) ? f : 0.0f, dps[i], dpj.t[1]);
-      }
-      store_T32(stg_lane, 160, dpj);      // rows 160..180 (181..191: zeros), free in phase B
-      // d B[j][x] += sum over THIS wave's 16 samples of dproj[j][s] t[x][s] (embedding.py:48): the wave re-reads
-      // its own columns as MFMA operands (A = table rows, B = the t rows 32..34 of the x1 staging)
-      __builtin_amdgcn_wave_barrier();
-      asm volatile("" ::: "memory");
-      const float* ta = stg + (160 + c) * STG_LD + 16 * w + g;
-      const float* tb = stg + (32 + (c < 3 ? c : 2)) * STG_LD + 16 * w + g;
-#pragma unroll
-      for (int st = 0; st < 4; ++st) {
-        const float bv = (c < 3) ? tb[4 * st] : 0.0f;
-        accT0 = OBJ_MFMA(ta[4 * st], bv, accT0);
-        accT1 = OBJ_MFMA(ta[16 * STG_LD + 4 * st], bv, accT1);
-      }
-    }
-    PT(11);
-    TILE_SYNC();
-    RELAUNDER();
-    PT(12);
-    wgrad_pair(accB0, accB1, lane_rd + 128 * STG_LD, lane_rd + (16 * w) * STG_LD);
-    PT(13);
-    TILE_SYNC();
-    RELAUNDER();
-    // ---- phase C: in layer (x1 stays at rows 32..127) + mid1.  h1 rows 0.., d_h1pre 128.., d_h2pre 160..
-    fetch_point(tile + a.G, slot, nx, ny, nz);
-    store_T32(stg_lane, 0, act.h1);
-    store_T32(stg_lane, 128, d_h1);
-    store_T32(stg_lane, 160, d_h2);
-    PT(14);
-    TILE_SYNC();
-    RELAUNDER();
-    PT(15);
-    {
-      const int dTr = (w < 6) ? 128 : 160;
-      const int aTr = (w < 6) ? 32 + 16 * w : 16 * (w - 6);
-      wgrad_pair(accC0, accC1, lane_rd + dTr * STG_LD, lane_rd + aTr * STG_LD);
-    }
-    PT(16);
-    // The staging area is next written in phase A of the following tile, two barriers from here; only the feature
-    // build writes it earlier (its hidden-feature buffer after the forward pass) and needs this barrier.
-    if (FEAT) TILE_SYNC();
-    RELAUNDER();
-    PT(17);
-  }
-  PT_FLUSH();
-#undef c
-#undef g
-#undef wt_fl
-#undef stg_lane
-#undef lane_rd
-#undef wt_in
-#undef wt_m1
-#undef wt_cat
-#undef wt_m2
-#undef wt_cl
-
-  // ------------------------------------------------------------------ write this workgroup's slab
-  float* slab = a.slab + ((long)k * a.G + gi) * a.slab_stride;
-  const Layout& L = a.L;
-  if (w < 5) write_pair(slab, accA0, accA1, c, g, w, L.cl_w, H + OBJ_E2, L.cl_b);
-  else if (w < 7) write_pair(slab, accA0, accA1, c, g, w - 5, L.m2_w, H, -1);
-  write_pair(slab, accB0, accB1, c, g, w, L.cat_w, H + OBJ_E1, L.cat_b);
-  if (w < 6) write_pair(slab, accC0, accC1, c, g, w, L.in_w, OBJ_E1, L.in_b);
-  else write_pair(slab, accC0, accC1, c, g, w - 6, L.m1_w, H, -1);
-  if (FEAT && w < 5) write_pair(slab, accF0, accF1, c, g, w, L.fl_w, H + OBJ_E2, L.fl_b);
-  // slot registers -> LDS (per wave), then sum the 8 waves
-  __syncthreads();    // the last tile's weight-gradient reads of the staging area are done
-  float* red = stg;   // [NWAVE][NRED]
-  {
-    float* mine = red + w * NRED;
-    const int s = c & 7;
-    const int row = 16 * (s >> 2) + 4 * g + (s & 3);
-    if (c < 8) { mine[64 + row] = gS0; mine[128 + row] = gS1; mine[row] = gS2; }          // wa, woc1, bm1
-    else { mine[96 + row] = gS0; mine[160 + row] = gS1; mine[32 + row] = gS2; }           // woc0, woc2, bm2
-    const float s0 = wave_sum64(g_ba), s1 = wave_sum64(g_boc0), s2 = wave_sum64(g_boc1), s3 = wave_sum64(g_boc2);
-    if (lane == 0) { mine[192] = s0; mine[193] = s1; mine[194] = s2; mine[195] = s3; }
-    const float e0 = wave_sum64(l_d), e1 = wave_sum64(l_c), e2 = wave_sum64(l_o);
-    const float e3 = wave_sum64(l_f);
-    if (lane == 0) { mine[196] = e0; mine[197] = e1; mine[198] = e2; mine[199] = e3; }
-    if (c < 3) {
-      float* dbw = red + NWAVE * NRED + w * 64;            // d B partial of this wave: [21 * 3]
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        dbw[(4 * g + r) * 3 + c] = accT0[r];
-        if (16 + 4 * g + r < OBJ_NDIR) dbw[(16 + 4 * g + r) * 3 + c] = accT1[r];
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < 3 * OBJ_NDIR) {
-    float v = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < NWAVE; ++ww) v += red[NWAVE * NRED + ww * 64 + tid];
-    slab[L.pe_b + tid] = v;
-  }
-  for (int i = tid; i < NRED; i += NTHR) {
-    float v = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < NWAVE; ++ww) v += red[ww * NRED + i];
-    if (i < 32) slab[L.m1_b + i] = v;
-    else if (i < 64) slab[L.m2_b + i - 32] = v;
-    else if (i < 96) slab[L.a_w + i - 64] = v;
-    else if (i < 192) slab[L.oc_w + i - 96] = v;
-    else if (i == 192) slab[L.a_b] = v;
-    else if (i < 196) slab[L.oc_b + i - 193] = v;
-    else a.loss_part[((long)k * a.G + gi) * 4 + (i - 196)] = v;
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // The step's last launch: grads[k][i] = sum_g slab[k][g][i] for every entry this configuration differentiates,
@@ -1470,22 +698,46 @@ static void choose_flat(TrainDev& d, int K, const long TILE_EQUIV) {
   if (cost_flat < cost_strided && gs <= grid_cap(K)) { d.flat_nwg = cu; d.Gs = (int)gs; }
 }
 
+// The hidden-32 step's workspace, laid out in one place: objnerf_train_workspace_bytes sizes it (base 0),
+// objnerf_train_step hands out its regions.  Every region starts on a 256-byte boundary.
+struct Workspace32 {
+  float* slab;                  // [K][grid_cap(K)][ps]: the partial-gradient slabs (grid_cap bounds the workgroups per object)
+  float* loss_part;             // [K][grid_cap(K)][4]
+  // the feature loss only (NULL without it)
+  float *rayin, *gram, *rayfeat;
+  float *X1, *X2;               // [K][R][XCOLS] each, adjacent: the one-pass route keeps its partials in the room of both
+  float *Tm, *mom;              // [K][C][XCOLS] | [K][XCOLS][XCOLS], one region
+  float *parts_t, *parts_m;     // objgen::wgrad_f32's split-K partials of Tm and mom
+  float* head_snap;             // [K][C][XCOLS]: feat_pre_kernel's copy of [W_of | b_of] for finalize_kernel
+  size_t bytes;
+};
+static Workspace32 workspace32(uintptr_t base, int K, int R, int C, int64_t ps, bool feat) {
+  Workspace32 w = {};
+  auto take = [&](size_t floats) { float* p = (float*)(base + w.bytes); w.bytes += align256(floats * 4); return p; };
+  w.slab = take((size_t)K * grid_cap(K) * ps);
+  w.loss_part = take((size_t)K * grid_cap(K) * 4);
+  if (feat) {
+    w.rayin = take((size_t)K * R * RAYIN);
+    w.gram = take((size_t)K * GRAM);
+    w.rayfeat = take((size_t)K * R * RAYFEAT);
+    w.X1 = take((size_t)K * R * XCOLS);
+    w.X2 = take((size_t)K * R * XCOLS);
+    w.Tm = take((size_t)K * C * XCOLS + (size_t)K * XCOLS * XCOLS);
+    w.mom = w.Tm + (size_t)K * C * XCOLS;
+    w.parts_t = take(objgen::wgrad_parts_floats(K, C, XCOLS, R));
+    w.parts_m = take(objgen::wgrad_parts_floats(K, XCOLS, XCOLS, R));
+    w.head_snap = take((size_t)K * C * XCOLS);
+  }
+  return w;
+}
+
 size_t objnerf_train_workspace_bytes(const objnerf_net* net, int32_t K, int32_t R, int32_t S, int32_t with_feat) {
   if (!net || K <= 0 || R <= 0 || S <= 0) return 0;
   // bit 1 of with_feat (value 2): size for the layer-wise path (OBJNERF_TRAIN_LAYERWISE)
   if (net->hidden != 32 || S > 64 || (with_feat & 2)) return objgen::train_workspace_bytes(net, K, R, S, with_feat & 1, (with_feat & 4) != 0);
-  with_feat &= 1;
   int64_t offs[OBJNERF_N_TENSORS + 1];
   const int64_t ps = objnerf_param_layout(net, offs);
-  const int Gmax = grid_cap(K);   // upper bound on the workgroups per object
-  size_t n = align256((size_t)K * Gmax * ps * 4) + align256((size_t)K * Gmax * 4 * 4) + align256((size_t)ps) + 256;
-  if (with_feat)
-    n += align256((size_t)K * R * RAYIN * 4) + align256((size_t)K * GRAM * 4) + align256((size_t)K * R * RAYFEAT * 4) +
-         2 * align256((size_t)K * R * XCOLS * 4) +
-         align256(((size_t)K * net->feat_dim * XCOLS + (size_t)K * XCOLS * XCOLS) * 4) +
-         align256(objgen::wgrad_parts_floats(K, net->feat_dim, XCOLS, R) * 4) +
-         align256(objgen::wgrad_parts_floats(K, XCOLS, XCOLS, R) * 4);
-  return n;
+  return workspace32(0, K, R, net->feat_dim, ps, (with_feat & 1) != 0).bytes;
 }
 
 int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void* stream) {
@@ -1548,11 +800,12 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
   if (feat && (TS / a->S) > 16) return OBJNERF_ENOTSUP;
   const bool bf16 = (a->mode & OBJNERF_TRAIN_BF16) != 0;
   if (bf16 && (a->relu_masks || a->emb_debug)) return OBJNERF_ENOTSUP;
-  if (a->workspace_bytes < objnerf_train_workspace_bytes(net, a->K, a->R, a->S, a->gt_feat != nullptr))
-    return OBJNERF_EINVAL;
   int64_t offs[OBJNERF_N_TENSORS + 1];
   const int64_t ps = objnerf_param_layout(net, offs);
   if (a->p_stride < offs[OBJNERF_N_TENSORS]) return OBJNERF_EINVAL;
+  const int C = net->feat_dim;
+  const Workspace32 ws = workspace32((uintptr_t)a->workspace, a->K, a->R, C, ps, feat);
+  if (a->workspace_bytes < ws.bytes) return OBJNERF_EINVAL;
 
   TrainDev d;
   d.K = a->K; d.R = a->R; d.S = a->S;
@@ -1567,34 +820,10 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
   d.gt_depth = a->gt_depth; d.gt_rgb = a->gt_rgb; d.labels = a->labels; d.gt_feat = a->gt_feat;
   d.counts = a->counts; d.flags = a->flags; d.derive_flags = self_counts ? 1 : 0;
   d.L = make_layout(net->feat_dim);
-  char* ws = (char*)a->workspace;
-  const int Gmax = grid_cap(a->K);
-  d.slab = (float*)ws;
+  d.slab = ws.slab;
   d.slab_stride = ps;
-  ws += align256((size_t)a->K * Gmax * ps * 4);
-  d.loss_part = (float*)ws;
-  ws += align256((size_t)a->K * Gmax * 4 * 4);
-  uint8_t* has_grad = (uint8_t*)ws;
-  ws += align256((size_t)ps) + 256;
-  float* rayin = nullptr; float* gram = nullptr; float* rayfeat = nullptr; float* head_snap = nullptr;
-  float *X1 = nullptr, *X2 = nullptr, *Tm = nullptr, *mom = nullptr, *parts_t = nullptr, *parts_m = nullptr;
-  const int C = net->feat_dim;
-  if (feat) {
-    rayin = (float*)ws;   ws += align256((size_t)a->K * a->R * RAYIN * 4);
-    gram = (float*)ws;    ws += align256((size_t)a->K * GRAM * 4);
-    rayfeat = (float*)ws; ws += align256((size_t)a->K * a->R * RAYFEAT * 4);
-    X1 = (float*)ws;      ws += align256((size_t)a->K * a->R * XCOLS * 4);
-    X2 = (float*)ws;      ws += align256((size_t)a->K * a->R * XCOLS * 4);
-    Tm = (float*)ws;
-    mom = Tm + (size_t)a->K * C * XCOLS;
-    ws += align256(((size_t)a->K * C * XCOLS + (size_t)a->K * XCOLS * XCOLS) * 4);
-    parts_t = (float*)ws; ws += align256(objgen::wgrad_parts_floats(a->K, C, XCOLS, a->R) * 4);
-    parts_m = (float*)ws;
-    // (the one-pass route does not use the split-K parts: the copy of [W_of | b_of] for finalize_kernel lives in their room,
-    // K C 33 floats of the K ceil(R / ..) C 33 + 64 that wgrad_parts_floats reserves)
-    head_snap = parts_t;
-  }
-  d.rayin = rayin; d.gram = gram; d.rayfeat = rayfeat;
+  d.loss_part = ws.loss_part;
+  d.rayin = ws.rayin; d.gram = ws.gram; d.rayfeat = ws.rayfeat;
   d.relu_masks = a->relu_masks;
   d.emb_debug = a->emb_debug;
 
@@ -1602,19 +831,11 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
   // (no byte mask and no zero fills: finalize_kernel takes the ranges without a gradient as arguments -- without
   // gt_feat the whole feature branch has none (train.py:435-438 -> .grad stays None); with it, the 512-d head's
   // gradient is produced by feat_finish_kernel instead of the slabs -- and writes the status word itself)
-  (void)has_grad;
-  const size_t lds_bytes = (size_t)((feat ? W_FLOATS_FEAT : W_FLOATS_NOFEAT) + SM_FLOATS + STG_ROWS * STG_LD) * 4;
-  objnerf_once_per_device([] {
-    (void)hipFuncSetAttribute((const void*)train_fused_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((W_FLOATS_FEAT + SM_FLOATS + STG_ROWS * STG_LD) * 4));
-    (void)hipFuncSetAttribute((const void*)train_fused_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((W_FLOATS_FEAT + SM_FLOATS + STG_ROWS * STG_LD) * 4));
-  });
   const float *fin_T = nullptr, *fin_M = nullptr;
   int fin_G = 0;
   if (feat) {
     const bool pre_one = C <= FEAT_PRE_MAXC && C % 16 == 0;
-    if (!pre_one) objgen::feat_gram(stream, a->K, a->params, (long)a->p_stride, d.L.of_w, d.L.of_b, C, 32, gram, GRAM);
+    if (!pre_one) objgen::feat_gram(stream, a->K, a->params, (long)a->p_stride, d.L.of_w, d.L.of_b, C, 32, ws.gram, GRAM);
     // u = gt_feat W_of  ([R x C] [C x 32] per object) on the batched MFMA GEMM; beta, |g| beside it
     if (pre_one) {
       // u, beta, |g| in one pass over gt_feat (feat_pre_kernel)
@@ -1627,22 +848,16 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
       if (gpo < 1) gpo = 1;
       if (gpo > (a->R + 127) / 128) gpo = (a->R + 127) / 128;
       hipLaunchKernelGGL(feat_pre_kernel, dim3(gpo, a->K), dim3(512), pre_lds, st, a->params, (long)a->p_stride,
-                         d.L.of_w, d.L.of_b, C, a->R, a->gt_feat, rayin, gram, head_snap, a->labels,
+                         d.L.of_w, d.L.of_b, C, a->R, a->gt_feat, ws.rayin, ws.gram, ws.head_snap, a->labels,
                          counts_in_pre ? const_cast<int32_t*>(a->counts) : nullptr);
     } else {
       objgen::gemm_f32(stream, a->K, a->R, 32, C, a->gt_feat, C, 1, (long)a->R * C, a->params + d.L.of_w, 32, 1,
-                       (long)a->p_stride, rayin, RAYIN, 1, (long)a->R * RAYIN, false);
+                       (long)a->p_stride, ws.rayin, RAYIN, 1, (long)a->R * RAYIN, false);
       hipLaunchKernelGGL(feat_rowstats_kernel, dim3((a->R + 15) / 16, a->K), dim3(256), 0, st, a->params,
-                         (long)a->p_stride, d.L.of_b, C, a->R, a->gt_feat, rayin);
+                         (long)a->p_stride, d.L.of_b, C, a->R, a->gt_feat, ws.rayin);
     }
     if (bf16) launch_train_bf16(d, stream, true);
-#ifdef OBJ_FEAT_GEN1      // diagnostic builds: the first-generation feature kernel (tools/build_variant.sh)
-    else if (d.relu_masks) hipLaunchKernelGGL((train_fused_kernel<true, true>), dim3(a->K * d.G), dim3(NTHR), lds_bytes, st, d);
-    else hipLaunchKernelGGL((train_fused_kernel<true, false>), dim3(a->K * d.G), dim3(NTHR), lds_bytes, st, d);
-#else
     else { choose_flat(d, a->K, 4); launch_train32(d, stream, true); }
-    (void)lds_bytes;
-#endif
     if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
     // 512-d head gradient from the per-ray (fh, O, a, c): two split-K GEMMs over the rays + a small finish
     const long nr = (long)a->K * a->R;
@@ -1652,23 +867,23 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
     // the partials live in the room of X1 AND X2 (adjacent in the workspace, both unused on this route): 2 K R XCOLS floats.
     // (Round 4 used X1's room only and at most 8 chunks: a rank's share of configs[3] -- 15 objects -- then ran 105
     // workgroups over 126 MB of target features, 1.1 TB/s.)
-    const size_t part_room = ((size_t)((char*)X2 - (char*)X1) / 4 + (size_t)a->K * a->R * XCOLS) / (size_t)a->K;
+    const size_t part_room = ((size_t)((char*)ws.X2 - (char*)ws.X1) / 4 + (size_t)a->K * a->R * XCOLS) / (size_t)a->K;
     while (gpo > 1 && (size_t)gpo * ((size_t)C * XCOLS + XCOLS * XCOLS) > part_room) --gpo;
     const bool one_pass = C == 512 && (size_t)gpo * ((size_t)C * XCOLS + XCOLS * XCOLS) <= part_room;
     int Gfin = 1;
-    const float *Tsrc = Tm, *Msrc = mom;
+    const float *Tsrc = ws.Tm, *Msrc = ws.mom;
     if (one_pass) {
-      float* Tpart = X1;
-      float* Mpart = X1 + (size_t)a->K * gpo * C * XCOLS;
-      hipLaunchKernelGGL(feat_post_kernel, dim3(gpo, a->K), dim3(512), 0, st, C, a->R, a->gt_feat, rayfeat, Tpart, Mpart);
+      float* Tpart = ws.X1;
+      float* Mpart = ws.X1 + (size_t)a->K * gpo * C * XCOLS;
+      hipLaunchKernelGGL(feat_post_kernel, dim3(gpo, a->K), dim3(512), 0, st, C, a->R, a->gt_feat, ws.rayfeat, Tpart, Mpart);
       Gfin = gpo; Tsrc = Tpart; Msrc = Mpart;
     } else {
-      hipLaunchKernelGGL(feat_scale_kernel, dim3((unsigned)((nr * XCOLS + 255) / 256)), dim3(256), 0, st, nr, rayfeat, X1, X2);
-      (void)hipMemsetAsync(Tm, 0, ((size_t)a->K * C * XCOLS + (size_t)a->K * XCOLS * XCOLS) * 4, st);
-      objgen::wgrad_f32(stream, a->K, C, XCOLS, a->R, a->gt_feat, 1, C, (long)a->R * C, X1, XCOLS, 1, (long)a->R * XCOLS, Tm,
-                        XCOLS, (long)C * XCOLS, parts_t, objgen::wgrad_parts_floats(a->K, C, XCOLS, a->R));
-      objgen::wgrad_f32(stream, a->K, XCOLS, XCOLS, a->R, X2, 1, XCOLS, (long)a->R * XCOLS, rayfeat, RAYFEAT, 1,
-                        (long)a->R * RAYFEAT, mom, XCOLS, (long)XCOLS * XCOLS, parts_m,
+      hipLaunchKernelGGL(feat_scale_kernel, dim3((unsigned)((nr * XCOLS + 255) / 256)), dim3(256), 0, st, nr, ws.rayfeat, ws.X1, ws.X2);
+      (void)hipMemsetAsync(ws.Tm, 0, ((size_t)a->K * C * XCOLS + (size_t)a->K * XCOLS * XCOLS) * 4, st);
+      objgen::wgrad_f32(stream, a->K, C, XCOLS, a->R, a->gt_feat, 1, C, (long)a->R * C, ws.X1, XCOLS, 1, (long)a->R * XCOLS, ws.Tm,
+                        XCOLS, (long)C * XCOLS, ws.parts_t, objgen::wgrad_parts_floats(a->K, C, XCOLS, a->R));
+      objgen::wgrad_f32(stream, a->K, XCOLS, XCOLS, a->R, ws.X2, 1, XCOLS, (long)a->R * XCOLS, ws.rayfeat, RAYFEAT, 1,
+                        (long)a->R * RAYFEAT, ws.mom, XCOLS, (long)XCOLS * XCOLS, ws.parts_m,
                         objgen::wgrad_parts_floats(a->K, XCOLS, XCOLS, a->R));
     }
     if (one_pass && pre_one) {      // finalize_kernel forms the head's gradient itself (round 6: one launch fewer)
@@ -1697,7 +912,7 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
   fa.lo1 = offs[OBJNERF_T_CL_W]; fa.lo2 = offs[OBJNERF_T_FL_W]; fa.hi2 = offs[OBJNERF_T_PE_B];
   fa.lr = fa.b1 = fa.b2 = fa.wd = 0.0; fa.eps = 0.f;
   fa.counts_in = self_counts ? a->counts : nullptr; fa.flags_out = const_cast<int*>(a->flags);
-  fa.Tpart = fin_T; fa.Mpart = fin_M; fa.head_w = head_snap; fa.Gfin = fin_G; fa.C = C; fa.of_w = d.L.of_w; fa.of_b = d.L.of_b;
+  fa.Tpart = fin_T; fa.Mpart = fin_M; fa.head_w = ws.head_snap; fa.Gfin = fin_G; fa.C = C; fa.of_w = d.L.of_w; fa.of_b = d.L.of_b;
   if (a->optim) {
     const objnerf_adamw_args* o = a->optim;
     fa.params = const_cast<float*>(a->params); fa.m = o->exp_avg; fa.v = o->exp_avg_sq; fa.steps = o->group_steps;
@@ -1708,14 +923,6 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
   if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
   return OBJNERF_OK;
 }
-
-#ifdef PHASE_TIMING
-extern "C" int objnerf_debug_phase(unsigned long long* out_host) {
-  if (hipDeviceSynchronize() != hipSuccess) return OBJNERF_ELAUNCH;
-  return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 8 * 24) == hipSuccess
-             ? OBJNERF_OK : OBJNERF_ELAUNCH;
-}
-#endif
 
 int objnerf_eval_points(const objnerf_net* net, int32_t K, int64_t N, const float* params, int64_t p_stride,
                         const float* scale, const float* pts, float* out_alpha, float* out_color, float* out_hfeat,

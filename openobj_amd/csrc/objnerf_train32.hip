@@ -1,7 +1,7 @@
 // Fused fp32 training iteration for K stacked hidden-32 object networks, second generation (gfx950).
 //
-// Same contract and tile structure as the first generation (objnerf_train.hip: its forward-only / eval kernels and
-// the host entry points): one launch = forward, compositing, losses, backward (dgrad + wgrad) of train.py:424-472; a 512-thread
+// Same contract and tile structure as the first generation (since removed; objnerf_train.hip holds the host entry
+// points, finalize_kernel and the eval kernel): one launch = forward, compositing, losses, backward (dgrad + wgrad) of train.py:424-472; a 512-thread
 // workgroup owns one object's weights in LDS and sweeps its rays in tiles of 128 samples; partial gradients leave as
 // one slab per workgroup (no global atomics, bit-reproducible).  What is new is in objnerf_mlp32.h: the
 // direction-owner positional encoding (no cross-group sums, d B in registers, one range reduction per direction for

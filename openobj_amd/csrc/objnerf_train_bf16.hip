@@ -1,5 +1,5 @@
 // bf16-operand variant of the fused training iteration (OBJNERF_TRAIN_BF16): same tile structure as
-// objnerf_train.hip (8 waves x 16 samples, whole rays, register-resident activations, LDS transposes for
+// objnerf_train32.hip (8 waves x 16 samples, whole rays, register-resident activations, LDS transposes for
 // the weight gradients) but every contraction runs on v_mfma_f32_16x16x32_bf16 with fp32 accumulation.
 //
 // One MFMA consumes a whole 32-feature block: lane (c, g) supplies k-slots 8g..8g+7 = features
@@ -120,23 +120,9 @@ __device__ __forceinline__ void write_pair_b(float* slab, const f32x4& a0, const
   }
 }
 
-#ifdef PHASE_TIMING
-__device__ unsigned long long g_phase_b[8][24];
-#define PT_INIT() unsigned long long pt_acc[18]; for (int i_ = 0; i_ < 18; ++i_) pt_acc[i_] = 0; \
-  unsigned long long pt_t0 = __builtin_amdgcn_s_memtime()
-#define PT(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pt_acc[i] += t_ - pt_t0; pt_t0 = t_; } while (0)
-#define PT_FLUSH() do { if (blockIdx.x == 0 && lane == 0) for (int i_ = 0; i_ < 18; ++i_) g_phase_b[w][i_] = pt_acc[i_]; } while (0)
-#else
-#define PT_INIT() do {} while (0)
-#define PT(i) do {} while (0)
-#define PT_FLUSH() do {} while (0)
-#endif
-
-// SS: samples per ray when known at compile time (64 = the metric shape: no integer divisions by S), 0 = any S <= 64
-template <bool FEAT, int SS>
-__global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a_) {
-  TrainDev a = a_;
-  if (SS) { a.S = SS; a.TR = TS / SS; }
+// Launched for S != 64: the 64-sample shape runs the second-generation kernels (objnerf_bf16v2_body.h)
+template <bool FEAT>
+__global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a) {
   extern __shared__ __attribute__((aligned(16))) char ldsb[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -154,7 +140,7 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
   __syncthreads();
 
   const float inv_scale = 1.0f / a.scale[k];
-  const int S = SS ? SS : a.S, R = a.R, TR = SS ? TS / SS : a.TR;
+  const int S = a.S, R = a.R, TR = a.TR;
   const float n1 = (float)a.counts[2 * k], n2 = (float)a.counts[2 * k + 1];
   int bflag0, bflag1;
   batch_flags(a, bflag0, bflag1);
@@ -168,7 +154,7 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
 #ifdef OBJ_BF16_BUTTERFLY
   constexpr bool LAZY_H = false, LAZY_B = false;
 #else
-  constexpr bool LAZY_H = !FEAT || SS != 0, LAZY_B = !FEAT;     // (the any-S feature build has no registers to spare)
+  constexpr bool LAZY_H = !FEAT, LAZY_B = !FEAT;     // (the feature build has no registers to spare)
 #endif
   float gS0 = 0.f, gS1 = 0.f, gS2 = 0.f;
   float hW[4][8], bS[2][8];
@@ -186,9 +172,9 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
   float* s_gof = s_gfh + 16 * 32;
 
 
-  const bool rows_mode = SS ? true : seg_is_rows(a.S);
+  const bool rows_mode = seg_is_rows(a.S);
   const SegRows seg_rows = SegRows::make(rows_mode ? S : 64, lane);
-  // sample position of (tile, slot); issued one tile ahead (phase C), as in objnerf_train.hip
+  // sample position of (tile, slot); issued one tile ahead (phase C), as in objnerf_train32.hip
   auto fetch_point = [&](const int tile_, const int slot_, float& x, float& y, float& z_) {
     const int q_ = slot_ / S, si_ = slot_ - q_ * S;
     const int ray_ = tile_ * TR + q_;
@@ -230,7 +216,6 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
 #define t_fl (ldsb + T_FL + c * RST + 16 * g)
   float nx, ny, nz;
   fetch_point(gi, 16 * w + c, nx, ny, nz);
-  PT_INIT();
   for (int tile = gi; tile < a.NT; tile += a.G) {
     asm volatile("" ::: "memory");
     RELAUNDER();
@@ -243,7 +228,6 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
     const float px = nx, py = ny, pz = nz;       // fetched during the previous tile's phase C
     obj32n::Pe32 pe;
     pe_project_b(sm, g, px, py, pz, inv_scale, pe);
-    PT(0);
     T32 h1, h2, h3, h4, hc;
     T32 hf = zero32();           // (feature build) dead after the forward: the backward keeps its sign mask only
     unsigned hf_mask = 0;
@@ -376,11 +360,9 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
         pf_lab2 = (int)a.labels[rr2_];
       }
     } else if (FEAT && w * (64 / S) < TR) feat_inputs(w, 0, pf_uh, pf_beta, pf_ngv, pf_lab2);
-    PT(2);
     __syncthreads();
     RELAUNDER();
-    PT(3);
-    // ---------------------------------------------------------------- 2. composite + loss (fp32, as objnerf_train.hip)
+    // ---------------------------------------------------------------- 2. composite + loss (fp32, as objnerf_train32.hip)
     auto composite_passes = [&](const auto& sg) {
       const int rpp = 64 / S;
       const int npass = (TR + rpp - 1) / rpp;
@@ -426,7 +408,7 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
         }
         float dw = gD * zz + gO + gC0 * c0 + gC1 * c1 + gC2 * c2;
         if (FEAT) {
-          // feature-distillation term with the 512-d head hoisted past the compositing (objnerf_train.hip, 4.3 of
+          // feature-distillation term with the 512-d head hoisted past the compositing (objnerf_train32.hip, 4.3 of
           // DESIGN.md): fp32 throughout, only the hidden feature itself came out of bf16 MFMAs
           float* s_fhb = stgf + FA_FHB + 64 * w;
           const float* Gb = stgf + FA_G;
@@ -638,11 +620,9 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
           s_col[2 * TS + sl] = gC2 * wgt * c2 * (1.0f - c2);
         }
       }
-    } else if (SS || rows_mode) composite_passes(seg_rows); else composite_passes(SegGeneric{S});
-    PT(4);
+    } else if (rows_mode) composite_passes(seg_rows); else composite_passes(SegGeneric{S});
     __syncthreads();
     RELAUNDER();
-    PT(5);
     // ---------------------------------------------------------------- 3. backward
     const float da = valid ? s_alpha[slot] : 0.0f;
     const float dc0 = valid ? s_col[slot] : 0.0f;
@@ -738,16 +718,13 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
     bwd_tile(d_h3.t[0], t_m2, 0, d_h4_b);
     bwd_tile(d_h3.t[1], t_m2, 16, d_h4_b);
     d_h3 = relu_mask32(d_h3, h3);
-    PT(6);
     __syncthreads();
     RELAUNDER();
-    PT(7);
     if (w < 7) {
       const int dTr = (w < 5) ? 128 : 160;
       const int aTr = (w < 5) ? 16 * w : 96 + 16 * (w - 5);
       wgrad_pair_b(accA0, accA1, lane_rd + dTr * STG_PITCH, lane_rd + aTr * STG_PITCH);
     }
-    PT(8);
     __syncthreads();
     RELAUNDER();
     if (FEAT) {             // feature layer weight gradient: same inputs [h4 | x2], d_hf in place of d_hc
@@ -760,7 +737,6 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
       RELAUNDER();
     RELAUNDER();
     }
-    PT(9);
     // ---- phase B
     store32_b(stg_lane, 0, h2);
     store32_b(stg_lane, 128, d_h3);
@@ -804,12 +780,9 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
       dB[i][1] = fmaf(dps[i], pe.t[1], dB[i][1]);
       dB[i][2] = fmaf(dps[i], pe.t[2], dB[i][2]);
     }
-    PT(11);
     __syncthreads();
     RELAUNDER();
-    PT(12);
     wgrad_pair_b(accB0, accB1, lane_rd + 128 * STG_PITCH, lane_rd + (16 * w) * STG_PITCH);
-    PT(13);
     __syncthreads();
     RELAUNDER();
     // ---- phase C
@@ -817,21 +790,16 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
     store32_b(stg_lane, 0, h1);
     store32_b(stg_lane, 128, d_h1);
     store32_b(stg_lane, 160, d_h2);
-    PT(14);
     __syncthreads();
     RELAUNDER();
-    PT(15);
     {
       const int dTr = (w < 6) ? 128 : 160;
       const int aTr = (w < 6) ? 32 + 16 * w : 16 * (w - 6);
       wgrad_pair_b(accC0, accC1, lane_rd + dTr * STG_PITCH, lane_rd + aTr * STG_PITCH);
     }
-    PT(16);
     __syncthreads();
     RELAUNDER();
-    PT(17);
   }
-  PT_FLUSH();
 #undef c
 #undef g
 #undef stg_lane
@@ -923,38 +891,20 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
 
 size_t bf16_lds_bytes() { return LDS_BYTES; }
 
-#ifdef PHASE_TIMING
-extern "C" int objnerf_debug_phase_bf16(unsigned long long* out_host) {
-  if (hipDeviceSynchronize() != hipSuccess) return OBJNERF_ELAUNCH;
-  return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_phase_b), sizeof(unsigned long long) * 8 * 24) == hipSuccess
-             ? OBJNERF_OK : OBJNERF_ELAUNCH;
-}
-#endif
-
-// OBJNERF_BF16_V1=1 (read once): keep the first-generation kernel for the 64-sample no-feature shape too (A/B runs)
-static bool bf16_first_generation() {
-  static const bool v1 = [] { const char* e = getenv("OBJNERF_BF16_V1"); return e && e[0] == '1'; }();
-  return v1;
-}
-
 void launch_train_bf16(const TrainDev& d, void* stream, bool feat) {
   objnerf_once_per_device([] {
     const auto at = hipFuncAttributeMaxDynamicSharedMemorySize;
-    (void)hipFuncSetAttribute((const void*)train_fused_bf16_kernel<false, 0>, at, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)train_fused_bf16_kernel<false, 64>, at, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)train_fused_bf16_kernel<true, 0>, at, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)train_fused_bf16_kernel<true, 64>, at, LDS_BYTES);
+    (void)hipFuncSetAttribute((const void*)train_fused_bf16_kernel<false>, at, LDS_BYTES);
+    (void)hipFuncSetAttribute((const void*)train_fused_bf16_kernel<true>, at, LDS_BYTES);
   });
-  if (d.S == 64 && !bf16_first_generation()) {
+  if (d.S == 64) {
     if (feat) launch_train_bf16_v2f(d, stream); else launch_train_bf16_v2(d, stream);
     return;
   }
   const dim3 grid(d.K * d.G), blk(NTHR);
   hipStream_t st = (hipStream_t)stream;
-  if (feat && d.S == 64) hipLaunchKernelGGL((train_fused_bf16_kernel<true, 64>), grid, blk, LDS_BYTES, st, d);
-  else if (feat) hipLaunchKernelGGL((train_fused_bf16_kernel<true, 0>), grid, blk, LDS_BYTES, st, d);
-  else if (d.S == 64) hipLaunchKernelGGL((train_fused_bf16_kernel<false, 64>), grid, blk, LDS_BYTES, st, d);
-  else hipLaunchKernelGGL((train_fused_bf16_kernel<false, 0>), grid, blk, LDS_BYTES, st, d);
+  if (feat) hipLaunchKernelGGL((train_fused_bf16_kernel<true>), grid, blk, LDS_BYTES, st, d);
+  else hipLaunchKernelGGL((train_fused_bf16_kernel<false>), grid, blk, LDS_BYTES, st, d);
 }
 
 }  // namespace objtrain

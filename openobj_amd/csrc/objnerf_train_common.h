@@ -53,10 +53,7 @@ __host__ __device__ inline int flat_wg_of(const long T, const int nwg, const lon
 constexpr int HF_LD = 33;                       // hfbuf [128][33] at stg + 0
 constexpr int OFF_GBUF = TS * HF_LD;            // G [32][33], wb [32], bb          (4224 ..)
 constexpr int OFF_FHB = OFF_GBUF + 32 * 33 + 64;   // fh exchange buffer [NWAVE][2][32] (one per wave)
-constexpr int OFF_SW = 80 * STG_LD;             // rows 80..95 are untouched by the phase-A staging
-constexpr int OFF_GFH = OFF_SW + TS;            // gfh [16][32]
-constexpr int OFF_GOF = OFF_GFH + 16 * 32;      // gO_feat [16], O [16]
-static_assert(OFF_FHB + 64 * NWAVE <= 80 * STG_LD && OFF_GOF + 32 <= 96 * STG_LD, "feat lds aliases");
+static_assert(OFF_FHB + 64 * NWAVE <= 80 * STG_LD, "feat lds aliases");
 
 
 // ReLU branch bits of one 16-sample block (test hook, objnerf_train_args.relu_masks): lane (c, g) holds features

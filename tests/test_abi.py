@@ -68,6 +68,30 @@ def test_train_workspace_sizes():
     assert size(32, 50, 4096, 64, 2) > size(32, 50, 4096, 64, 0)       # bit 1: the layer-wise path's activations
 
 
+@pytest.mark.parametrize("K,R,S,old_nofeat,old_feat", [
+    (1, 256, 32, 31492352, 31852800),          # c1
+    (50, 4096, 64, 196664576, 342409472),      # c2 / c3
+    (120, 4096, 64, 471951616, 817556480),     # c4
+    (15, 4096, 64, 59021056, 102745088),       # c4, one rank's share
+    (50, 120, 10, 196664576, 210938112),       # the reference-native shape
+])
+def test_fused32_workspace_sizes(K, R, S, old_nofeat, old_feat):
+    """The fused hidden-32 step's workspace against the sizes of its earlier layout (256 compute units, as without a
+    device and on the MI355X): the unused byte-mask region (align256(p_stride) + 256 bytes) is gone, and with the
+    feature loss the copy of [W_of | b_of] for finalize_kernel has K C 33 floats of its own instead of sharing the
+    split-K partials' room."""
+    import ctypes as C
+    from openobj_amd import ops
+    l = _lib.lib()
+    net = ops.NetShape(32, 512, 6).c()
+    _, p_stride = _lib.param_layout(32, 512, 6)
+    align256 = lambda n: (n + 255) // 256 * 256
+    mask = align256(p_stride) + 256
+    head_snap = align256(K * 512 * 33 * 4)
+    assert l.objnerf_train_workspace_bytes(C.byref(net), K, R, S, 0) == old_nofeat - mask
+    assert l.objnerf_train_workspace_bytes(C.byref(net), K, R, S, 1) == old_feat - mask + head_snap
+
+
 def test_missing_library_is_loud(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))

@@ -1,5 +1,6 @@
 """Diagnostic: per-phase s_memtime breakdown of the fused fp32 training kernel (workgroup 0, every wave).
-Build first:  tools/build_variant.sh PHASE -DPHASE_TIMING ;  run on the GPU box (--bf16: the bf16 kernel, --feat)."""
+Build first:  tools/build_variant.sh PHASE -DPHASE_TIMING ;  run on the GPU box (--bf16v2: the second-generation bf16
+kernel, --feat)."""
 import ctypes as C, os, sys
 import numpy as np
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -9,16 +10,15 @@ import torch
 from openobj_amd import _lib, ops, synthetic, init as obj_init
 
 NAMES = ["load+project", "embed(sincos fwd)", "mlp fwd", "sync1", "composite", "sync2", "phaseA compute", "sync3",
-         "wgrad A", "sync4", "phaseB compute", "(dB, first generation)", "sync5", "wgrad B", "sync6+phaseC stores",
+         "wgrad A", "sync4", "phaseB compute", "(unused)", "sync5", "wgrad B", "sync6+phaseC stores",
          "sync7", "wgrad C", "sync8"]
 dev = torch.device("cuda:0")
 K, R, n1, n2 = 50, 4096, 16, 48
 arena = ops.ParamArena(K, ops.NetShape(), dev)
 arena.load_stacked(obj_init.init_stacked(K, 32, 512, seed=1000))
 FEAT = "--feat" in sys.argv
-BF16 = "--bf16" in sys.argv or "--bf16v2" in sys.argv
-V2 = "--bf16v2" in sys.argv           # second-generation bf16 kernel (objnerf_train_bf16v2.hip)
-if V2:
+BF16 = "--bf16v2" in sys.argv         # second-generation bf16 kernel (objnerf_train_bf16v2.hip)
+if BF16:
     NAMES = ["load+project", "embed + mlp fwd + heads", "sync1", "composite | wgrad(t-1)", "sync2", "bwd: d_hc, d_h4",
              "bwd: x2 chain rule", "bwd: d_h3 .. d_h1", "bwd: x1 chain rule, dB, next point"]
     if FEAT:
@@ -30,7 +30,7 @@ for _ in range(3):
     ops.train_step(arena, ws, batch, with_feat=FEAT, bf16=BF16)
 torch.cuda.synchronize()
 out = (C.c_ulonglong * (8 * 24))()
-f = ((_lib.lib().objnerf_debug_phase_bf16v2f if FEAT else _lib.lib().objnerf_debug_phase_bf16v2) if V2 else _lib.lib().objnerf_debug_phase_bf16) if BF16 else _lib.lib().objnerf_debug_phase32
+f = (_lib.lib().objnerf_debug_phase_bf16v2f if FEAT else _lib.lib().objnerf_debug_phase_bf16v2) if BF16 else _lib.lib().objnerf_debug_phase32
 f.restype = C.c_int
 assert f(out) == 0
 a = np.array(list(out), dtype=np.float64).reshape(8, 24)[:, :18]
