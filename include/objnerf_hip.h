@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define OBJNERF_ABI_VERSION 7
+#define OBJNERF_ABI_VERSION 8
 
 #define OBJNERF_OK 0
 #define OBJNERF_EINVAL (-22)       /* bad shape / null pointer / unsupported size        */
@@ -473,6 +473,28 @@ int objnerf_stratified_bins(int64_t n_rays, int32_t n_bins, const float* lo, flo
  * g = injected draws (already scaled) or NULL for the counter-based generator. */
 int objnerf_normal_bins(int64_t n_rays, int32_t n_bins, const float* depth, float delta, const float* g, uint64_t seed,
                         uint64_t offset, float* out, void* stream);
+
+/* ABI 8 -- marching cubes (vis.py:6-22: skimage.measure.marching_cubes(occupancy, level, gradient_direction='ascent'),
+ * as Trainer.meshing calls it, trainer.py:46-103) on a device fp32 volume vol [dim][dim][dim], last axis fastest
+ * (occ.view(grid_dim, grid_dim, grid_dim), trainer.py:81), 2 <= dim <= 1024.  Output in index units, welded: one
+ * vertex per lattice edge whose endpoints straddle the level (a corner is above when its value > level), ordered by
+ * (owning lattice point, axis); faces ordered by (cell, table order); bit-reproducible, no atomics.
+ * objnerf_mc_workspace_bytes: the workspace both calls share (0 for a dim outside the range).
+ * objnerf_mc_count: out_counts (device int64 [2]) = V, F; leaves per-workgroup offsets in ws.
+ * objnerf_mc_emit: only valid after objnerf_mc_count with the same dim, level, vol and ws.  out_verts [V][3] fp32,
+ * out_normals [V][3] fp32 (unit, down the gradient, as skimage's), out_faces [F][3] int32; nothing is written past
+ * max_verts / max_faces rows.  The caller keeps V <= 2^31 - 1 (int32 face indices).  flags: OBJNERF_MC_DESCENT
+ * writes every face reversed (gradient_direction='descent'). */
+#define OBJNERF_MC_DESCENT 1
+size_t objnerf_mc_workspace_bytes(int32_t dim);
+int objnerf_mc_count(int32_t dim, float level, const float* vol, void* ws, size_t ws_bytes, int64_t* out_counts,
+                     void* stream);
+int objnerf_mc_emit(int32_t dim, float level, int32_t flags, const float* vol, void* ws, size_t ws_bytes,
+                    int64_t max_verts, int64_t max_faces, float* out_verts, float* out_normals, int32_t* out_faces,
+                    void* stream);
+/* host only: copies of the compiled case table (objnerf_mc_tables.h; any pointer may be NULL): edge_c0 [12],
+ * edge_axis [12], ntri [256], tri [256][3 * max_tris] (0xff past a case's triangles).  Returns max_tris. */
+int objnerf_mc_tables(uint8_t* edge_c0, uint8_t* edge_axis, uint8_t* ntri, uint8_t* tri);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OBJNERF_LIB") or os.path.join(_HERE, "csrc", "libobjnerf_hip.so")   # OBJNERF_LIB: diagnostic builds
 
 OBJNERF_N_TENSORS = 19
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class ObjnerfError(RuntimeError):
@@ -169,6 +169,12 @@ SIGNATURES = {
     "objnerf_adamw_step_flags": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                            C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    # ABI 8: marching cubes (objnerf_mesh.hip)
+    "objnerf_mc_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "objnerf_mc_count": (C.c_int, [C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "objnerf_mc_emit": (C.c_int, [C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64,
+                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_mc_tables": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,95 @@
+"""Map export for the open-vocabulary viewer: visualization/gen_map_vis.py:82-146 over the checkpoints the mapper writes
+(mapping.py save_checkpoints: <logdir>/ckpt/<obj_id>/obj_<id>.pth).
+
+    python -m openobj_amd.map_vis --logdir DIR [--grid-dim 128] [--device cuda:0]
+
+For every object whose checkpoint carries a box: Trainer.meshing(box, obj_center, grid_dim, save_mesh, if_color,
+if_part) on the GPU, the part feature L2-normalised per vertex, and the reference's per-object dict (clip_feat,
+caption_feat, class_id, mesh, color, part_feat) collected into <logdir>/map_vis.pkl.gz; each mesh is also written to
+<logdir>/map_vis/obj_<id>.ply.  Objects without a box (the reference fits one with open3d, vmap.py:287-379, which is
+outside this project) are skipped with a message, as are objects whose network meshes to nothing."""
+from __future__ import annotations
+
+import argparse
+import gzip
+import os
+import pickle
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import cfg as ocfg
+from . import trainer
+
+
+def load_object(ckpt_file: str, device: str):
+    """-> (Trainer with the checkpoint's weights, checkpoint dict)."""
+    ck = torch.load(ckpt_file, map_location="cpu", weights_only=False)
+    fc = ck["FC_state_dict"]
+    c = ocfg.Config(ocfg.replica_room0_config(train_device=device))
+    c.obj_id = int(ck["obj_id"])
+    c.hidden_feature_size = int(fc["in_layer.0.weight"].shape[0])
+    c.clip_point_feature_size = int(fc["out_clip.weight"].shape[0])
+    c.obj_scale = float(ck["obj_scale"])
+    t = trainer.Trainer(c)
+    with torch.no_grad():
+        sd = t.fc_occ_map.state_dict()
+        for k, v in fc.items():
+            sd[k].copy_(v)
+        t.pe.B_layer.weight.copy_(ck["PE_state_dict"]["B_layer.weight"])
+    return t, ck
+
+
+def export(logdir: str, grid_dim: int = 128, device: str = "cuda:0", obj_center: float = 0.0) -> Optional[Dict]:
+    ckpt_dir = os.path.join(logdir, "ckpt")
+    ids = sorted(int(d) for d in os.listdir(ckpt_dir) if os.path.isdir(os.path.join(ckpt_dir, d)) and d.isdigit())
+    ply_dir = os.path.join(logdir, "map_vis")
+    os.makedirs(ply_dir, exist_ok=True)
+    all_obj = {}
+    for obj_id in ids:
+        f = os.path.join(ckpt_dir, str(obj_id), f"obj_{obj_id}.pth")
+        if not os.path.exists(f):
+            print("ckpt not exist ", f)
+            continue
+        t, ck = load_object(f, device)
+        box = ck.get("bbox")
+        if box is None:
+            print(f"obj {obj_id}: the checkpoint carries no box, skipped")
+            continue
+        res = t.meshing(box, torch.tensor(obj_center), grid_dim=grid_dim, save_pcd=False, save_mesh=True,
+                        if_color=True, if_part=True)
+        if res is None or len(res) != 3 or res[1] is None:
+            print(f"obj {obj_id}: no surface, skipped")
+            continue
+        _, mesh, part_feat = res
+        part_feat = part_feat.cpu().numpy()
+        part_feat = part_feat / np.linalg.norm(part_feat, axis=-1, keepdims=True)       # gen_map_vis.py:121
+        all_obj[obj_id] = {
+            "clip_feat": ck.get("clip_feat"),
+            "caption_feat": ck.get("caption_feat"),
+            "class_id": ck.get("semantic_id"),
+            "mesh": mesh,
+            "color": mesh.visual.vertex_colors,
+            "part_feat": part_feat,
+        }
+        mesh.export(os.path.join(ply_dir, f"obj_{obj_id}.ply"))
+        print(f"obj {obj_id}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces")
+    path = os.path.join(logdir, "map_vis.pkl.gz")
+    with gzip.open(path, "wb") as fh:
+        pickle.dump(all_obj, fh)
+    print(path)
+    return all_obj
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--logdir", required=True)
+    ap.add_argument("--grid-dim", type=int, default=128)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    export(a.logdir, a.grid_dim, a.device)
+
+
+if __name__ == "__main__":
+    main()

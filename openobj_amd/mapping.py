@@ -18,8 +18,9 @@ replicated, each rank trains it on its share of the frame's background rays and 
 
 Everything numerical runs in libobjnerf_hip.so (sampler, fused iteration, AdamW); this file is bookkeeping.
 The class-name text features (CLIP ViT-B/32 and SBERT encoders in the reference, train.py:108-147) are inputs
-here: pass `class_clipfeat` / `class_capfeat` arrays to `assign_semantics`.  Visualisation, meshing and the live
-ROS mode are outside the path.
+here: pass `class_clipfeat` / `class_capfeat` arrays to `assign_semantics`.  Meshing the checkpoints this loop writes is
+`python -m openobj_amd.map_vis --logdir DIR` (Trainer.meshing on the GPU, gen_map_vis.py:82-146); the open3d window and
+the live ROS mode are outside the path.
 """
 import contextlib
 import os

@@ -985,3 +985,39 @@ def normal_bins(depth: torch.Tensor, n_bins: int, delta: float, g: Optional[torc
                                     _next_offset() if draw is None else int(draw), _ptr(out), _stream()),
           "objnerf_normal_bins")
     return out
+
+
+def marching_cubes(volume: torch.Tensor, level: float = 0.5, gradient_direction: str = "ascent"):
+    """skimage.measure.marching_cubes(volume, level, gradient_direction=...) (vis.py:11-12) on the GPU:
+    volume [d,d,d] (2 <= d <= 1024; cast to fp32 like skimage) -> device (verts [V,3] fp32 in index units,
+    faces [F,3] int32, normals [V,3] fp32 unit, down the gradient).  One vertex per crossing lattice edge, ordered by
+    (owning lattice point, axis); faces by (cell, table order); bit-reproducible (objnerf_mesh.hip).
+    Synchronises the stream once: objnerf_mc_count's V and F are read back (.item()) to size the outputs before
+    objnerf_mc_emit.  skimage raises where this returns V = F = 0 (no crossing edge) and where `level` lies outside
+    [min, max]; vis.marching_cubes maps both to None as the reference does.
+    Normals are the central-difference gradient (one-sided at the border) interpolated along the edge.  skimage's
+    Lewiner implementation takes forward differences inside the cell instead, so its normals agree with these in sign
+    and direction (cos > 0.99, mean > 0.999 on smooth volumes) but not in digits; vertices, faces and winding match."""
+    if gradient_direction not in ("ascent", "descent"):
+        raise ValueError(f"Incorrect input {gradient_direction} in `gradient_direction`")
+    if volume.dim() != 3 or len(set(volume.shape)) != 1:
+        raise _lib.ObjnerfError(f"marching_cubes: expected a cubic [d,d,d] volume, got {tuple(volume.shape)}")
+    vol = _req(volume if volume.dtype == torch.float32 else volume.float(), torch.float32, "volume")
+    d, dev = int(vol.shape[0]), vol.device
+    nbytes = int(lib().objnerf_mc_workspace_bytes(d))
+    if nbytes == 0:
+        raise _lib.ObjnerfError(f"marching_cubes: dim {d} outside 2..1024")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    check(lib().objnerf_mc_count(d, float(level), _ptr(vol), _ptr(ws), nbytes, _ptr(counts), _stream()),
+          "objnerf_mc_count")
+    V, F = (int(x) for x in counts.tolist())                  # the one host sync
+    if V > 2 ** 31 - 1:
+        raise _lib.ObjnerfError(f"marching_cubes: {V} vertices do not fit int32 face indices")
+    verts = torch.empty(V, 3, device=dev)
+    normals = torch.empty(V, 3, device=dev)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    flags = 1 if gradient_direction == "descent" else 0        # OBJNERF_MC_DESCENT
+    check(lib().objnerf_mc_emit(d, float(level), flags, _ptr(vol), _ptr(ws), nbytes, V, F, _ptr(verts) if V else None,
+                                _ptr(normals) if V else None, _ptr(faces) if F else None, _stream()), "objnerf_mc_emit")
+    return verts, faces, normals

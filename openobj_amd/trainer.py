@@ -3,7 +3,8 @@ parameters are views of ONE per-object arena block, so update_vmap can gather K 
 import numpy as np
 import torch
 
-from . import embedding, model, ops
+from . import embedding, model, ops, render_rays, vis
+from .mesh import PointCloud
 
 
 class Trainer:
@@ -118,6 +119,70 @@ class Trainer:
     def input_pcs(self, v):
         self._input_pcs = v
 
-    def meshing(self, *a, **k):
-        raise NotImplementedError("marching cubes / open3d meshing (trainer.py:46-103, vis.py) is outside the "
-                                  "accelerated path; evaluate the grid with eval_points(render_rays.make_3D_grid(...))")
+    def _eval_grid(self, points, chunk_size=1 << 21):
+        """occupancy [N], colour [N,3] on the device, without the 512-d head (trainer.py:64-66 keeps only these two
+        of the grid's outputs; at 128^3 the head alone would be a 4.3 GB tensor).  Hidden 32: one fused launch;
+        wider networks run layer by layer in chunks that bound the activation workspace."""
+        self.arena.scale.fill_(float(self.obj_scale))
+        n = points.shape[0]
+        step = n if self.hidden_feature_size == 32 else chunk_size
+        occ, color = [], []
+        with torch.no_grad():
+            for k in range(0, n, step):
+                pts = points[k:k + step].reshape(1, -1, 3).to(self.device).contiguous()
+                a, c, _, _ = ops.eval_points(self.arena, pts)
+                occ.append(ops.occupancy(a[0]))
+                color.append(c[0])
+        return torch.cat(occ), torch.cat(color)
+
+    def meshing(self, bound, obj_center, grid_dim=256, save_pcd=True, save_mesh=True, if_color=False, if_part=False):
+        """Trainer.meshing (trainer.py:46-103) with its return shapes: (None, None) when the grid is empty (:63-64),
+        None when marching cubes or the vertex re-query fails (:81-84, :95-96), (pcd, None, None) on the save_pcd
+        branch (its voxel_down_sample result is discarded there, :70-77), (None, mesh, partfeat) otherwise.
+        bound: .center [3], .R [3,3], .extent [3] (an open3d OrientedBoundingBox in the reference).  mesh is a
+        mesh.TriMesh, pcd a mesh.PointCloud; partfeat the [V, 512] device feature of the vertices (if_part)."""
+        occ_range = [-1., 1.]
+        range_dist = occ_range[1] - occ_range[0]
+        scene_scale_np = np.asarray(bound.extent) / (range_dist * self.bound_extent)        # :51
+        scene_scale = torch.from_numpy(np.asarray(scene_scale_np)).float().to(self.device)
+        transform_np = np.eye(4, dtype=np.float32)                                            # :53-56
+        transform_np[:3, 3] = np.asarray(bound.center)
+        transform_np[:3, :3] = np.asarray(bound.R)
+        transform = torch.from_numpy(transform_np).to(self.device)
+        grid_pc = render_rays.make_3D_grid(occ_range=occ_range, dim=grid_dim, device=self.device,
+                                           scale=scene_scale, transform=transform).view(-1, 3)   # :58-59
+        grid_pc -= torch.as_tensor(obj_center, dtype=torch.float32).to(grid_pc.device)        # :60
+        occ, colors = self._eval_grid(grid_pc)                                                # :61
+        if occ.max() == 0:                                                                    # (eval_points :124-126)
+            print("no occ")
+            return None, None
+        pcd = mesh = partfeat = None
+        if save_pcd:                                                                          # :69-77
+            mask_valid = occ > 0.5
+            pcd = PointCloud(grid_pc[mask_valid].cpu().numpy(), colors[mask_valid].cpu().numpy())
+        elif save_mesh:                                                                       # :78-101
+            mesh = vis.marching_cubes(occ.view(grid_dim, grid_dim, grid_dim))
+            if mesh is None:
+                print("marching cube failed")
+                return None
+            mesh.apply_translation([-0.5, -0.5, -0.5])                                        # :85-90
+            mesh.apply_scale(2)
+            mesh.apply_scale(scene_scale_np)
+            mesh.apply_transform(transform_np)
+            if if_color or if_part:
+                # the re-query does NOT subtract obj_center (:92), as in the reference
+                vertices_pts = torch.from_numpy(np.array(mesh.vertices)).float().to(self.device)
+                if if_part:
+                    ret = self.eval_points(vertices_pts)
+                    if ret is None:
+                        return None
+                    _, color, clip = ret
+                    partfeat = clip
+                else:
+                    o, color = self._eval_grid(vertices_pts)
+                    if o.max() == 0:
+                        print("no occ")
+                        return None
+                if if_color:
+                    mesh.visual.vertex_colors = (color * 255).cpu().numpy().astype(np.uint8)  # truncates (:97-99)
+        return pcd, mesh, partfeat
