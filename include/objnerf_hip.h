@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define OBJNERF_ABI_VERSION 8
+#define OBJNERF_ABI_VERSION 9
 
 #define OBJNERF_OK 0
 #define OBJNERF_EINVAL (-22)       /* bad shape / null pointer / unsupported size        */
@@ -495,6 +495,62 @@ int objnerf_mc_emit(int32_t dim, float level, int32_t flags, const float* vol, v
 /* host only: copies of the compiled case table (objnerf_mc_tables.h; any pointer may be NULL): edge_c0 [12],
  * edge_axis [12], ntri [256], tri [256][3 * max_tris] (0xff past a case's triangles).  Returns max_tris. */
 int objnerf_mc_tables(uint8_t* edge_c0, uint8_t* edge_axis, uint8_t* ntri, uint8_t* tri);
+
+/* ABI 9 -- object bounds from keyframes (objnerf_bounds.hip): sceneObject.get_bound (vmap.py:287-384), which the
+ * reference runs on the CPU per object through open3d (create_from_depth_image + voxel_down_sample, :303-320) and
+ * trimesh.bounds.oriented_bounds (:330-334).
+ *
+ * (a) Voxel centroids of K objects' keyframe point clouds (vmap.py:303-320).  `table` [K] (device): the objects'
+ * keyframe stores (objnerf_kf_store; rgbs and depth are read, F slots of [W][H] each); n_keyframes [K] (device): only
+ * slots 0 .. n_keyframes-1 are read; camera_pose [K][F][16] (device, row-major) = inv64(inv32(twc)) per slot, as open3d
+ * receives it (vmap.py:307-310).  A pixel (row i, column j) belongs to the cloud when its state byte is 1 and its depth
+ * z > 0 (NaN fails); point = camera_pose (x, y, z, 1), x = (j - cx) z / fx, y = (i - cy) z / fy, all in fp64 without
+ * contraction; points in the order (slot, i, j).
+ * objnerf_voxel_workspace_bytes: the workspace scan and emit share.
+ * objnerf_voxel_scan: out_total [K] (device int64) = point counts, out_minmax [K][6] (device fp64) = min xyz, max xyz
+ * (+inf / -inf for an empty cloud).
+ * objnerf_voxel_emit: the points of objects k0 .. k1-1 (after a scan with the same arguments): object k's points go to
+ * rows base[k] .. base[k] + total[k] - 1 of out_pts [n_points][3] (fp64), in the cloud's order, with out_keys [n_points]
+ * = (k - k0) << 42 | (ix + dims[k][0] (iy + dims[k][1] iz)), ixyz = floor((p - vmin[k]) / voxel) (open3d's voxel
+ * index; vmin [K][3], dims [K][2] device).  Nothing is written past n_points rows.
+ * objnerf_voxel_heads: for keys sorted ascending with equal keys in cloud order (a stable sort of out_keys): ws
+ * (objnerf_voxel_heads_workspace_bytes(n)) receives per-block offsets of the distinct keys, ws[last] = their count V.
+ * objnerf_voxel_centroids: one row per distinct key, in key order (V <= max_voxels rows written): out_centroids
+ * [V][3] = the in-order fp64 sum of the key's points (perm = the sort's permutation into out_pts) / their count
+ * (voxel_down_sample, vmap.py:320), out_keys [V] = the key's low 42 bits, out_first[k - k0] = the first row of object k
+ * (left untouched for an object without points). */
+typedef struct objnerf_voxel_args {
+  int32_t K, F, W, H;
+  double fx, fy, cx, cy, voxel;
+  const objnerf_kf_store* table; const int32_t* n_keyframes; const double* camera_pose;
+} objnerf_voxel_args;
+size_t objnerf_voxel_workspace_bytes(int32_t K, int32_t F, int32_t W, int32_t H);
+int objnerf_voxel_scan(const objnerf_voxel_args* a, void* ws, size_t ws_bytes, int64_t* out_total, double* out_minmax,
+                       void* stream);
+int objnerf_voxel_emit(const objnerf_voxel_args* a, const void* ws, size_t ws_bytes, int32_t k0, int32_t k1,
+                       const int64_t* base, const double* vmin, const int64_t* dims, int64_t n_points, double* out_pts,
+                       int64_t* out_keys, void* stream);
+size_t objnerf_voxel_heads_workspace_bytes(int64_t n);
+int objnerf_voxel_heads(int64_t n, const int64_t* sorted_keys, int64_t* ws, void* stream);
+int objnerf_voxel_centroids(int64_t n, const int64_t* sorted_keys, const int64_t* perm, const double* pts,
+                            const int64_t* ws, int64_t max_voxels, double* out_centroids, int64_t* out_keys,
+                            int64_t* out_first, void* stream);
+
+/* (b) Oriented-box search for K point sets (trimesh.bounds.oriented_bounds(points, ordered=True), vmap.py:330-334,
+ * over an exact candidate set): verts [V][3] fp64 hull vertices, object k's rows vert_off[k] .. vert_off[k+1]-1;
+ * normals [N][3] unit (global rows); edges [E][2] int32 vertex indices local to the object; cand [C][2] int32 =
+ * (global normal row, global edge row), object k's rows cand_off[k] .. cand_off[k+1]-1; mode [K]: 0 = minimise the
+ * volume, 1 = a coplanar set (one normal, height 0): minimise the (u, v) area.  Per candidate: u = e projected onto
+ * the plane normal to n, normalised (skipped when degenerate), v = n x u; extents = max - min of the vertices'
+ * projections on (u, v, n).  The minimum is taken in (criterion, candidate row) order.  ws: 2 K n_split doubles.
+ * out [K][16] fp64: R [3][3] row-major with columns u, v, n; extents [3]; centre [3] (world); criterion (+inf: no
+ * valid candidate).  All device pointers. */
+typedef struct objnerf_obb_args {
+  int32_t K, reserved;
+  const double* verts; const int64_t* vert_off; const double* normals; const int32_t* edges; const int32_t* cand;
+  const int64_t* cand_off; const int32_t* mode;
+} objnerf_obb_args;
+int objnerf_obb_search(const objnerf_obb_args* a, int32_t n_split, double* ws, double* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OBJNERF_LIB") or os.path.join(_HERE, "csrc", "libobjnerf_hip.so")   # OBJNERF_LIB: diagnostic builds
 
 OBJNERF_N_TENSORS = 19
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class ObjnerfError(RuntimeError):
@@ -94,6 +94,22 @@ class TrainArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
                 ("relu_masks", C.c_void_p), ("context", C.c_void_p), ("emb_debug", C.c_void_p),
                 ("optim", C.c_void_p)]
+
+
+class KfStore(C.Structure):
+    _fields_ = [("rgbs", C.c_void_p), ("depth", C.c_void_p), ("t_wc", C.c_void_p), ("bbox", C.c_void_p)]
+
+
+class VoxelArgs(C.Structure):
+    _fields_ = [("K", C.c_int32), ("F", C.c_int32), ("W", C.c_int32), ("H", C.c_int32),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("voxel", C.c_double),
+                ("table", C.c_void_p), ("n_keyframes", C.c_void_p), ("camera_pose", C.c_void_p)]
+
+
+class ObbArgs(C.Structure):
+    _fields_ = [("K", C.c_int32), ("reserved", C.c_int32), ("verts", C.c_void_p), ("vert_off", C.c_void_p),
+                ("normals", C.c_void_p), ("edges", C.c_void_p), ("cand", C.c_void_p), ("cand_off", C.c_void_p),
+                ("mode", C.c_void_p)]
 
 
 # name -> (restype, argtypes); every symbol include/objnerf_hip.h declares
@@ -175,6 +191,16 @@ SIGNATURES = {
     "objnerf_mc_emit": (C.c_int, [C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64,
                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "objnerf_mc_tables": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ABI 9: object bounds from keyframes (objnerf_bounds.hip)
+    "objnerf_voxel_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "objnerf_voxel_scan": (C.c_int, [C.POINTER(VoxelArgs), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_voxel_emit": (C.c_int, [C.POINTER(VoxelArgs), C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_voxel_heads_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "objnerf_voxel_heads": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_voxel_centroids": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_obb_search": (C.c_int, [C.POINTER(ObbArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -6,8 +6,10 @@
 For every object whose checkpoint carries a box: Trainer.meshing(box, obj_center, grid_dim, save_mesh, if_color,
 if_part) on the GPU, the part feature L2-normalised per vertex, and the reference's per-object dict (clip_feat,
 caption_feat, class_id, mesh, color, part_feat) collected into <logdir>/map_vis.pkl.gz; each mesh is also written to
-<logdir>/map_vis/obj_<id>.ply.  Objects without a box (the reference fits one with open3d, vmap.py:287-379, which is
-outside this project) are skipped with a message, as are objects whose network meshes to nothing."""
+<logdir>/map_vis/obj_<id>.ply.  The boxes are the ones the mapper fitted to each object's keyframes before writing the
+checkpoint (sceneObject.get_bound, vmap.py:287-384; `python -m openobj_amd.mapping` does it for every checkpoint).
+Objects whose checkpoint carries no box (too few keyframe points to fit one, as in the reference) are skipped with a
+message, as are objects whose network meshes to nothing."""
 from __future__ import annotations
 
 import argparse

@@ -19,8 +19,9 @@ replicated, each rank trains it on its share of the frame's background rays and 
 Everything numerical runs in libobjnerf_hip.so (sampler, fused iteration, AdamW); this file is bookkeeping.
 The class-name text features (CLIP ViT-B/32 and SBERT encoders in the reference, train.py:108-147) are inputs
 here: pass `class_clipfeat` / `class_capfeat` arrays to `assign_semantics`.  Meshing the checkpoints this loop writes is
-`python -m openobj_amd.map_vis --logdir DIR` (Trainer.meshing on the GPU, gen_map_vis.py:82-146); the open3d window and
-the live ROS mode are outside the path.
+`python -m openobj_amd.map_vis --logdir DIR` (Trainer.meshing on the GPU, gen_map_vis.py:82-146) inside the oriented
+boxes that save_checkpoints fits to every object's keyframes (compute_bounds); the open3d window and the live ROS mode
+are outside the path.
 """
 import contextlib
 import os
@@ -32,7 +33,7 @@ import torch
 from . import dist as odist
 from . import ops
 from . import train as otrain
-from .vmap import StackedSampler, cameraInfo, sceneObject
+from .vmap import StackedSampler, cameraInfo, get_bounds, sceneObject
 
 
 def get_majority_cluster_mean(vectors, eps, min_samples):
@@ -332,17 +333,26 @@ class IncrementalMapper:
             so.set_semantic(mapping[obj_id])
         return mapping
 
+    def _own_objects(self):
+        """The objects whose checkpoints this rank writes: its foreground shard, and the replicated background on rank 0."""
+        return {i: so for i, so in self.vis_dict.items() if not (i == 0 and self.scene_bg is so and self.rank != 0)}
+
+    def compute_bounds(self, intrinsic_open3d=None, final=False):
+        """sceneObject.get_bound for all of this rank's objects in one ops.object_bounds call (train.py:533 calls it per
+        object before every checkpoint) -> {obj_id: (bbox3d, bbox) | (None, None)}."""
+        own = self._own_objects()
+        return dict(zip(own, get_bounds(list(own.values()), intrinsic_open3d, final)))
+
     def save_checkpoints(self, log_dir: str, need_bound: bool = False):
-        """ckpt/<obj_id>/obj_<id>.pth for every object + cam_pose/twc_frame.pth (train.py:527-541).  The reference
-        refreshes each object's 3-D box first (open3d point-cloud fitting, outside this build): with need_bound the
-        caller must have set sceneObject.bbox3dour."""
-        for obj_id, so in self.vis_dict.items():
-            if obj_id == 0 and self.scene_bg is so and self.rank != 0:
-                continue                                  # the replicated background is written by rank 0
+        """ckpt/<obj_id>/obj_<id>.pth for every object + cam_pose/twc_frame.pth (train.py:527-541).  need_bound: refresh
+        every object's 3-D box from its keyframes first (compute_bounds; an object without enough points keeps bbox
+        None, as in the reference)."""
+        own = self._own_objects()
+        if need_bound:
+            self.compute_bounds()
+        for obj_id, so in own.items():
             d = os.path.join(log_dir, "ckpt", str(obj_id))
             os.makedirs(d, exist_ok=True)
-            if need_bound:
-                so.get_bound(None)
             so.save_checkpoints(d, self.last_frame_id)
         if self.rank != 0:
             return
@@ -393,7 +403,7 @@ def main(argv=None):
             print("frame %d: %d objects, last-iteration loss terms (depth, colour, opacity, feature) = %s"
                   % (frame_id, t.shape[0], [round(float(x), 5) for x in t.sum(0).tolist()]), flush=True)
         if cfg.if_ckpt and frame_id > 0 and (frame_id % cfg.n_vis_iter == 0 or frame_id == n_total - 1):
-            mapper.save_checkpoints(args.logdir)
+            mapper.save_checkpoints(args.logdir, need_bound=True)        # train.py:533: bound, then checkpoint
 
     mapper.run(loader, n_frames=args.frames, on_frame=on_frame)
     return mapper

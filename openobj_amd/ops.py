@@ -1021,3 +1021,18 @@ def marching_cubes(volume: torch.Tensor, level: float = 0.5, gradient_direction:
     check(lib().objnerf_mc_emit(d, float(level), flags, _ptr(vol), _ptr(ws), nbytes, V, F, _ptr(verts) if V else None,
                                 _ptr(normals) if V else None, _ptr(faces) if F else None, _stream()), "objnerf_mc_emit")
     return verts, faces, normals
+
+
+def objects_voxels(objects, intrinsics=None, voxel: float = 0.05, **kw):
+    """Voxel-down-sampled keyframe point clouds of sceneObjects (vmap.py:303-320) -> per object (voxel indices int64
+    [n,3], centroids fp64 [n,3]); objnerf_voxel_scan / _emit / _heads / _centroids (openobj_amd/bounds.py)."""
+    from . import bounds
+    return bounds.objects_voxels(objects, intrinsics, voxel, **kw)
+
+
+def object_bounds(objects, intrinsics=None, voxel: float = 0.05, min_extent: float = 0.10, **kw):
+    """sceneObject.get_bound (vmap.py:287-384) for a list of objects: the voxel chain above, the hull of each object's
+    centroids on the host, objnerf_obb_search for all of them in one launch -> [(bbox3d, bbox) | (None, None)]
+    (openobj_amd/bounds.py states the algorithm and its one deviation from trimesh)."""
+    from . import bounds
+    return bounds.object_bounds(objects, intrinsics, voxel, min_extent, **kw)

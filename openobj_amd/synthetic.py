@@ -236,3 +236,68 @@ def grid_frame(i: int, n_objects: int, W: int = 1200, H: int = 680, part: bool =
     if part:
         s["part_feat"] = torch.randn(W // 5, H // 5, 512)
     return s
+
+
+class KeyframeObject:
+    """The part of a sceneObject that get_bound reads (vmap.py:287-384): a device keyframe store (rgbs_batch [F,W,H,4]
+    u8 with the state in channel 3, depth_batch [F,W,H], t_wc_batch [F,4,4], bbox [F,4]), n_keyframes and the camera."""
+
+    def __init__(self, device, F: int, W: int, H: int, intrinsics, n_keyframes: int = 0):
+        import torch
+        self.data_device = device
+        self.keyframe_buffer_size, self.frames_width, self.frames_height = F, W, H
+        self.intrinsics = tuple(float(v) for v in intrinsics)
+        self.n_keyframes = n_keyframes
+        self.rgbs_batch = torch.zeros(F, W, H, 4, dtype=torch.uint8, device=device)
+        self.depth_batch = torch.zeros(F, W, H, dtype=torch.float32, device=device)
+        self.t_wc_batch = torch.eye(4, device=device).repeat(F, 1, 1)
+        self.bbox = torch.zeros(F, 4, device=device)
+
+    def keyframe_store(self):
+        return self.rgbs_batch, self.depth_batch, self.t_wc_batch, self.bbox
+
+
+def native_bound_map(device, n_obj: int = 51, F: int = 20, W: int = 1200, H: int = 680, seed: int = 0):
+    """The reference's native map shape for get_bound: n_obj objects (object 0 = the background) with F keyframes of
+    W x H each.  Every keyframe shares a smooth depth surface (2-3 m) seen from a camera that pans and turns; the
+    background holds the top half of every keyframe, object k a rectangle of 1-5 % of it (closer, 1.0-1.8 m) that drifts
+    from keyframe to keyframe; a 16-pixel border is "unknown" (state 2).  Rectangles, depths and poses come from
+    RandomState(seed) -> [KeyframeObject]."""
+    import torch
+    rs = np.random.RandomState(seed)
+    fx = fy = 600.0
+    intr = (fx, fy, (W - 1) / 2.0, (H - 1) / 2.0)
+    objs = [KeyframeObject(device, F, W, H, intr, F) for _ in range(n_obj)]
+    xs = torch.arange(W, device=device, dtype=torch.float32)[:, None]
+    ys = torch.arange(H, device=device, dtype=torch.float32)[None, :]
+    frac = rs.uniform(0.01, 0.05, n_obj)
+    aspect = rs.uniform(0.7, 1.4, n_obj)
+    ow = np.minimum(W - 40, np.sqrt(frac * W * H * aspect)).astype(int)
+    oh = np.minimum(H - 40, (frac * W * H / np.maximum(ow, 1))).astype(int)
+    ox = rs.randint(16, W - 16 - ow + 1)
+    oy = rs.randint(16, H - 16 - oh + 1)
+    odepth = rs.uniform(1.0, 1.8, n_obj)
+    for f in range(F):
+        a = 0.02 * f
+        twc = np.eye(4, dtype=np.float32)
+        twc[:3, :3] = [[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]]
+        twc[:3, 3] = [0.05 * f, 0.01 * f, 0.0]
+        twc_d = torch.from_numpy(twc).to(device)
+        depth = 2.5 + 0.3 * torch.sin(xs / 150.0 + 0.1 * f) + 0.2 * torch.cos(ys / 120.0)      # [W, H]
+        border = torch.zeros(W, H, dtype=torch.bool, device=device)
+        border[:16], border[-16:], border[:, :16], border[:, -16:] = True, True, True, True
+        for k, o in enumerate(objs):
+            st = torch.zeros(W, H, dtype=torch.uint8, device=device)
+            d = depth.clone()
+            if k == 0:
+                st[:, :H // 2] = 1
+            else:
+                x0, y0 = int(ox[k]) + 2 * f, int(oy[k])
+                x0 = min(x0, W - 16 - int(ow[k]))
+                st[x0:x0 + ow[k], y0:y0 + oh[k]] = 1
+                d[x0:x0 + ow[k], y0:y0 + oh[k]] = float(odepth[k]) + 0.0005 * (xs[x0:x0 + ow[k]] - x0).expand(-1, int(oh[k]))
+            st[border] = 2
+            o.rgbs_batch[f, :, :, 3] = st
+            o.depth_batch[f] = d
+            o.t_wc_batch[f] = twc_d
+    return objs

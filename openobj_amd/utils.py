@@ -1,6 +1,7 @@
 """utils -- the hot-path helpers of the reference's utils.py: update_vmap (:55-62), origin_dirs_W
 (:324-336), ray_box_intersection (:309-319), stratified_bins (:342-379), normal_bins_sampling
-(:382-397), performance_measure (:13-27).  Bbox / instance-tracking helpers are out of scope."""
+(:382-397), performance_measure (:13-27), BoundingBox (:30-36).  The other bbox / instance-tracking helpers are out of
+scope."""
 from time import perf_counter_ns
 
 import torch
@@ -27,6 +28,17 @@ class performance_measure:
         self.end_time = perf_counter_ns()
         self.exec_time = self.end_time - self.start_time
         print(f"{self.name} excution time: {(self.exec_time)/1000000:.2f} ms")
+
+
+class BoundingBox:
+    """An oriented 3-D box (utils.py:30-36): center [3], R [3,3] (columns = the box axes in world coordinates),
+    extent [3], points3d [8,3] (the corners, vmap.py:350-361).  Plain attributes: picklable, it goes into checkpoints."""
+
+    def __init__(self):
+        self.extent = None
+        self.R = None
+        self.center = None
+        self.points3d = None    # (8,3)
 
 
 class StackedModel:

@@ -1,8 +1,9 @@
 """vmap -- scene-object state of the reference's vmap.py that feeds the hot path: cameraInfo
 (:689-720), sceneObject's keyframe buffers + append_keyframe (:29-257), the pixel / ray sampler
-get_training_samples + sample_3d_points (:386-554) on objnerf_sample_rays, and the checkpoint dict
-(:556-602).  3-D bounding-box estimation, point-cloud denoising and novel-view rendering
-(get_bound, render_2D_syn) are not on the accelerated training path.
+get_training_samples + sample_3d_points (:386-554) on objnerf_sample_rays, the oriented 3-D box from the keyframes
+(get_bound, :287-384, on objnerf_voxel_* / objnerf_obb_search: openobj_amd/bounds.py), novel-view rendering
+(render_2D_syn, :604-685) and the checkpoint dict (:556-602).  The reference's point-cloud denoising (DBSCAN) is
+commented out there and absent here.
 """
 import copy
 import os
@@ -61,6 +62,7 @@ class sceneObject:
             self.n_bins_cam2surface = cfg.n_bins_cam2surface
             self.keyframe_step = cfg.keyframe_step
         self.frames_width, self.frames_height = rgb.shape[0], rgb.shape[1]
+        self.intrinsics = (float(cfg.fx), float(cfg.fy), float(cfg.cx), float(cfg.cy))   # get_bound's default camera
         self.min_bound, self.max_bound = cfg.min_depth, cfg.max_depth
         self.n_bins = cfg.n_bins
         self.n_unidir_funcs = cfg.n_unidir_funcs
@@ -104,6 +106,8 @@ class sceneObject:
         self.trainer = trainer.Trainer(trainer_cfg)
         self.bbox_final = False
         self.bbox3dour = None
+        self.bbox3d = None
+        self._computed_bound = None         # the box get_bound stored last: any other bbox3dour was set by the caller
         self.obj_center = torch.tensor(0.0)
 
     # ------------------------------------------------------------------ keyframes (vmap.py:166-257)
@@ -238,12 +242,18 @@ class sceneObject:
         self.semantic_id = semantic_id
 
     # ------------------------------------------------------------------ checkpoints (vmap.py:556-602)
-    def get_bound(self, intrinsic_open3d=None, final=True):
-        """The object's oriented 3-D box (vmap.py:259-384 builds it from the keyframe point cloud with open3d,
-        outside the accelerated path): returns (None, self.bbox3dour), which the caller must have set."""
-        if self.bbox3dour is None:
-            raise RuntimeError("sceneObject.bbox3dour is not set: assign an oriented box (.center, .R, .extent)")
-        return None, self.bbox3dour
+    def get_bound(self, intrinsic_open3d=None, final=False):
+        """The object's oriented 3-D box from its keyframes (vmap.py:287-384) -> (bbox3d, bbox), or (None, None) when
+        the keyframes hold too few points (the reference's "too few pcs obj").  Once a call with final=True has run,
+        the stored pair is returned as it is (as after load_checkpoints).  A box the caller assigned to bbox3dour is
+        returned unchanged and never replaced.  intrinsic_open3d: anything with a 3x3 `intrinsic_matrix`; None = the
+        camera of the object's config.  The computation (bounds.object_bounds) restates open3d's back-projection and
+        voxel_down_sample(0.05) and trimesh's oriented_bounds over every distinct hull-facet normal (a superset of
+        trimesh's bucketed candidates: never a larger box)."""
+        return get_bounds([self], intrinsic_open3d, final)[0]
+
+    def _caller_box(self):
+        return self.bbox3dour is not None and self.bbox3dour is not self._computed_bound
 
     def render_2D_syn(self, T_WC, intrinsic_open3d, cached_rays_dir, T_WO=None, chunk_size=1000, do_fine=True,
                       obj_mask=None, render_part=False, draws=None):
@@ -350,6 +360,26 @@ class sceneObject:
         self.semantic_id = checkpoint["semantic_id"]
         self.bbox_final = True
         return True
+
+
+def get_bounds(objs, intrinsic_open3d=None, final=False):
+    """sceneObject.get_bound for a list of objects: the objects that need a box get it from ONE ops.object_bounds
+    call (an object's box does not depend on the others in the call) -> [(bbox3d, bbox) | (None, None)] per object."""
+    todo = [o for o in objs if not o.bbox_final and not o._caller_box()]
+    res = dict(zip(map(id, todo), ops.object_bounds(todo, intrinsic_open3d) if todo else []))
+    out = []
+    for o in objs:
+        if id(o) not in res:
+            out.append((o.bbox3d, o.bbox3dour))
+            continue
+        o.bbox_final = final                        # vmap.py:299, set before the fit whatever its outcome
+        bbox3d, bbox = res[id(o)]
+        if bbox is None:
+            out.append((None, None))                # vmap.py:335-337: the stored box stays
+            continue
+        o.bbox3d, o.bbox3dour, o._computed_bound = bbox3d, bbox, bbox
+        out.append((bbox3d, bbox))
+    return out
 
 
 class StackedSampler:
