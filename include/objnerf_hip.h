@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define OBJNERF_ABI_VERSION 9
+#define OBJNERF_ABI_VERSION 10
 
 #define OBJNERF_OK 0
 #define OBJNERF_EINVAL (-22)       /* bad shape / null pointer / unsupported size        */
@@ -551,6 +551,71 @@ typedef struct objnerf_obb_args {
   const int64_t* cand_off; const int32_t* mode;
 } objnerf_obb_args;
 int objnerf_obb_search(const objnerf_obb_args* a, int32_t n_split, double* ws, double* out, void* stream);
+
+/* ABI 10 -- open-vocabulary queries over the exported map (objnerf_query.hip): the numerical core of
+ * visualization/vis_interaction.py, which the reference runs per object on the host (F.cosine_similarity :372-373,
+ * :388; sim_and_update's min-max + matplotlib "rainbow" :329-332, :389-392; StandardScaler + PCA(3) + joint min-max
+ * :205-216).  Segments are row ranges: segment s is rows seg_off[s] .. seg_off[s+1]-1 (device int64 [S+1], clamped to
+ * [0, V]); an empty segment is allowed.  All pointers are device pointers unless stated; no float atomics, and two
+ * calls with the same inputs write the same bytes.
+ *
+ * objnerf_project: out [V][Q] fp32 = f . W + bias for every row f of every segment; feat [V][D] fp32 with a row
+ * stride (floats, >= D), 1 <= D <= 1024, 1 <= Q <= 16; W [D][Q] row-major, shared, or [S][D][Q] with
+ * OBJNERF_PROJ_PER_SEGMENT (bias [Q] or [S][Q] likewise; NULL: none).  OBJNERF_PROJ_COSINE: f and every column of W
+ * are divided by max(|.|, 1e-8) first (torch.nn.functional.cosine_similarity).  minmax [S][Q][2] = min, max of the
+ * segment's rows of out (+inf / -inf for an empty segment).  Products on v_mfma_f32_16x16x4_f32 (fp32).  Rows outside
+ * every segment are not written.  ws: objnerf_project_workspace_bytes(S, Q, V). */
+#define OBJNERF_PROJ_COSINE 1
+#define OBJNERF_PROJ_PER_SEGMENT 2
+typedef struct objnerf_project_args {
+  int32_t S, D, Q, flags;
+  int64_t V, row_stride;
+  const float* feat; const int64_t* seg_off; const float* W; const float* bias;
+  float* out; float* minmax;
+} objnerf_project_args;
+size_t objnerf_project_workspace_bytes(int32_t S, int32_t Q, int64_t V);
+int objnerf_project(const objnerf_project_args* a, void* ws, size_t ws_bytes, void* stream);
+
+/* objnerf_moments: per segment, mean [S][D] fp64 (fp64 sums of contiguous row chunks, combined in chunk order) and
+ * the centred scatter matrix scatter [S][D][D] fp64 = sum over the rows of (f - m)(f - m)^T, m = the mean rounded to
+ * fp32: centred before the products (part features are unit vectors with a large common mean: X^T X - n m m^T in fp32
+ * loses the spread); products and runs of 128 rows in fp32 on v_mfma_f32_16x16x4_f32, folded into fp64 in row order;
+ * exactly symmetric.  An empty segment gives zeros.  ws: objnerf_moments_workspace_bytes(S, D). */
+typedef struct objnerf_moments_args {
+  int32_t S, D;
+  int64_t V, row_stride;
+  const float* feat; const int64_t* seg_off;
+  double* mean; double* scatter;
+} objnerf_moments_args;
+size_t objnerf_moments_workspace_bytes(int32_t S, int32_t D);
+int objnerf_moments(const objnerf_moments_args* a, void* ws, size_t ws_bytes, void* stream);
+
+/* objnerf_vertex_colors: out [V][3] fp32 for the rows of every segment, by mode[s]:
+ *   OBJNERF_COLOR_RGB      fp32(rgb[row][c] / 255 * factor[s]) in fp64 (rgb: uint8, rgb_stride bytes per row; the
+ *                          reference's color[..., :3] / 255 * 0.8 (color_by_rgb) or * 0.5 (a non-selected object));
+ *   OBJNERF_COLOR_CONSTANT constant[s][0..2];
+ *   OBJNERF_COLOR_RAINBOW  matplotlib's "rainbow" of x = fp32(fp32(v - mn) / fp32(mx - mn)), v = proj[row][column[s]],
+ *                          (mn, mx) = minmax[s][column[s]]: entry trunc(256 x) (256 -> 255), x < 0 -> 0, x > 1 -> 255,
+ *                          NaN (a constant segment) -> (0, 0, 0); proj [V][Q];
+ *   OBJNERF_COLOR_PCA      columns 0..2 of proj (Q >= 3), each negated when -min > max (the largest |score| positive),
+ *                          normalised by one joint min / max over the three, clipped to [0, 1] (NaN -> 0).
+ * Arrays a mode does not read may be NULL. */
+#define OBJNERF_COLOR_RGB 0
+#define OBJNERF_COLOR_CONSTANT 1
+#define OBJNERF_COLOR_RAINBOW 2
+#define OBJNERF_COLOR_PCA 3
+typedef struct objnerf_color_args {
+  int32_t S, Q;
+  int64_t V, rgb_stride;
+  const int64_t* seg_off; const int32_t* mode;
+  const uint8_t* rgb; const double* factor; const float* constant; const int32_t* column;
+  const float* proj; const float* minmax;
+  float* out;
+} objnerf_color_args;
+int objnerf_vertex_colors(const objnerf_color_args* a, void* stream);
+/* host only: the "rainbow" table the colour kernel uses, out [256][3] fp32 (matplotlib's _lut[:256, :3] rounded to
+ * fp32).  Returns 256. */
+int objnerf_rainbow_lut(float* out);
 
 #ifdef __cplusplus
 }

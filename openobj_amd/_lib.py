@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OBJNERF_LIB") or os.path.join(_HERE, "csrc", "libobjnerf_hip.so")   # OBJNERF_LIB: diagnostic builds
 
 OBJNERF_N_TENSORS = 19
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class ObjnerfError(RuntimeError):
@@ -112,6 +112,30 @@ class ObbArgs(C.Structure):
                 ("mode", C.c_void_p)]
 
 
+class ProjectArgs(C.Structure):
+    _fields_ = [("S", C.c_int32), ("D", C.c_int32), ("Q", C.c_int32), ("flags", C.c_int32),
+                ("V", C.c_int64), ("row_stride", C.c_int64),
+                ("feat", C.c_void_p), ("seg_off", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p),
+                ("out", C.c_void_p), ("minmax", C.c_void_p)]
+
+
+class MomentsArgs(C.Structure):
+    _fields_ = [("S", C.c_int32), ("D", C.c_int32), ("V", C.c_int64), ("row_stride", C.c_int64),
+                ("feat", C.c_void_p), ("seg_off", C.c_void_p), ("mean", C.c_void_p), ("scatter", C.c_void_p)]
+
+
+class ColorArgs(C.Structure):
+    _fields_ = [("S", C.c_int32), ("Q", C.c_int32), ("V", C.c_int64), ("rgb_stride", C.c_int64),
+                ("seg_off", C.c_void_p), ("mode", C.c_void_p), ("rgb", C.c_void_p), ("factor", C.c_void_p),
+                ("constant", C.c_void_p), ("column", C.c_void_p), ("proj", C.c_void_p), ("minmax", C.c_void_p),
+                ("out", C.c_void_p)]
+
+
+PROJ_COSINE = 1          # OBJNERF_PROJ_COSINE
+PROJ_PER_SEGMENT = 2     # OBJNERF_PROJ_PER_SEGMENT
+COLOR_RGB, COLOR_CONSTANT, COLOR_RAINBOW, COLOR_PCA = 0, 1, 2, 3      # OBJNERF_COLOR_*
+
+
 # name -> (restype, argtypes); every symbol include/objnerf_hip.h declares
 SIGNATURES = {
     "objnerf_abi_version": (C.c_int, []),
@@ -201,6 +225,13 @@ SIGNATURES = {
     "objnerf_voxel_centroids": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "objnerf_obb_search": (C.c_int, [C.POINTER(ObbArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ABI 10: open-vocabulary queries over the exported map (objnerf_query.hip)
+    "objnerf_project_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64]),
+    "objnerf_project": (C.c_int, [C.POINTER(ProjectArgs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "objnerf_moments_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "objnerf_moments": (C.c_int, [C.POINTER(MomentsArgs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "objnerf_vertex_colors": (C.c_int, [C.POINTER(ColorArgs), C.c_void_p]),
+    "objnerf_rainbow_lut": (C.c_int, [C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,110 @@
+"""Open-vocabulary queries over an exported map (openobj_amd.query.MapQuery on map_vis.pkl.gz):
+
+    python -m openobj_amd.map_query --logdir DIR --mode {rgb,class,instance,partpca,object,part}
+        [--clip-query F.npy --sbert-query F.npy --part-query F.npy --top N --color-yaml PATH
+         --dataset Replica|Scannet --scene NAME] --out DIR
+
+Writes one coloured obj_<id>.ply per visible object (uint8 colours round(c * 255)) and query.json (mode, the visible
+ids, the ranked object ids with their similarities, the top-k ids).  --dataset Replica hides the "ceiling" objects as
+the reference's viewer does by default (vis_interaction.py:181-184); without --dataset every object is written.
+Every argument, query file and query width is checked before the device is touched."""
+from __future__ import annotations
+
+import argparse
+import gzip
+import json
+import os
+import pickle
+
+import numpy as np
+
+MODES = ("rgb", "class", "instance", "partpca", "object", "part")
+NEEDS = {"object": ("clip_query", "sbert_query"), "part": ("clip_query", "sbert_query", "part_query"),
+         "class": ("color_yaml",)}
+
+
+def _width(all_obj, key):
+    for o in all_obj.values():
+        f = o.get(key)
+        if f is not None and np.size(f):
+            return int(np.shape(f)[-1])
+    return None
+
+
+def _parse(argv):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--logdir", required=True)
+    ap.add_argument("--mode", required=True, choices=MODES)
+    ap.add_argument("--clip-query")
+    ap.add_argument("--sbert-query")
+    ap.add_argument("--part-query")
+    ap.add_argument("--top", type=int, default=None)
+    ap.add_argument("--color-yaml")
+    ap.add_argument("--dataset", choices=("Replica", "Scannet"))
+    ap.add_argument("--scene", default="room_0")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    for k in NEEDS.get(a.mode, ()):
+        v = getattr(a, k)
+        if v is None:
+            ap.error(f"--mode {a.mode} needs --{k.replace('_', '-')}")
+        if not os.path.isfile(v):
+            ap.error(f"--{k.replace('_', '-')}: no such file {v}")
+    path = os.path.join(a.logdir, "map_vis.pkl.gz")
+    if not os.path.isfile(path):
+        ap.error(f"{path} is missing: run python -m openobj_amd.map_vis --logdir {a.logdir} first")
+    with gzip.open(path, "rb") as fh:
+        all_obj = pickle.load(fh)
+    queries = {}
+    for k, feat in (("clip_query", "clip_feat"), ("sbert_query", "caption_feat"), ("part_query", "part_feat")):
+        if getattr(a, k) is None or k not in NEEDS.get(a.mode, ()):
+            continue
+        q = np.load(getattr(a, k)).astype(np.float32).reshape(-1)
+        w = _width(all_obj, feat)
+        if w is None or q.size != w:
+            ap.error(f"--{k.replace('_', '-')}: width {q.size} does not match the map's {feat} width {w}")
+        queries[k] = q
+    return a, all_obj, queries
+
+
+def main(argv=None):
+    a, all_obj, q = _parse(argv)
+    from . import mesh as omesh
+    from . import query as oquery
+    mq = oquery.MapQuery(all_obj, a.device)
+    if a.mode == "rgb":
+        col = mq.color_by_rgb()
+    elif a.mode == "class":
+        col = mq.color_by_class(a.color_yaml)
+    elif a.mode == "instance":
+        col = mq.color_by_instance()
+    elif a.mode == "partpca":
+        col = mq.color_by_partfeat()
+    elif a.mode == "object":
+        col = mq.color_by_object_query(q["clip_query"], q["sbert_query"], 0 if a.top is None else a.top)
+    else:
+        col = mq.color_by_part_query(q["clip_query"], q["sbert_query"], q["part_query"], 1 if a.top is None else a.top)
+    hidden = set(mq.hidden_sets(a.dataset, a.scene)["hidden"]) if a.dataset else set()
+    os.makedirs(a.out, exist_ok=True)
+    visible = []
+    for p, (k, c) in enumerate(zip(mq.keys, mq.split(col))):
+        if p in hidden:
+            continue
+        m = all_obj[k]["mesh"]
+        out = omesh.TriMesh(m.vertices, m.faces, m.vertex_normals)
+        out.visual.vertex_colors = np.round(c.cpu().numpy().astype(np.float64) * 255).astype(np.uint8)
+        out.export(os.path.join(a.out, f"obj_{k}.ply"))
+        visible.append(k)
+    rank = mq.last_ranking or []
+    top = [k for k, _ in rank[: (1 if a.top is None else a.top) if a.mode == "part" else (a.top or 0)]]
+    doc = {"mode": a.mode, "visible": [int(k) for k in visible],
+           "ranking": [{"id": int(k), "similarity": s} for k, s in rank], "top": [int(k) for k in top]}
+    with open(os.path.join(a.out, "query.json"), "w") as fh:
+        json.dump(doc, fh, indent=1)
+    print(f"{len(visible)} objects -> {a.out}")
+    return doc
+
+
+if __name__ == "__main__":
+    main()

@@ -1036,3 +1036,124 @@ def object_bounds(objects, intrinsics=None, voxel: float = 0.05, min_extent: flo
     (openobj_amd/bounds.py states the algorithm and its one deviation from trimesh)."""
     from . import bounds
     return bounds.object_bounds(objects, intrinsics, voxel, min_extent, **kw)
+
+
+# ------------------------------------------------------------------------------------------------ ABI 10: map queries
+def _rows(feat: torch.Tensor, name: str):
+    """feat [V, D] fp32 on the device, unit stride along D (any row stride) -> (V, D, row stride)."""
+    if feat.dtype != torch.float32 or not feat.is_cuda or feat.dim() != 2:
+        raise _lib.ObjnerfError(f"{name}: expected a device fp32 [V, D] tensor, got {feat.dtype} {tuple(feat.shape)}")
+    if feat.shape[1] > 1 and feat.stride(1) != 1:
+        raise _lib.ObjnerfError(f"{name}: the feature dimension must be contiguous")
+    V, D = int(feat.shape[0]), int(feat.shape[1])
+    return V, D, max(int(feat.stride(0)), D) if V > 1 else D
+
+
+def _seg(seg_off: torch.Tensor, dev) -> torch.Tensor:
+    s = torch.as_tensor(seg_off, dtype=torch.int64).to(dev).contiguous()
+    if s.dim() != 1 or s.numel() < 2:
+        raise _lib.ObjnerfError("seg_off: expected [S + 1] row offsets")
+    return s
+
+
+def segment_project(feat: torch.Tensor, seg_off, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                    cosine: bool = False, out: Optional[torch.Tensor] = None):
+    """out [V, Q] = feat . W + bias per segment (objnerf_project), W [D, Q] shared or [S, D, Q] per segment (bias [Q] /
+    [S, Q]); cosine=True: F.cosine_similarity of every row against every column of W (vis_interaction.py:372, :388).
+    -> (out [V, Q] fp32, minmax [S, Q, 2] fp32: the min / max of each segment's rows of out, +inf / -inf if empty)."""
+    V, D, rs = _rows(feat, "segment_project")
+    dev = feat.device
+    seg = _seg(seg_off, dev)
+    S = seg.numel() - 1
+    Wt = _req(torch.as_tensor(W).to(device=dev, dtype=torch.float32), torch.float32, "W")
+    per = Wt.dim() == 3
+    if Wt.shape[-2] != D or Wt.dim() not in (2, 3) or (per and Wt.shape[0] != S):
+        raise _lib.ObjnerfError(f"segment_project: W {tuple(Wt.shape)} does not match D = {D}, S = {S}")
+    Q = int(Wt.shape[-1])
+    b = None if bias is None else _req(torch.as_tensor(bias).to(device=dev, dtype=torch.float32), torch.float32, "bias")
+    if b is not None and tuple(b.shape) != ((S, Q) if per else (Q,)):
+        raise _lib.ObjnerfError(f"segment_project: bias {tuple(b.shape)} does not match W")
+    if out is None:
+        out = torch.empty(V, Q, device=dev)
+    minmax = torch.empty(S, Q, 2, device=dev)
+    nbytes = int(lib().objnerf_project_workspace_bytes(S, Q, V))
+    if nbytes == 0:
+        raise _lib.ObjnerfError(f"segment_project: unsupported S = {S}, Q = {Q}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    a = _lib.ProjectArgs(S, D, Q, (_lib.PROJ_COSINE if cosine else 0) | (_lib.PROJ_PER_SEGMENT if per else 0), V, rs,
+                         _ptr(feat) if V else None, _ptr(seg), _ptr(Wt), _ptr(b), _ptr(out), _ptr(minmax))
+    check(lib().objnerf_project(C.byref(a), _ptr(ws), nbytes, _stream()), "objnerf_project")
+    return out, minmax
+
+
+def segment_moments(feat: torch.Tensor, seg_off):
+    """objnerf_moments -> (mean [S, D] fp64, scatter [S, D, D] fp64 = sum of (f - m)(f - m)^T over each segment)."""
+    V, D, rs = _rows(feat, "segment_moments")
+    dev = feat.device
+    seg = _seg(seg_off, dev)
+    S = seg.numel() - 1
+    mean = torch.empty(S, D, dtype=torch.float64, device=dev)
+    scatter = torch.empty(S, D, D, dtype=torch.float64, device=dev)
+    nbytes = int(lib().objnerf_moments_workspace_bytes(S, D))
+    if nbytes == 0:
+        raise _lib.ObjnerfError(f"segment_moments: unsupported S = {S}, D = {D}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    a = _lib.MomentsArgs(S, D, V, rs, _ptr(feat) if V else None, _ptr(seg), _ptr(mean), _ptr(scatter))
+    check(lib().objnerf_moments(C.byref(a), _ptr(ws), nbytes, _stream()), "objnerf_moments")
+    return mean, scatter
+
+
+def vertex_colors(seg_off, mode, V: int, rgb: Optional[torch.Tensor] = None, factor=None, constant=None, column=None,
+                  proj: Optional[torch.Tensor] = None, minmax: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """objnerf_vertex_colors: [V, 3] fp32 colours, per segment mode[s] in _lib.COLOR_* (RGB: rgb [V, >=3] uint8 x
+    factor[s]; CONSTANT: constant[s]; RAINBOW: "rainbow" of proj[:, column[s]] over minmax[s]; PCA: columns 0..2)."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if out is None else out.device
+    seg = _seg(seg_off, dev)
+    S = seg.numel() - 1
+    md = torch.as_tensor(mode, dtype=torch.int32).to(dev).contiguous()
+    if md.numel() != S:
+        raise _lib.ObjnerfError("vertex_colors: one mode per segment")
+    fac = None if factor is None else torch.as_tensor(factor, dtype=torch.float64).to(dev).contiguous()
+    cst = None if constant is None else torch.as_tensor(constant, dtype=torch.float32).to(dev).reshape(S, 3).contiguous()
+    colm = None if column is None else torch.as_tensor(column, dtype=torch.int32).to(dev).contiguous()
+    Q, rs = 0, 0
+    if rgb is not None:
+        if rgb.dtype != torch.uint8 or rgb.dim() != 2 or rgb.shape[1] < 3 or rgb.stride(1) != 1:
+            raise _lib.ObjnerfError("vertex_colors: rgb must be uint8 [V, 3 or 4] with unit channel stride")
+        rs = int(rgb.stride(0))
+    if proj is not None:
+        proj = _req(proj, torch.float32, "proj")
+        Q = int(proj.shape[1])
+    # every array a mode reads must be there and large enough: the kernel trusts these shapes
+    mh = md.cpu().numpy()
+    if ((mh < _lib.COLOR_RGB) | (mh > _lib.COLOR_PCA)).any():
+        raise _lib.ObjnerfError("vertex_colors: unknown mode")
+    if (mh == _lib.COLOR_RGB).any() and (rgb is None or fac is None or fac.numel() != S or rgb.shape[0] < V):
+        raise _lib.ObjnerfError("vertex_colors: RGB needs rgb [V, 3+] and factor [S]")
+    if (mh == _lib.COLOR_CONSTANT).any() and cst is None:
+        raise _lib.ObjnerfError("vertex_colors: CONSTANT needs constant [S, 3]")
+    if ((mh == _lib.COLOR_RAINBOW) | (mh == _lib.COLOR_PCA)).any():
+        if proj is None or minmax is None or proj.shape[0] < V or tuple(minmax.shape) != (S, Q, 2):
+            raise _lib.ObjnerfError("vertex_colors: RAINBOW / PCA need proj [V, Q] and minmax [S, Q, 2]")
+        if (mh == _lib.COLOR_PCA).any() and Q < 3:
+            raise _lib.ObjnerfError("vertex_colors: PCA needs three columns")
+        if (mh == _lib.COLOR_RAINBOW).any():
+            ch = None if colm is None else colm.cpu().numpy()
+            if ch is None or ch.size != S or ((ch[mh == _lib.COLOR_RAINBOW] < 0) | (ch[mh == _lib.COLOR_RAINBOW] >= Q)).any():
+                raise _lib.ObjnerfError("vertex_colors: RAINBOW needs column [S] within proj's Q columns")
+    if out is None:
+        out = torch.empty(V, 3, device=dev)
+    a = _lib.ColorArgs(S, Q, int(V), rs, _ptr(seg), _ptr(md), _ptr(rgb), _ptr(fac), _ptr(cst), _ptr(colm), _ptr(proj),
+                       _ptr(None if minmax is None else _req(minmax, torch.float32, "minmax")), _ptr(out))
+    check(lib().objnerf_vertex_colors(C.byref(a), _stream()), "objnerf_vertex_colors")
+    return out
+
+
+def rainbow_lut() -> np.ndarray:
+    """The colour kernel's "rainbow" table [256, 3] fp32 (objnerf_rainbow_lut, host only)."""
+    out = np.empty((256, 3), np.float32)
+    n = lib().objnerf_rainbow_lut(out.ctypes.data)
+    if n != 256:
+        raise _lib.ObjnerfError("objnerf_rainbow_lut failed")
+    return out
