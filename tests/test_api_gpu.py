@@ -612,7 +612,9 @@ def test_render_fwd_equals_the_unfused_chain(dev, seeded):
     """objnerf_render_fwd (one launch, a lane per ray) against objnerf_box_points -> objnerf_eval_points ->
     objnerf_composite, which fixture G11 pinned to the reference's render_2D_syn in rounds 1-3 (the fused entry is what
     test_render_2d_syn_g11 runs now): same mid-points (also for draws generated in the kernel under the same (seed,
-    draw)), depth / opacity / colour / composited feature hidden to 2e-5, a ragged ray count."""
+    draw)), depth / opacity / colour / composited feature hidden to 2e-5, a ragged ray count.  Both routes share
+    objnerf_mlp32.h, so this is a consistency check of the fusion only: parity with an fp64 chain, the grid-stride loop,
+    want_hfeat=False and the ray regimes live in tests/test_render_gpu.py."""
     torch.manual_seed(21)
     t = trainer.Trainer(make_cfg(dev))
     with torch.no_grad():
@@ -645,7 +647,8 @@ def test_render_fwd_equals_the_unfused_chain(dev, seeded):
 def test_render_fwd_bf16_mode_close_to_fp32(dev):
     """The opt-in bf16-operand renderer (objnerf_render_fwd, mode OBJNERF_TRAIN_BF16) against the fp32 one on the same
     rays and draws: not the reference's arithmetic, so a tolerance of its own -- depth within 2 % of the ray's range,
-    opacity and colour within 0.03, the composited feature hidden within 5 % in norm."""
+    opacity and colour within 0.03, the composited feature hidden within 5 % in norm.  (The bf16 arithmetic itself is
+    held to its specification in tests/test_render_gpu.py.)"""
     torch.manual_seed(22)
     t = trainer.Trainer(make_cfg(dev))
     with torch.no_grad():
