@@ -769,7 +769,6 @@ struct GemmEnv {
     return p;
   }
 };
-// per-row bias factor of the NEXT gemm(E, ) call (feature_head), reset by the caller
 
 // ---- deterministic split-K: partial-tile slabs + an ordered reduction (instead of float atomics)
 #ifndef OBJ_WGRAD_TARGET
@@ -931,6 +930,14 @@ static void launch_reductions(hipStream_t st, RedGroup& rg) {
   if (rg.count) hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)(rg.beg[rg.count] + tail)), dim3(256), 0, st, rg);
   rg.count = 0;
 }
+// items collected into the step's reduction launch (collect != NULL), or launched now as a group of their own
+static void red_emit(hipStream_t st, RedGroup* collect, const RedItem* items, int count) {
+  RedGroup own;
+  own.count = 0;
+  RedGroup& rg = collect ? *collect : own;
+  for (int i = 0; i < count; ++i) red_append(rg, items[i]);
+  if (!collect) launch_reductions(st, own);
+}
 // the layer GEMMs the resident-panel kernel takes (16-bit modes, rows k-contiguous, contraction <= 352, N <= 256)
 static bool panel_ok(const GemmEnv& E, int M, int N, int Kd, long sak, int splitk, bool rowsum, int nz) {
   return OBJ_G16_AFULL && E.operands && sak == 1 && Kd <= 352 && N <= 256 && splitk <= 1 && M >= 4096 && !rowsum &&
@@ -1052,13 +1059,7 @@ static void wgrad(GemmEnv& E, hipStream_t st, int batch, int M, int N, long n, c
     RedItem r;
     r.part = part; r.rs_part = rs_part; r.C = C; r.rowsum = bias_grad;
     r.M = M; r.N = N; r.sk = skd; r.batch = batch; r.scm = scm; r.bsc = bsc; r.bsrs = bsc;
-    if (E.red_group && E.red_group->count < RedGroup::MAXG) {
-      red_append(*E.red_group, r);
-    } else {
-      RedGroup rg;
-      rg.count = 1; rg.beg[0] = 0; rg.beg[1] = red_blocks(r); rg.it[0] = r;
-      hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)rg.beg[1]), dim3(256), 0, st, rg);
-    }
+    red_emit(st, (E.red_group && E.red_group->count < RedGroup::MAXG) ? E.red_group : nullptr, &r, 1);
     return;
   }
 #endif
@@ -1554,7 +1555,7 @@ __global__ __launch_bounds__(512) void mlp_bwd_small_kernel(const BwdSmall a) {
 }
 
 template <int RT>
-static void launch_bwd_small(hipStream_t st, const BwdSmall& f, int K, bool bf) {
+static void launch_small(hipStream_t st, const BwdSmall& f, int K, bool bf) {
   objnerf_once_per_device([] {
     (void)hipFuncSetAttribute((const void*)mlp_bwd_small_kernel<RT, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)bs_lds_bytes<RT>());
@@ -1567,7 +1568,7 @@ static void launch_bwd_small(hipStream_t st, const BwdSmall& f, int K, bool bf) 
 }
 
 template <int RT>
-static void launch_fwd_small(hipStream_t st, const FwdSmall& f, int K, bool bf) {
+static void launch_small(hipStream_t st, const FwdSmall& f, int K, bool bf) {
   objnerf_once_per_device([] {
     (void)hipFuncSetAttribute((const void*)mlp_fwd_small_kernel<RT, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)fs_lds_bytes<RT>());
@@ -1577,6 +1578,17 @@ static void launch_fwd_small(hipStream_t st, const FwdSmall& f, int K, bool bf) 
   dim3 grid((unsigned)((f.n + 16 * RT - 1) / (16 * RT)), (unsigned)K);
   if (bf) hipLaunchKernelGGL((mlp_fwd_small_kernel<RT, true>), grid, dim3(512), fs_lds_bytes<RT>(), st, f);
   else hipLaunchKernelGGL((mlp_fwd_small_kernel<RT, false>), grid, dim3(512), fs_lds_bytes<RT>(), st, f);
+}
+// (RT as a run-time value: small_batch_rt)
+template <class Args>
+static void launch_small_rt(hipStream_t st, const Args& f, int K, bool bf, int rt) {
+  switch (rt) {
+    case 1: launch_small<1>(st, f, K, bf); break;
+    case 2: launch_small<2>(st, f, K, bf); break;
+    case 3: launch_small<3>(st, f, K, bf); break;
+    case 4: launch_small<4>(st, f, K, bf); break;
+    default: launch_small<5>(st, f, K, bf); break;
+  }
 }
 
 #include "objnerf_small_body.h"
@@ -1615,7 +1627,6 @@ static void flush_group(GemmEnv& E, hipStream_t st, GemmGroup& gr) {
   E.group16 = false;
   E.red_group = nullptr;                 // (the caller launches the collected reductions: launch_reductions)
 }
-
 
 // Activation loads of the kernels around the GEMMs: act = 0 fp32 storage, 1 bf16, 2 fp16 (the 16-bit modes keep
 // h1 .. hc in the operand type at hidden 256: half the traffic of the HBM-bound layer GEMMs).
@@ -2132,7 +2143,7 @@ size_t train_workspace_bytes(const objnerf_net* net, int K, int R, int S, int fe
 struct objnerf_context {
   static constexpr int NEV = 16, NS = 3;
   hipStream_t s = nullptr;             // = all[0]
-  hipStream_t all[NS];                 // small batches: the independent weight-gradient GEMMs spread over three streams
+  hipStream_t all[NS];                 // train_step forks onto all[0] only (all[1..] and their events are created but idle)
   hipEvent_t ev[NEV];
   hipEvent_t done, done_all[NS];
   bool own = false;                    // false: single-stream stand-in (all[] = the caller's stream, no events)
@@ -2196,9 +2207,397 @@ __global__ void form_points_kernel(long total, int S, const float* origins, cons
   for (int x = 0; x < 3; ++x) pts[i * 3 + x] = (origins[ray * 3 + x] + dirs[ray * 3 + x] * zz) - centre;
 }
 
-// forward declaration: the one-launch iteration (after the workspace carve below)
+// ------------------------------------------------------------------------------------------------
+// The OccupancyMap chain (model.py:61-103), described once:  in -> mid1 -> cat(+x1) -> mid2 -> colour(+x2) -> heads,
+// with the feature layer (+x2) beside the colour layer.  train_step, train_step_small, eval_points and mlp_backward
+// emit their layer GEMMs through layer_fwd / layer_wgrad / layer_dgrad: a layer's operand strides are written here only.
+constexpr int T_TRAINED_END = OBJNERF_T_FL_W;      // off[..]: end of the tensors that always receive a gradient
+constexpr int T_FEAT_END = OBJNERF_T_PE_B;         // off[..]: end of the feature branch (feature layer + 512-d head)
+enum { L_IN, L_M1, L_CAT, L_M2, L_CL, L_FL };
+struct LayerDesc {
+  int w, b;            // OBJNERF_T_* of the weight [H][ld] and the bias [H]
+  int in_main;         // width of the main input: E1 (the in layer reads x1 = emb[:, 0 : E1) itself) or H
+  int in_side;         // width of the side input behind the main one in the weight's rows (0: none) ...
+  int side_col;        // ... and its first column of emb (x1: 0, x2: E1)
+  int ld() const { return in_main + in_side; }
+  bool from_emb() const { return w == OBJNERF_T_IN_W; }
+};
+static LayerDesc layer_desc(int l, int H) {
+  switch (l) {
+    case L_IN: return {OBJNERF_T_IN_W, OBJNERF_T_IN_B, OBJ_E1, 0, 0};
+    case L_M1: return {OBJNERF_T_M1_W, OBJNERF_T_M1_B, H, 0, 0};
+    case L_CAT: return {OBJNERF_T_CAT_W, OBJNERF_T_CAT_B, H, OBJ_E1, 0};
+    case L_M2: return {OBJNERF_T_M2_W, OBJNERF_T_M2_B, H, 0, 0};
+    case L_CL: return {OBJNERF_T_CL_W, OBJNERF_T_CL_B, H, OBJ_E2, OBJ_E1};
+    default: return {OBJNERF_T_FL_W, OBJNERF_T_FL_B, H, OBJ_E2, OBJ_E1};
+  }
+}
+// one call's view of the K stacked networks and its activation / gradient buffers ([K][n][H] each, NULL: not present)
+struct NetView {
+  const float* P; float* G; long ps; const int64_t* off; int K; long n; int H;
+  const float* emb; float* d_emb;                           // [K][n][OBJ_EMB]
+  float *h1, *h2, *h3, *h4, *hc, *hf;
+  float *d_hc, *d_h4, *d_h3, *d_h2, *d_h1, *d_hf;
+};
+struct Rows { const float* p; long ld, bs; };               // a [K][n][ld] operand: row stride, batch stride
+static Rows main_rows(const NetView& c, const LayerDesc& L, const float* h) {
+  return L.from_emb() ? Rows{c.emb, OBJ_EMB, c.n * OBJ_EMB} : Rows{h, c.H, c.n * c.H};
+}
+static Rows side_rows(const NetView& c, const LayerDesc& L) { return Rows{c.emb + L.side_col, OBJ_EMB, c.n * OBJ_EMB}; }
+
+// out = relu([in | side] W^T + b).  fuse2: [in | side] as ONE contraction (the resident-panel kernel reads the side
+// input as its second A source: no round trip of the partial result)
+static void layer_fwd(GemmEnv& E, hipStream_t st, const NetView& c, const LayerDesc& L, const float* in, float* out,
+                      bool fuse2 = false) {
+  const int H = c.H, K = c.K, M = (int)c.n;
+  const long nH = c.n * H, ps = c.ps;
+  const Rows a = main_rows(c, L, in), s = side_rows(c, L);
+  const float *W = c.P + c.off[L.w], *b = c.P + c.off[L.b];
+  if (!L.in_side || fuse2) {
+    if (L.in_side) E.a2 = A2Src{s.p, s.ld, s.bs, L.in_main};
+    gemm(E, st, K, M, H, L.ld(), a.p, a.ld, 1, a.bs, W, 1, L.ld(), ps, out, H, 1, nH, false, b, ps, true);
+  } else {
+    gemm(E, st, K, M, H, L.in_main, a.p, a.ld, 1, a.bs, W, 1, L.ld(), ps, out, H, 1, nH);
+    gemm(E, st, K, M, H, L.in_side, s.p, s.ld, 1, s.bs, W + L.in_main, 1, L.ld(), ps, out, H, 1, nH, true, b, ps, true);
+  }
+}
+// d W = d_out^T [in | side], d b = column sums of d_out (riding on the main part's GEMM: row sums of its operand tile)
+static void layer_wgrad(GemmEnv& E, hipStream_t st, const NetView& c, const LayerDesc& L, const float* d_out,
+                        const float* in) {
+  const int H = c.H, K = c.K;
+  const long n = c.n, nH = n * H, ps = c.ps;
+  const Rows a = main_rows(c, L, in), s = side_rows(c, L);
+  float *dW = c.G + c.off[L.w], *db = c.G + c.off[L.b];
+  wgrad(E, st, K, H, L.in_main, n, d_out, 1, H, nH, a.p, a.ld, 1, a.bs, dW, L.ld(), ps, db);
+  if (L.in_side) wgrad(E, st, K, H, L.in_side, n, d_out, 1, H, nH, s.p, s.ld, 1, s.bs, dW + L.in_main, L.ld(), ps);
+}
+// d_in (+)= (d_out W_main) o [mask > 0] and d_emb[:, side columns] (+)= d_out W_side; the in layer's input IS x1, so its
+// main part lands in d_emb.  fold_dhead (colour layer without the feature branch): the alpha head's rank-1 term
+// wa x dhead[:, 0] is added in the epilogue (Gemm::biasrow), so d_in is written once instead of written, read and written.
+static void layer_dgrad(GemmEnv& E, hipStream_t st, const NetView& c, const LayerDesc& L, const float* d_out, float* d_in,
+                        const float* mask, bool accumulate, bool side_accumulate = false, const float* fold_dhead = nullptr) {
+  const int H = c.H, K = c.K, M = (int)c.n;
+  const long n = c.n, nH = n * H, ps = c.ps;
+  const float* W = c.P + c.off[L.w];
+  float* out = L.from_emb() ? c.d_emb : d_in;
+  const long ldo = L.from_emb() ? OBJ_EMB : H, bso = n * ldo;
+  const float* wa = fold_dhead ? c.P + c.off[OBJNERF_T_ALPHA_W] : nullptr;      // (the folded form overwrites)
+  if (fold_dhead) { E.biasrow = fold_dhead; E.bsbr = n * 4; E.sbr = 4; }
+  gemm(E, st, K, M, L.in_main, H, d_out, H, 1, nH, W, L.ld(), 1, ps, out, ldo, 1, bso, accumulate && !wa, wa, wa ? ps : 0,
+       false, mask, mask ? H : 0, mask ? 1 : 0, mask ? nH : 0);
+  E.biasrow = nullptr; E.bsbr = 0; E.sbr = 1;
+  if (L.in_side)
+    gemm(E, st, K, M, L.in_side, H, d_out, H, 1, nH, W + L.in_main, L.ld(), 1, ps, c.d_emb + L.side_col, OBJ_EMB, 1,
+         n * OBJ_EMB, side_accumulate);
+}
+// h1 .. hc, alpha / color and (hf != NULL) the feature layer.  act16: h1 .. hc live in the operand type (train_step)
+static void forward_chain(GemmEnv& E, hipStream_t st, const NetView& c, float* alpha, float* color, float* hf, int act16) {
+  const int H = c.H;
+  const bool fuse2 = panel_ok(E, (int)c.n, H, H + OBJ_E1, 1, 1, false, c.K) && H == 256;
+  layer_fwd(E, st, c, layer_desc(L_IN, H), nullptr, c.h1);
+  layer_fwd(E, st, c, layer_desc(L_M1, H), c.h1, c.h2);
+  layer_fwd(E, st, c, layer_desc(L_CAT, H), c.h2, c.h3, fuse2);
+  layer_fwd(E, st, c, layer_desc(L_M2, H), c.h3, c.h4);
+  layer_fwd(E, st, c, layer_desc(L_CL, H), c.h4, c.hc, fuse2);
+  hipLaunchKernelGGL(heads_fwd_kernel, dim3((unsigned)((c.n + 15) / 16), (unsigned)c.K), dim3(256),
+                     (size_t)4 * H * sizeof(float), st, H, c.n, c.h4, c.hc, c.P, c.ps, (int)c.off[OBJNERF_T_ALPHA_W],
+                     (int)c.off[OBJNERF_T_ALPHA_B], (int)c.off[OBJNERF_T_OC_W], (int)c.off[OBJNERF_T_OC_B], alpha, color, act16);
+  if (hf) layer_fwd(E, st, c, layer_desc(L_FL, H), c.h4, hf);
+}
+// the weight gradients alone (the dgrad chain ran in a kernel of its own): colour, mid2, cat, mid1, in; the feature
+// layer first (train_step's small-batch branch) or last (train_step_small) -- GemmGroup slots and slab addresses follow
+static void wgrad_chain(GemmEnv& E, hipStream_t st, const NetView& c, bool feat, bool feat_first) {
+  const int H = c.H;
+  if (feat && feat_first) layer_wgrad(E, st, c, layer_desc(L_FL, H), c.d_hf, c.h4);
+  layer_wgrad(E, st, c, layer_desc(L_CL, H), c.d_hc, c.h4);
+  layer_wgrad(E, st, c, layer_desc(L_M2, H), c.d_h4, c.h3);
+  layer_wgrad(E, st, c, layer_desc(L_CAT, H), c.d_h3, c.h2);
+  layer_wgrad(E, st, c, layer_desc(L_M1, H), c.d_h2, c.h1);
+  layer_wgrad(E, st, c, layer_desc(L_IN, H), c.d_h1, nullptr);
+  if (feat && !feat_first) layer_wgrad(E, st, c, layer_desc(L_FL, H), c.d_hf, c.h4);
+}
+// the layer-wise backward from d_hc / d_h4 (heads_bwd_kernel) and d_hf: per layer the weight gradient on `wst` and the
+// input gradient on `st`; fork() runs ahead of every layer but the feature layer (whose caller has just forked).
+// d_emb needs no zero fill: the first dgrad into each column block overwrites (x2: feature layer if present, else
+// colour layer; x1: cat layer), later ones accumulate; columns 0..2 (d t) are never read.
+template <class Fork>
+static void backward_chain(GemmEnv& E, hipStream_t st, hipStream_t wst, const NetView& c, bool feat,
+                           const float* fold_dhead, Fork fork) {
+  const int H = c.H;
+  if (feat) {     // feature layer: grads + contributions to d_h4 / d_x2
+    const LayerDesc L = layer_desc(L_FL, H);
+    layer_wgrad(E, wst, c, L, c.d_hf, c.h4);
+    layer_dgrad(E, st, c, L, c.d_hf, c.d_h4, nullptr, true, false);
+  }
+  const struct { int l; const float* d_out; float* h; float* d_in; bool acc; } steps[5] = {
+      {L_CL, c.d_hc, c.h4, c.d_h4, true},       // colour layer (acc is IGNORED with fold_dhead: that form overwrites d_h4)
+      {L_M2, c.d_h4, c.h3, c.d_h3, false},      // mid2:  d_h4 (masked above) -> grads, d_h3
+      {L_CAT, c.d_h3, c.h2, c.d_h2, false},     // cat layer
+      {L_M1, c.d_h2, c.h1, c.d_h1, false},      // mid1
+      {L_IN, c.d_h1, nullptr, nullptr, true}};  // in layer
+  for (const auto& s : steps) {
+    const LayerDesc L = layer_desc(s.l, H);
+    fork();
+    layer_wgrad(E, wst, c, L, s.d_out, s.h);
+    layer_dgrad(E, st, c, L, s.d_out, s.d_in, s.h, s.acc, s.l == L_CL && feat, s.l == L_CL ? fold_dhead : nullptr);
+  }
+}
+// ordered reductions into the gradient arena: a head's block partials [K][sk][rows][H] + [K][sk][rows], d B's [K][sk][63]
+static RedItem head_red_item(const NetView& c, int t_w, int t_b, int rows, const float* part, const float* rs_part, int sk) {
+  RedItem r;
+  r.part = part; r.rs_part = rs_part; r.C = c.G + c.off[t_w]; r.rowsum = c.G + c.off[t_b];
+  r.M = rows; r.N = c.H; r.sk = sk; r.batch = c.K; r.scm = c.H; r.bsc = c.ps; r.bsrs = c.ps;
+  return r;
+}
+// workgroups of pe_bwd_kernel per object: 12 samples per block and pass, at least 4 passes per block
+static int pe_bwd_blocks(long n) { return (int)std::min(std::max((n + 47) / 48, 1L), 1024L); }
+static RedItem pe_red_item(const NetView& c, const float* part, int sk) {
+  RedItem r;
+  r.part = part; r.rs_part = nullptr; r.C = c.G + c.off[OBJNERF_T_PE_B]; r.rowsum = nullptr;
+  r.M = 1; r.N = 63; r.sk = sk; r.batch = c.K; r.scm = 63; r.bsc = c.ps; r.bsrs = 0;
+  return r;
+}
+// the parameter offsets of the one-launch kernels' argument structs (FwdSmall, BwdSmall, SmallFused)
+template <class T> static void set_weight_offsets(T& f, const int64_t* off) {
+  f.o_in_w = (int)off[OBJNERF_T_IN_W]; f.o_m1_w = (int)off[OBJNERF_T_M1_W]; f.o_cat_w = (int)off[OBJNERF_T_CAT_W];
+  f.o_m2_w = (int)off[OBJNERF_T_M2_W]; f.o_cl_w = (int)off[OBJNERF_T_CL_W]; f.o_fl_w = (int)off[OBJNERF_T_FL_W];
+}
+template <class T> static void set_forward_offsets(T& f, const int64_t* off) {
+  set_weight_offsets(f, off);
+  f.o_in_b = (int)off[OBJNERF_T_IN_B]; f.o_m1_b = (int)off[OBJNERF_T_M1_B]; f.o_cat_b = (int)off[OBJNERF_T_CAT_B];
+  f.o_m2_b = (int)off[OBJNERF_T_M2_B]; f.o_cl_b = (int)off[OBJNERF_T_CL_B]; f.o_fl_b = (int)off[OBJNERF_T_FL_B];
+  f.o_a_w = (int)off[OBJNERF_T_ALPHA_W]; f.o_a_b = (int)off[OBJNERF_T_ALPHA_B];
+  f.o_oc_w = (int)off[OBJNERF_T_OC_W]; f.o_oc_b = (int)off[OBJNERF_T_OC_B];
+}
+
+// ---- the hoisted 512-d feature head on the caller's GemmEnv and stream.  The head is NOT applied per
+// sample: per object G = W_of^T W_of (+ wb, bb), per ray u = W_of^T g, beta, |g| ahead of the loss; behind it the head's
+// gradient d W_of = gt_feat^T [a fh] + W_of M2 + b_of m1^T, d b_of = gt_feat^T [a O] + W_of m1 + b_of s2 from the moments
+// [M2 m1; . s2] = [c fh | c O]^T [fh | O]: two split-K GEMMs over the rays + a small finish
+struct FeatHeadArgs { int K, R, Hh, C; const float* P; long ps; int off_w, off_b; const float* gt_feat; };
+static void feat_gram_gemm(GemmEnv& E, hipStream_t st, const FeatHeadArgs& h, float* gram, long gst) {
+  gemm(E, st, h.K, h.Hh, h.Hh, h.C, h.P + h.off_w, 1, h.Hh, h.ps, h.P + h.off_w, h.Hh, 1, h.ps, gram, h.Hh, 1, gst);
+}
+static void feat_rays_gemm(GemmEnv& E, hipStream_t st, const FeatHeadArgs& h, float* rayin) {
+  const long R = h.R;
+  gemm(E, st, h.K, h.R, h.Hh, h.C, h.gt_feat, h.C, 1, R * h.C, h.P + h.off_w, h.Hh, 1, h.ps, rayin, h.Hh + 2, 1,
+       R * (h.Hh + 2));
+}
+static void feat_gram_enqueue(GemmEnv& E, hipStream_t st, const FeatHeadArgs& h, float* gram, long gst) {
+  feat_gram_gemm(E, st, h, gram, gst);
+  hipLaunchKernelGGL(featg_wb_kernel, dim3(h.Hh + 1, h.K), dim3(64), 0, st, h.P, h.ps, h.off_w, h.off_b, h.C, h.Hh, gram, gst);
+}
+static void feat_prep_enqueue(GemmEnv& E, hipStream_t st, const FeatHeadArgs& h, const FeatHead& f) {
+  feat_gram_enqueue(E, st, h, f.gram, (long)h.Hh * h.Hh + h.Hh + 1);
+  feat_rays_gemm(E, st, h, f.rayin);
+  hipLaunchKernelGGL(featg_rowstats_kernel, dim3((unsigned)((h.R + 15) / 16), h.K), dim3(256), 0, st, h.P, h.ps, h.off_b, h.C,
+                     h.R, h.Hh + 2, h.gt_feat, f.rayin);
+}
+// T = gt_feat^T [a fh | a O], M = [c fh | c O]^T [fh | O] over the rays (X1 / X2: featg_scale_kernel or the fused kernel)
+static void feat_moments_enqueue(GemmEnv& E, hipStream_t st, const FeatHeadArgs& h, const FeatHead& f) {
+  const int XC = h.Hh + 1;
+  const long R = h.R;
+  wgrad(E, st, h.K, h.C, XC, R, h.gt_feat, 1, h.C, R * h.C, f.X1, XC, 1, R * XC, f.Tm, XC, (long)h.C * XC);
+  wgrad(E, st, h.K, XC, XC, R, f.X2, 1, XC, R * XC, f.rayfeat, h.Hh + 3, 1, R * (h.Hh + 3), f.mom, XC, (long)XC * XC);
+}
+// d W_of = T + W_of M + b_of m^T, d b_of likewise
+static void feat_finish_enqueue(hipStream_t st, const FeatHeadArgs& h, const FeatHead& f, float* grads) {
+  hipLaunchKernelGGL(featg_finish_kernel, dim3((unsigned)(((long)h.C * (h.Hh + 1) + 255) / 256), h.K), dim3(256), 0, st, h.P,
+                     h.ps, h.off_w, h.off_b, h.C, h.Hh, f.Tm, f.mom, grads);
+}
+static FeatHeadArgs feat_head_args(const NetView& c, int R, int C, const float* gt_feat) {
+  return {c.K, R, c.H, C, c.P, c.ps, (int)c.off[OBJNERF_T_OF_W], (int)c.off[OBJNERF_T_OF_B], gt_feat};
+}
+static NetView net_view(const WS& w, const float* P, float* G, long ps, const int64_t* off, int K, long n, int H) {
+  NetView c;
+  c.P = P; c.G = G; c.ps = ps; c.off = off; c.K = K; c.n = n; c.H = H;
+  c.emb = w.emb; c.d_emb = w.d_emb;
+  c.h1 = w.h1; c.h2 = w.h2; c.h3 = w.h3; c.h4 = w.h4; c.hc = w.hc; c.hf = w.hf;
+  c.d_hc = w.dA; c.d_h4 = w.dB_; c.d_h3 = w.dC; c.d_h2 = w.dD; c.d_h1 = w.dE; c.d_hf = w.d_hf;
+  return c;
+}
+// test hook (objnerf_train_args.relu_masks): the iteration's ReLU branch bits; act16 / hf16: storage type of h1 .. hc / hf
+static void emit_relu_masks(hipStream_t st, const NetView& c, uint8_t* masks, int act16, int hf16) {
+  const float* acts[6] = {c.h1, c.h2, c.h3, c.h4, c.hc, c.hf};
+  const long nb = (long)c.K * c.n * (c.H / 8);
+  for (int l = 0; l < 6; ++l)
+    if (acts[l])
+      hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, nb, c.H, acts[l], masks, l,
+                         l < 5 ? act16 : hf16);
+}
+static FeatHead feat_head_view(const WS& w) { return {w.gram, w.rayin, w.rayfeat, w.X1, w.X2, w.Tm, w.mom, nullptr, 0}; }
+
+// The one-launch small-batch iteration: train_small_kernel -> the seven weight-gradient GEMMs as ONE grouped launch ->
+// ONE reduction launch (weight-gradient slices, head / d B / loss partials, status, optionally AdamW).  Everything on
+// the caller's stream: three dependent launches need no helper stream and no events.
 static int train_step_small(const objnerf_net* net, const objnerf_train_args* a, hipStream_t st, GemmEnv& E, const WS& w,
-                            const int64_t* off, bool bf, int* done);
+                            const int64_t* off, bool bf, int* done) {
+  const int H = net->hidden, K = a->K, S = a->S, C = net->feat_dim;
+  const long n = (long)a->R * S, ps = a->p_stride;
+  const bool feat = a->gt_feat != nullptr;
+  const int rpw = sf_rays_per_wg(S, feat);
+  const int nwg = (int)(((long)a->R + rpw - 1) / rpw);
+  const float* P = a->params;
+  float* G = a->grads;
+  const NetView c = net_view(w, P, G, ps, off, K, n, H);
+  const FeatHeadArgs fh = feat_head_args(c, a->R, C, a->gt_feat); const FeatHead fhb = feat_head_view(w);
+  const bool self_counts = (a->mode & OBJNERF_TRAIN_SELF_COUNTS) != 0;
+  if (self_counts && K > 1) {        // several objects: the cross-object flags need every object's labels (one small launch)
+    const int rc0 = objnerf_label_counts(K, a->R, a->labels, const_cast<int32_t*>(a->counts), const_cast<int32_t*>(a->flags),
+                                         (void*)st);
+    if (rc0) return rc0;
+  }
+  const long R = a->R;
+  const int XC = H + 1;
+  float* head_snap = nullptr;          // [K][C (H + 1)]: [W_of | b_of] before the step (FeatPrepTask), for the fused finish + AdamW
+  if (feat) {
+    // the 512-d head's preparation does not depend on the forward pass: ahead of the fused launch
+    const long gst = (long)H * H + H + 1;
+    E.operands = 0;
+    // Round 6: ONE launch for the four (the two GEMMs as a group, wb / bb, the rays' beta and |g| and -- with an optimiser
+    // attached -- the copy of [W_of | b_of] the head's finish reads, as extra workgroups of the same launch: FeatPrepTask)
+    head_snap = a->optim ? E.parts_alloc((size_t)K * C * XC) : nullptr;
+    GemmGroup g0;
+    g0.count = 0;
+    E.group = &g0; E.group16 = false;
+    feat_gram_gemm(E, st, fh, w.gram, gst);
+    feat_rays_gemm(E, st, fh, w.rayin);
+    if (E.error) return OBJNERF_EINVAL;
+    if (g0.count == 2) {
+      FeatPrepTask& t = g0.task;
+      t.params = P; t.ps = ps; t.off_w = fh.off_w; t.off_b = fh.off_b; t.C = C; t.Hh = H; t.R = (int)R; t.rin_ld = H + 2;
+      t.K = K; t.gt_feat = a->gt_feat; t.rayin = w.rayin; t.gram = w.gram; t.gstride = gst; t.snap = head_snap;
+      t.nb_wb = (H + 1 + 7) / 8; t.nb_rs = (int)((R + 31) / 32);
+      t.nb_snap = head_snap ? (int)(((long)C * XC + 2047) / 2048) : 0;
+      t.blocks = K * (t.nb_wb + t.nb_rs + t.nb_snap);
+      flush_group(E, st, g0);
+    } else {      // (cannot happen for these shapes: the group is dropped, all four launches are redone ungrouped)
+      E.group = nullptr;
+      head_snap = nullptr;
+      feat_prep_enqueue(E, st, fh, fhb);
+    }
+  }
+  SmallFused f;
+  f.K = K; f.R = a->R; f.S = S; f.rpw = rpw;
+  f.fs = a->feat_scaling;
+  f.rayin = w.rayin; f.gram = w.gram; f.hf = w.hf; f.d_hf = w.d_hf; f.rayfeat = w.rayfeat; f.X1 = w.X1; f.X2 = w.X2;
+  f.params = P; f.ps = ps; f.scale = a->scale;
+  f.pts = a->pts; f.origins = a->origins; f.dirs = a->dirs; f.z = a->z; f.centre = a->obj_center;
+  f.gt_depth = a->gt_depth; f.gt_rgb = a->gt_rgb; f.labels = a->labels;
+  f.counts = const_cast<int*>(a->counts); f.flags = const_cast<int*>(a->flags); f.self_counts = (self_counts && K == 1) ? 1 : 0;
+  f.cs = a->color_scaling; f.os = a->opacity_scaling;
+  f.emb = w.emb; f.h1 = w.h1; f.h2 = w.h2; f.h3 = w.h3; f.h4 = w.h4; f.hc = w.hc;
+  f.d_hc = c.d_hc; f.d_h4 = c.d_h4; f.d_h3 = c.d_h3; f.d_h2 = c.d_h2; f.d_h1 = c.d_h1;
+  // per-workgroup partials live in workspace regions this path does not use otherwise (d_emb: K n 129 floats, dhead:
+  // K n 4, loss_part: K R 4): objnerf_train_step's applicability test checked that they fit
+  float* hp = w.d_emb;
+  f.partA = hp; hp += (size_t)K * nwg * H;
+  f.partW = hp; hp += (size_t)K * nwg * 3 * H;
+  f.rsA = hp; hp += (size_t)K * nwg;
+  f.rsW = hp;
+  f.pe_part = w.dhead;
+  f.loss_part = w.loss_part;
+  set_forward_offsets(f, off);
+  f.o_B = (int)off[OBJNERF_T_PE_B];
+  if (feat) {
+    if (rpw * S <= 64) launch_train_small<4, true>(st, f, nwg, bf);
+    else launch_train_small<5, true>(st, f, nwg, bf);
+  } else {
+    if (rpw * S <= 64) launch_train_small<4, false>(st, f, nwg, bf);
+    else launch_train_small<5, false>(st, f, nwg, bf);
+  }
+  if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
+  if (a->relu_masks) emit_relu_masks(st, c, a->relu_masks, bf ? 1 : 0, bf ? 1 : 0);
+  if (bf) {
+    // bf16 mode: the kernel above stored h1 .. hc (hf, d_hf) and d_hc .. d_h1 as bf16 (objnerf_small_body.h, `hst`); gemm(E, )
+    // recognises 16-bit operands by address and the grouped launch passes them through unconverted
+    E.act16_lo = (const char*)w.h1;
+    E.act16_hi = feat ? (const char*)(w.d_hf + (size_t)K * n * H) : (const char*)(w.hc + w.act_floats);
+    E.grad16_lo = (const char*)w.dA; E.grad16_hi = (const char*)(w.dE + w.act_floats);
+  }
+  // ---- the step's reductions, collected: head partials, d B partials, the weight gradients' split-K slices
+  RedGroup red;
+  red.count = 0;
+  const RedItem partials[3] = {head_red_item(c, OBJNERF_T_ALPHA_W, OBJNERF_T_ALPHA_B, 1, f.partA, f.rsA, nwg),
+                               head_red_item(c, OBJNERF_T_OC_W, OBJNERF_T_OC_B, 3, f.partW, f.rsW, nwg),
+                               pe_red_item(c, f.pe_part, nwg)};
+  red_emit(st, &red, partials, 3);
+  E.operands = 0;                   // (the grouped launch picks its operand type through group16)
+  E.a_scale = 1.0f;
+  GemmGroup group;
+  group.count = 0;
+  E.group = &group;
+  E.group16 = bf;
+  E.red_group = &red;
+  E.need_parts = true;              // no zero-filled gradient arena here: the deterministic slab form or an error
+  // Split-K slices of the grouped launch: its seven GEMMs are ONE 128 x 128 tile each, so `slices` is also the number of
+  // workgroups per GEMM.  ~2 rounds of the chip (7 x 37 = 259 workgroups at least), at most ~1024 samples per slice
+  // beyond that: every slice writes its partial tile to HBM and the reduction reads it back -- 128 slices at the
+  // benchmark's 76 800 background samples were 48 MB each way for 0.4 MB of gradient (reduction 131 us).
+  {
+    long want = (n + 1023) / 1024;
+    if (want < 36) want = 36;
+    // whole rounds of the chip: 7 GEMMs x slices workgroups on num_cu compute units (75 slices = 525 workgroups left a
+    // third round for 13 of them: 260 us against 227)
+    const int cu = 256, ng = feat ? 9 : 7;
+    long rounds = (want * ng + cu / 2) / cu;
+    if (rounds < 1) rounds = 1;
+    E.max_slices = (int)(rounds * cu / ng);
+  }
+  wgrad_chain(E, st, c, feat, false);       // (the feature layer LAST here: the slots of the other seven do not move with it)
+  if (E.parts_failed || E.error) return OBJNERF_EINVAL;
+  flush_group(E, st, group);
+  if (feat) {
+    // the 512-d head's moments over the RAYS (featg_finish_kernel turns them into d W_of, d b_of after the reduction).
+    // A grouped launch of their own: inside the other one their 512-row output made it 5x slower (1.82 against 0.35 ms
+    // at the benchmark's background batch -- every GEMM of the group is then launched over four row tiles)
+    GemmGroup g2;
+    g2.count = 0;
+    E.group = &g2; E.group16 = false; E.operands = 0; E.red_group = &red; E.max_slices = 0;
+    feat_moments_enqueue(E, st, fh, fhb);
+    if (E.parts_failed || E.error) return OBJNERF_EINVAL;
+    RedGroup* keep = E.red_group;
+    flush_group(E, st, g2);              // (launches whatever was collected; GEMMs the group does not take were launched at once)
+    E.red_group = keep;
+  }
+  red.tail.loss_part = f.loss_part; red.tail.loss_blocks = nwg; red.tail.K = K; red.tail.loss_terms = a->loss_terms;
+  red.tail.status = a->status;
+  if (a->optim) {
+    const objnerf_adamw_args* o = a->optim;
+    RedTail& t = red.tail;
+    t.params = const_cast<float*>(a->params); t.grads = G; t.m = o->exp_avg; t.v = o->exp_avg_sq; t.flags = a->flags;
+    t.steps = o->group_steps; t.bank = o->bank; t.p_stride = ps; t.arena_floats = (long)K * ps;
+    t.lo1 = off[OBJNERF_T_CL_W]; t.lo2 = off[OBJNERF_T_FL_W]; t.hi2 = off[OBJNERF_T_PE_B];
+    t.lr = (double)o->lr; t.b1 = (double)o->beta1; t.b2 = (double)o->beta2; t.wd = (double)o->weight_decay; t.eps = o->eps;
+    if (done) *done |= 2;
+  }
+  launch_reductions(st, red);
+  if (feat && a->optim && head_snap) {
+    // the head's gradient AND its AdamW step in one launch, from the copy of [W_of | b_of] (round 6)
+    const objnerf_adamw_args* o = a->optim;
+    FeatFinishOpt fo;
+    fo.params = const_cast<float*>(a->params); fo.m = o->exp_avg; fo.v = o->exp_avg_sq; fo.flags = a->flags;
+    fo.steps = o->group_steps; fo.bank = o->bank;
+    fo.lr = (double)o->lr; fo.b1 = (double)o->beta1; fo.b2 = (double)o->beta2; fo.wd = (double)o->weight_decay; fo.eps = o->eps;
+    hipLaunchKernelGGL(featg_finish_adamw_kernel, dim3((unsigned)(((long)C * XC + 255) / 256), K), dim3(256), 0, st, head_snap, ps,
+                       fh.off_w, fh.off_b, C, H, w.Tm, w.mom, G, fo);
+  } else if (feat) {
+    feat_finish_enqueue(st, fh, fhb, G);
+    if (a->optim) {               // the head's own entries [of_w, pe_b): their gradient exists only now
+      const objnerf_adamw_args* o = a->optim;
+      // (entries [of_w, pe_b) only: "P" = off[PE_B] with [0, of_w) skipped -- B's gradient behind them was stepped
+      // by the reduction launch)
+      const int rc = objmisc::adamw_flags_range(K, off[OBJNERF_T_PE_B], ps, const_cast<float*>(a->params), G, o->exp_avg,
+                                                o->exp_avg_sq, nullptr, a->flags, o->group_steps, o->bank,
+                                                off[OBJNERF_T_CL_W], off[OBJNERF_T_FL_W], off[OBJNERF_T_PE_B], 0,
+                                                off[OBJNERF_T_OF_W], o->lr, o->beta1, o->beta2, o->eps, o->weight_decay,
+                                                (void*)st);
+      if (rc) return rc;
+    }
+  }
+  if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
+  return OBJNERF_OK;
+}
 
 int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* stream, int* done) {
   objnerf_train_args a_local = *a_in;
@@ -2249,8 +2648,8 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
   }
   const float* P = a->params;
   float* G = a->grads;
-  const int E1 = OBJ_E1, E2 = OBJ_E2, EM = OBJ_EMB;
-  const long nH = n * H;
+  const NetView c = net_view(w, P, G, ps, off, K, n, H);
+  const FeatHeadArgs fh = feat_head_args(c, a->R, C, a->gt_feat); const FeatHead fhb = feat_head_view(w);
 
   // helper stream: work that only READS what the main chain produced (or, for the feature preparation below, only
   // parameters and inputs) runs beside it; fork = the side stream waits for everything enqueued on `st` so far
@@ -2260,11 +2659,10 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
   Side& sd = a->context ? *(Side*)a->context : single;
   const bool multi = sd.own;
   int fk = 0;
-  const int n_side = 1;
   auto fork = [&]() {
     if (!multi) return;
     (void)hipEventRecord(sd.ev[fk], st);
-    for (int i = 0; i < n_side; ++i) (void)hipStreamWaitEvent(sd.all[i], sd.ev[fk], 0);
+    (void)hipStreamWaitEvent(sd.s, sd.ev[fk], 0);
     fk = (fk + 1) % Side::NEV;
   };
   hipStream_t ss = sd.s;
@@ -2273,19 +2671,13 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
   // "untouched").  The previous step's consumer of the gradient arena (AdamW) is ordered before this fork.
   fork();
   for (int k = 0; k < K; ++k) {
-    (void)hipMemsetAsync(a->grads + (long)k * ps, 0, (size_t)off[14] * 4, ss);
-    if (feat) (void)hipMemsetAsync(a->grads + (long)k * ps + off[14], 0, (size_t)(off[18] - off[14]) * 4, ss);
+    (void)hipMemsetAsync(a->grads + (long)k * ps, 0, (size_t)off[T_TRAINED_END] * 4, ss);
+    if (feat)
+      (void)hipMemsetAsync(a->grads + (long)k * ps + off[T_TRAINED_END], 0, (size_t)(off[T_FEAT_END] - off[T_TRAINED_END]) * 4, ss);
   }
   if (feat) {
-    // the 512-d head is NOT applied per sample: per object G = W_of^T W_of (+ wb, bb), per ray u = W_of^T g, beta, |g|.
-    // None of it depends on the forward pass: side stream, joined before the loss.
-    const long R = a->R;
-    const long gst = (long)H * H + H + 1;
-    gemm(E, ss, K, H, H, C, P + off[16], 1, H, ps, P + off[16], H, 1, ps, w.gram, H, 1, gst);
-    hipLaunchKernelGGL(featg_wb_kernel, dim3(H + 1, K), dim3(64), 0, ss, P, ps, (int)off[16], (int)off[17], C, H, w.gram, gst);
-    gemm(E, ss, K, (int)R, H, C, a->gt_feat, C, 1, R * C, P + off[16], H, 1, ps, w.rayin, H + 2, 1, R * (H + 2));
-    hipLaunchKernelGGL(featg_rowstats_kernel, dim3((unsigned)((R + 15) / 16), K), dim3(256), 0, ss, P, ps, (int)off[17], C,
-                       (int)R, H + 2, a->gt_feat, w.rayin);
+    // None of the head's preparation depends on the forward pass: side stream, joined before the loss.
+    feat_prep_enqueue(E, ss, fh, fhb);
     if (multi) (void)hipEventRecord(sd.done, ss);
   }
 
@@ -2303,7 +2695,7 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
   // epilogues, read as panels / masks / weight-gradient operands and by the head kernels (act_ld).  Their buffers keep
   // the fp32 spacing in the workspace; gemm(E, ) recognises them by address.
   const int act16 = half_acts ? E.operands : 0;
-  if (act16 && !panel_ok(E, (int)n, H, H + E1, 1, 1, false, K)) return OBJNERF_EINVAL;      // (cannot happen: same conditions)
+  if (act16 && !panel_ok(E, (int)n, H, H + OBJ_E1, 1, 1, false, K)) return OBJNERF_EINVAL;      // (cannot happen: same conditions)
   if (act16) {
     E.act16_lo = (const char*)w.h1; E.act16_hi = (const char*)(w.hc + w.act_floats);
     E.grad16_lo = (const char*)w.dA; E.grad16_hi = (const char*)(w.dE + w.act_floats);
@@ -2313,57 +2705,12 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
     f.n = n; f.feat = feat ? 1 : 0; f.params = P; f.ps = ps; f.emb = w.emb;
     f.h1 = w.h1; f.h2 = w.h2; f.h3 = w.h3; f.h4 = w.h4; f.hc = w.hc; f.hf = feat ? w.hf : nullptr;
     f.alpha = w.alpha; f.color = w.color;
-    f.o_in_w = (int)off[0]; f.o_in_b = (int)off[1]; f.o_m1_w = (int)off[2]; f.o_m1_b = (int)off[3];
-    f.o_cat_w = (int)off[4]; f.o_cat_b = (int)off[5]; f.o_m2_w = (int)off[6]; f.o_m2_b = (int)off[7];
-    f.o_a_w = (int)off[8]; f.o_a_b = (int)off[9]; f.o_cl_w = (int)off[10]; f.o_cl_b = (int)off[11];
-    f.o_oc_w = (int)off[12]; f.o_oc_b = (int)off[13]; f.o_fl_w = (int)off[14]; f.o_fl_b = (int)off[15];
-    switch (small_rt) {
-      case 1: launch_fwd_small<1>(st, f, K, small_bf); break;
-      case 2: launch_fwd_small<2>(st, f, K, small_bf); break;
-      case 3: launch_fwd_small<3>(st, f, K, small_bf); break;
-      case 4: launch_fwd_small<4>(st, f, K, small_bf); break;
-      default: launch_fwd_small<5>(st, f, K, small_bf); break;
-    }
+    set_forward_offsets(f, off);
+    launch_small_rt(st, f, K, small_bf, small_rt);
   } else {
-  // h1 = relu(x1 W_in^T + b)
-  gemm(E, st, K, n, H, E1, w.emb, EM, 1, n * EM, P + off[0], 1, E1, ps, w.h1, H, 1, nH, false, P + off[1], ps, true);
-  gemm(E, st, K, n, H, H, w.h1, H, 1, nH, P + off[2], 1, H, ps, w.h2, H, 1, nH, false, P + off[3], ps, true);
-  // h3 = relu([h2 | x1] W_cat^T + b)
-  // ([h2 | x1] as ONE contraction when the resident-panel kernel takes it: no round trip of the partial result)
-  const bool fuse2 = panel_ok(E, (int)n, H, H + E1, 1, 1, false, K) && H == 256;
-  if (fuse2) {
-    E.a2 = A2Src{w.emb, EM, n * EM, H};
-    gemm(E, st, K, n, H, H + E1, w.h2, H, 1, nH, P + off[4], 1, H + E1, ps, w.h3, H, 1, nH, false, P + off[5], ps, true);
-  } else {
-  gemm(E, st, K, n, H, H, w.h2, H, 1, nH, P + off[4], 1, H + E1, ps, w.h3, H, 1, nH);
-  gemm(E, st, K, n, H, E1, w.emb, EM, 1, n * EM, P + off[4] + H, 1, H + E1, ps, w.h3, H, 1, nH, true, P + off[5], ps, true);
+    forward_chain(E, st, c, w.alpha, w.color, w.hf, act16);
   }
-  gemm(E, st, K, n, H, H, w.h3, H, 1, nH, P + off[6], 1, H, ps, w.h4, H, 1, nH, false, P + off[7], ps, true);
-  // hc = relu([h4 | x2] W_cl^T + b)
-  if (fuse2) {
-    E.a2 = A2Src{w.emb + E1, EM, n * EM, H};
-    gemm(E, st, K, n, H, H + E2, w.h4, H, 1, nH, P + off[10], 1, H + E2, ps, w.hc, H, 1, nH, false, P + off[11], ps, true);
-  } else {
-  gemm(E, st, K, n, H, H, w.h4, H, 1, nH, P + off[10], 1, H + E2, ps, w.hc, H, 1, nH);
-  gemm(E, st, K, n, H, E2, w.emb + E1, EM, 1, n * EM, P + off[10] + H, 1, H + E2, ps, w.hc, H, 1, nH, true, P + off[11], ps,
-       true);
-  }
-  hipLaunchKernelGGL(heads_fwd_kernel, eg, dim3(256), head_lds, st, H, n, w.h4, w.hc, P, ps, (int)off[8], (int)off[9],
-                     (int)off[12], (int)off[13], w.alpha, w.color, act16);
-  if (feat) {
-    gemm(E, st, K, n, H, H, w.h4, H, 1, nH, P + off[14], 1, H + E2, ps, w.hf, H, 1, nH);
-    gemm(E, st, K, n, H, E2, w.emb + E1, EM, 1, n * EM, P + off[14] + H, 1, H + E2, ps, w.hf, H, 1, nH, true, P + off[15],
-         ps, true);
-  }
-  }
-  if (a->relu_masks) {       // test hook: the ReLU branch bits of this iteration (objnerf_train_args.relu_masks)
-    const float* acts[6] = {w.h1, w.h2, w.h3, w.h4, w.hc, feat ? w.hf : nullptr};
-    const long nb = (long)K * n * (H / 8);
-    for (int l = 0; l < 6; ++l)
-      if (acts[l])
-        hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, nb, H, acts[l],
-                           a->relu_masks, l, l < 5 ? act16 : 0);
-  }
+  if (a->relu_masks) emit_relu_masks(st, c, a->relu_masks, act16, 0);
   if (feat && multi) (void)hipStreamWaitEvent(st, sd.done, 0);      // the feature preparation (side stream) is needed from here
   // ---- loss + d(alpha, color, clip)      (loss.py:5-103)
   objnerf_loss_args la;
@@ -2388,26 +2735,18 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
   // scaled by ~8 R (a power of two: exact) before rounding and the product scaled back (Gemm::a_scale).
   const float grad_scale = exp2f(floorf(log2f((float)a->R)) + 3.0f);
   E.a_scale = grad_scale;
-  int rr = 0;
-  auto side = [&]() -> hipStream_t {        // stream of the next independent weight-gradient GEMM
-    hipStream_t r = sd.all[rr];
-    rr = (rr + 1) % n_side;
-    return r;
-  };
-  float* d_hc = w.dA;      // [n][H]
-  float* d_h4 = w.dB_;
-  // (layer-wise chain without the feature branch: the colour layer's input-gradient GEMM adds the alpha head's rank-1
-  // term wa x dhead[:, 0] in its epilogue, so d_h4 is written once instead of written, read and written)
-  const bool fold_a = !feat && !small_rt;
+  const bool fold_a = !feat && !small_rt;      // (layer_dgrad's fold_dhead form of the colour layer)
   hipLaunchKernelGGL(heads_bwd_kernel, eg, dim3(256), head_lds, st, H, n, w.hc, w.color, w.d_alpha, w.d_color, P, ps,
-                     (int)off[8], (int)off[12], w.dhead, d_hc, fold_a ? nullptr : d_h4, act16,
+                     (int)off[OBJNERF_T_ALPHA_W], (int)off[OBJNERF_T_OC_W], w.dhead, c.d_hc, fold_a ? nullptr : c.d_h4, act16,
                      act16 == 2 ? grad_scale : 1.0f);
   // head weight grads: d wa = dhead[:,0]^T h4, d Woc = dhead[:,1:4]^T hc; biases = column sums of dhead
   // (every bias gradient rides on its layer's weight-gradient GEMM: row sums of the d-output operand tile)
   fork();
   if (H > 256) {
-    wgrad(E, ss, K, 1, H, n, w.dhead, 1, 4, n * 4, w.h4, H, 1, nH, G + off[8], H, ps, G + off[9]);
-    wgrad(E, ss, K, 3, H, n, w.dhead + 1, 1, 4, n * 4, w.hc, H, 1, nH, G + off[12], H, ps, G + off[13]);
+    wgrad(E, ss, K, 1, H, n, w.dhead, 1, 4, n * 4, w.h4, H, 1, n * H, G + off[OBJNERF_T_ALPHA_W], H, ps,
+          G + off[OBJNERF_T_ALPHA_B]);
+    wgrad(E, ss, K, 3, H, n, w.dhead + 1, 1, 4, n * 4, w.hc, H, 1, n * H, G + off[OBJNERF_T_OC_W], H, ps,
+          G + off[OBJNERF_T_OC_B]);
   } else {
     // 64 samples per block (32 iterations of a 2-row pass at H = 128): the loop is a chain of load latencies, so the
     // reduction wants many short blocks (512 samples per block: 183 us for the background batch; now ~25 us)
@@ -2419,354 +2758,69 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
     float* rA = E.parts_alloc((size_t)K * hb), *rW = E.parts_alloc((size_t)K * hb * 3);
     if (!(pA && pW && rA && rW)) pA = pW = rA = rW = nullptr;        // no scratch: float atomics
     hipLaunchKernelGGL(head_wgrad_kernel, dim3((unsigned)hb, (unsigned)K), dim3(256), 0, ss, H, n, w.dhead, w.h4, w.hc, G, ps,
-                       (int)off[8], (int)off[9], (int)off[12], (int)off[13], pA, pW, rA, rW, act16);
+                       (int)off[OBJNERF_T_ALPHA_W], (int)off[OBJNERF_T_ALPHA_B], (int)off[OBJNERF_T_OC_W],
+                       (int)off[OBJNERF_T_OC_B], pA, pW, rA, rW, act16);
     if (pA) {
-      RedGroup rg;
-      rg.count = 2; rg.beg[0] = 0;
-      RedItem& a0 = rg.it[0];
-      a0.part = pA; a0.rs_part = rA; a0.C = G + off[8]; a0.rowsum = G + off[9];
-      a0.M = 1; a0.N = H; a0.sk = hb; a0.batch = K; a0.scm = H; a0.bsc = ps; a0.bsrs = ps;
-      RedItem& a1 = rg.it[1];
-      a1.part = pW; a1.rs_part = rW; a1.C = G + off[12]; a1.rowsum = G + off[13];
-      a1.M = 3; a1.N = H; a1.sk = hb; a1.batch = K; a1.scm = H; a1.bsc = ps; a1.bsrs = ps;
-      rg.beg[1] = red_blocks(a0); rg.beg[2] = rg.beg[1] + red_blocks(a1);
-      if (small_rt) { red_append(step_red, a0); red_append(step_red, a1); }
-      else hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)rg.beg[2]), dim3(256), 0, ss, rg);
+      const RedItem heads[2] = {head_red_item(c, OBJNERF_T_ALPHA_W, OBJNERF_T_ALPHA_B, 1, pA, rA, hb),
+                                head_red_item(c, OBJNERF_T_OC_W, OBJNERF_T_OC_B, 3, pW, rW, hb)};
+      red_emit(ss, small_rt ? &step_red : nullptr, heads, 2);
     }
   }
-  // d_emb needs no zero fill: the first dgrad into each column block overwrites (x2: feature layer if
-  // present, else colour layer; x1: cat layer), later ones accumulate; columns 0..2 (d t) are never read.
   if (feat) {
-    // d_hf (pre-activation gradient of the feature layer) came out of the loss kernel; the 512-d head's gradient is
-    // d W_of = gt_feat^T [a fh] + W_of M2 + b_of m1^T, d b_of = gt_feat^T [a O] + W_of m1 + b_of s2 with the moments
-    // [M2 m1; . s2] = [c fh | c O]^T [fh | O]: two split-K GEMMs over the rays + a small finish (side stream)
-    float* d_hf = w.d_hf;
-    const long R = a->R;
+    // d_hf (pre-activation gradient of the feature layer) came out of the loss kernel; the 512-d head's gradient from
+    // the rays' moments (side stream)
     const int XC = H + 1;
-    const long nr = (long)K * R;
+    const long nr = (long)K * a->R;
     fork();
     hipLaunchKernelGGL(featg_scale_kernel, dim3((unsigned)((nr * XC + 255) / 256)), dim3(256), 0, ss, nr, H, w.rayfeat, w.X1,
                        w.X2);
     (void)hipMemsetAsync(w.Tm, 0, ((size_t)K * C * XC + (size_t)K * XC * XC) * 4, ss);
     E.a_scale = 1.0f;                       // (targets and moments of the feature head: not gradients)
-    wgrad(E, ss, K, C, XC, R, a->gt_feat, 1, C, R * C, w.X1, XC, 1, R * XC, w.Tm, XC, (long)C * XC);
-    wgrad(E, ss, K, XC, XC, R, w.X2, 1, XC, R * XC, w.rayfeat, H + 3, 1, R * (H + 3), w.mom, XC, (long)XC * XC);
+    feat_moments_enqueue(E, ss, fh, fhb);
     E.a_scale = grad_scale;
-    hipLaunchKernelGGL(featg_finish_kernel, dim3((unsigned)(((long)C * XC + 255) / 256), K), dim3(256), 0, ss, P, ps,
-                       (int)off[16], (int)off[17], C, H, w.Tm, w.mom, G);
-    // feature layer: grads + contributions to d_h4 / d_x2
-    if (!small_rt) {
-      wgrad(E, ss, K, H, H, n, d_hf, 1, H, nH, w.h4, H, 1, nH, G + off[14], H + E2, ps, G + off[15]);
-      wgrad(E, ss, K, H, E2, n, d_hf, 1, H, nH, w.emb + E1, EM, 1, n * EM, G + off[14] + H, H + E2, ps);
-      gemm(E, st, K, n, H, H, d_hf, H, 1, nH, P + off[14], H + E2, 1, ps, d_h4, H, 1, nH, true);
-      gemm(E, st, K, n, E2, H, d_hf, H, 1, nH, P + off[14] + H, H + E2, 1, ps, w.d_emb + E1, EM, 1, n * EM, false);
-    }
+    feat_finish_enqueue(ss, fh, fhb, G);
   }
-  float* d_h3 = w.dC;
-  float* d_h2 = w.dD;
-  float* d_h1 = w.dE;
   if (small_rt) {
     // small batch: the whole input-gradient chain in one launch, then the (independent) weight-gradient GEMMs
-    // side by side on three streams
+    // as one grouped launch on the side stream
     BwdSmall b;
     b.n = n; b.feat = feat ? 1 : 0; b.params = P; b.ps = ps;
-    b.h1 = w.h1; b.h2 = w.h2; b.h3 = w.h3; b.h4 = w.h4; b.d_hc = d_hc; b.d_hf = feat ? w.d_hf : nullptr;
-    b.d_h4 = d_h4; b.d_h3 = d_h3; b.d_h2 = d_h2; b.d_h1 = d_h1; b.d_emb = w.d_emb;
-    b.o_in_w = (int)off[0]; b.o_m1_w = (int)off[2]; b.o_cat_w = (int)off[4]; b.o_m2_w = (int)off[6];
-    b.o_cl_w = (int)off[10]; b.o_fl_w = (int)off[14];
-    switch (small_rt) {
-      case 1: launch_bwd_small<1>(st, b, K, small_bf); break;
-      case 2: launch_bwd_small<2>(st, b, K, small_bf); break;
-      case 3: launch_bwd_small<3>(st, b, K, small_bf); break;
-      case 4: launch_bwd_small<4>(st, b, K, small_bf); break;
-      default: launch_bwd_small<5>(st, b, K, small_bf); break;
-    }
+    b.h1 = w.h1; b.h2 = w.h2; b.h3 = w.h3; b.h4 = w.h4; b.d_hc = c.d_hc; b.d_hf = feat ? w.d_hf : nullptr;
+    b.d_h4 = c.d_h4; b.d_h3 = c.d_h3; b.d_h2 = c.d_h2; b.d_h1 = c.d_h1; b.d_emb = w.d_emb;
+    set_weight_offsets(b, off);
+    launch_small_rt(st, b, K, small_bf, small_rt);
     fork();
     GemmGroup group;
     group.count = 0;
     E.group = &group;
     E.group16 = small_bf;             // bf16 mode: the weight gradients take bf16 operands like every other GEMM of the mode
     E.red_group = &step_red;
-    if (feat) {
-      wgrad(E, side(), K, H, H, n, w.d_hf, 1, H, nH, w.h4, H, 1, nH, G + off[14], H + E2, ps, G + off[15]);
-      wgrad(E, side(), K, H, E2, n, w.d_hf, 1, H, nH, w.emb + E1, EM, 1, n * EM, G + off[14] + H, H + E2, ps);
-    }
-    wgrad(E, side(), K, H, H, n, d_hc, 1, H, nH, w.h4, H, 1, nH, G + off[10], H + E2, ps, G + off[11]);
-    wgrad(E, side(), K, H, E2, n, d_hc, 1, H, nH, w.emb + E1, EM, 1, n * EM, G + off[10] + H, H + E2, ps);
-    wgrad(E, side(), K, H, H, n, d_h4, 1, H, nH, w.h3, H, 1, nH, G + off[6], H, ps, G + off[7]);
-    wgrad(E, side(), K, H, H, n, d_h3, 1, H, nH, w.h2, H, 1, nH, G + off[4], H + E1, ps, G + off[5]);
-    wgrad(E, side(), K, H, E1, n, d_h3, 1, H, nH, w.emb, EM, 1, n * EM, G + off[4] + H, H + E1, ps);
-    wgrad(E, side(), K, H, H, n, d_h2, 1, H, nH, w.h1, H, 1, nH, G + off[2], H, ps, G + off[3]);
-    wgrad(E, side(), K, H, E1, n, d_h1, 1, H, nH, w.emb, EM, 1, n * EM, G + off[0], E1, ps, G + off[1]);
+    wgrad_chain(E, ss, c, feat, true);
     flush_group(E, ss, group);
   } else {
-  // colour layer
-  fork();
-  wgrad(E, ss, K, H, H, n, d_hc, 1, H, nH, w.h4, H, 1, nH, G + off[10], H + E2, ps, G + off[11]);
-  wgrad(E, ss, K, H, E2, n, d_hc, 1, H, nH, w.emb + E1, EM, 1, n * EM, G + off[10] + H, H + E2, ps);
-  if (fold_a) {
-    E.biasrow = w.dhead; E.bsbr = n * 4; E.sbr = 4;
-    gemm(E, st, K, n, H, H, d_hc, H, 1, nH, P + off[10], H + E2, 1, ps, d_h4, H, 1, nH, false, P + off[8], ps, false, w.h4, H, 1,
-         nH);
-    E.biasrow = nullptr; E.bsbr = 0; E.sbr = 1;
-  } else {
-    gemm(E, st, K, n, H, H, d_hc, H, 1, nH, P + off[10], H + E2, 1, ps, d_h4, H, 1, nH, true, nullptr, 0, false, w.h4, H, 1, nH);
-  }
-  gemm(E, st, K, n, E2, H, d_hc, H, 1, nH, P + off[10] + H, H + E2, 1, ps, w.d_emb + E1, EM, 1, n * EM, feat);
-  // mid2:  d_h4 (masked above) -> grads, d_h3
-  fork();
-  wgrad(E, ss, K, H, H, n, d_h4, 1, H, nH, w.h3, H, 1, nH, G + off[6], H, ps, G + off[7]);
-  gemm(E, st, K, n, H, H, d_h4, H, 1, nH, P + off[6], H, 1, ps, d_h3, H, 1, nH, false, nullptr, 0, false, w.h3, H, 1, nH);
-  // cat layer
-  fork();
-  wgrad(E, ss, K, H, H, n, d_h3, 1, H, nH, w.h2, H, 1, nH, G + off[4], H + E1, ps, G + off[5]);
-  wgrad(E, ss, K, H, E1, n, d_h3, 1, H, nH, w.emb, EM, 1, n * EM, G + off[4] + H, H + E1, ps);
-  gemm(E, st, K, n, H, H, d_h3, H, 1, nH, P + off[4], H + E1, 1, ps, d_h2, H, 1, nH, false, nullptr, 0, false, w.h2, H, 1, nH);
-  gemm(E, st, K, n, E1, H, d_h3, H, 1, nH, P + off[4] + H, H + E1, 1, ps, w.d_emb, EM, 1, n * EM, false);
-  // mid1
-  fork();
-  wgrad(E, ss, K, H, H, n, d_h2, 1, H, nH, w.h1, H, 1, nH, G + off[2], H, ps, G + off[3]);
-  gemm(E, st, K, n, H, H, d_h2, H, 1, nH, P + off[2], H, 1, ps, d_h1, H, 1, nH, false, nullptr, 0, false, w.h1, H, 1, nH);
-  // in layer
-  fork();
-  wgrad(E, ss, K, H, E1, n, d_h1, 1, H, nH, w.emb, EM, 1, n * EM, G + off[0], E1, ps, G + off[1]);
-  gemm(E, st, K, n, E1, H, d_h1, H, 1, nH, P + off[0], E1, 1, ps, w.d_emb, EM, 1, n * EM, true);
+    backward_chain(E, st, ss, c, feat, fold_a ? w.dhead : nullptr, fork);
   }
   // embedding directions: block partials + ordered reduction straight into the gradient arena (float atomics into dBpe
   // and a copy when the scratch is exhausted)
-  int pg = (int)((n + 47) / 48);           // 12 samples per block and pass: at least 4 passes per block
-  if (pg > 1024) pg = 1024;
-  if (pg < 1) pg = 1;
+  const int pg = pe_bwd_blocks(n);
   float* pe_part = E.parts_alloc((size_t)K * pg * 63);
   if (!pe_part) (void)hipMemsetAsync(w.dBpe, 0, (size_t)K * 64 * 4, st);
-  hipLaunchKernelGGL(pe_bwd_kernel, dim3(pg, K), dim3(256), 0, st, n, P, ps, (int)off[18], a->scale, a->pts, w.d_emb,
-                     w.dBpe, pe_part);
+  hipLaunchKernelGGL(pe_bwd_kernel, dim3(pg, K), dim3(256), 0, st, n, P, ps, (int)off[OBJNERF_T_PE_B], a->scale, a->pts,
+                     w.d_emb, w.dBpe, pe_part);
   if (pe_part) {
-    RedGroup rg;
-    rg.count = 1; rg.beg[0] = 0;
-    RedItem& r = rg.it[0];
-    r.part = pe_part; r.rs_part = nullptr; r.C = G + off[18]; r.rowsum = nullptr;
-    r.M = 1; r.N = 63; r.sk = pg; r.batch = K; r.scm = 63; r.bsc = ps; r.bsrs = 0;
-    rg.beg[1] = red_blocks(r);
-    if (small_rt) red_append(step_red, r);
-    else hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)rg.beg[1]), dim3(256), 0, st, rg);
+    const RedItem r = pe_red_item(c, pe_part, pg);
+    red_emit(st, small_rt ? &step_red : nullptr, &r, 1);
   } else {
     hipLaunchKernelGGL(copy_cols_kernel, dim3((unsigned)((K * 63 + 255) / 256)), dim3(256), 0, st, (long)K, 63, w.dBpe, 63L,
-                       G + off[18], ps);
+                       G + off[OBJNERF_T_PE_B], ps);
   }
-  for (int i = 0; multi && i < n_side; ++i) {   // join: the caller's stream continues after the weight gradients
-    (void)hipEventRecord(sd.done_all[i], sd.all[i]);
-    (void)hipStreamWaitEvent(st, sd.done_all[i], 0);
+  if (multi) {   // join: the caller's stream continues after the weight gradients
+    (void)hipEventRecord(sd.done_all[0], ss);
+    (void)hipStreamWaitEvent(st, sd.done_all[0], 0);
   }
   launch_reductions(st, step_red);
   if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
   if (E.error) return OBJNERF_EINVAL;
-  return OBJNERF_OK;
-}
-
-// The one-launch small-batch iteration: train_small_kernel -> the seven weight-gradient GEMMs as ONE grouped launch ->
-// ONE reduction launch (weight-gradient slices, head / d B / loss partials, status, optionally AdamW).  Everything on
-// the caller's stream: three dependent launches need no helper stream and no events.
-static int train_step_small(const objnerf_net* net, const objnerf_train_args* a, hipStream_t st, GemmEnv& E, const WS& w,
-                            const int64_t* off, bool bf, int* done) {
-  const int H = net->hidden, K = a->K, S = a->S, C = net->feat_dim;
-  const long n = (long)a->R * S, nH = n * H, ps = a->p_stride;
-  const bool feat = a->gt_feat != nullptr;
-  const int rpw = sf_rays_per_wg(S, feat);
-  const int nwg = (int)(((long)a->R + rpw - 1) / rpw);
-  const int E1 = OBJ_E1, E2 = OBJ_E2, EM = OBJ_EMB;
-  const float* P = a->params;
-  float* G = a->grads;
-  const bool self_counts = (a->mode & OBJNERF_TRAIN_SELF_COUNTS) != 0;
-  if (self_counts && K > 1) {        // several objects: the cross-object flags need every object's labels (one small launch)
-    const int rc0 = objnerf_label_counts(K, a->R, a->labels, const_cast<int32_t*>(a->counts), const_cast<int32_t*>(a->flags),
-                                         (void*)st);
-    if (rc0) return rc0;
-  }
-  const long R = a->R;
-  const int XC = H + 1;
-  float* head_snap = nullptr;          // [K][C (H + 1)]: [W_of | b_of] before the step (FeatPrepTask), for the fused finish + AdamW
-  if (feat) {
-    // the 512-d head is NOT applied per sample: per object G = W_of^T W_of (+ wb, bb), per ray
-    // u = W_of^T g, beta, |g| -- none of it depends on the forward pass; four small launches ahead of the fused one
-    const long gst = (long)H * H + H + 1;
-    E.operands = 0;
-    // Round 6: ONE launch for the four (the two GEMMs as a group, wb / bb, the rays' beta and |g| and -- with an optimiser
-    // attached -- the copy of [W_of | b_of] the head's finish reads, as extra workgroups of the same launch: FeatPrepTask)
-    head_snap = a->optim ? E.parts_alloc((size_t)K * C * XC) : nullptr;
-    GemmGroup g0;
-    g0.count = 0;
-    E.group = &g0; E.group16 = false;
-    gemm(E, st, K, H, H, C, P + off[16], 1, H, ps, P + off[16], H, 1, ps, w.gram, H, 1, gst);
-    gemm(E, st, K, (int)R, H, C, a->gt_feat, C, 1, R * C, P + off[16], H, 1, ps, w.rayin, H + 2, 1, R * (H + 2));
-    if (g0.count == 2 && !E.error) {
-      FeatPrepTask& t = g0.task;
-      t.params = P; t.ps = ps; t.off_w = (int)off[16]; t.off_b = (int)off[17]; t.C = C; t.Hh = H; t.R = (int)R; t.rin_ld = H + 2;
-      t.K = K; t.gt_feat = a->gt_feat; t.rayin = w.rayin; t.gram = w.gram; t.gstride = gst; t.snap = head_snap;
-      t.nb_wb = (H + 1 + 7) / 8; t.nb_rs = (int)((R + 31) / 32);
-      t.nb_snap = head_snap ? (int)(((long)C * XC + 2047) / 2048) : 0;
-      t.blocks = K * (t.nb_wb + t.nb_rs + t.nb_snap);
-      flush_group(E, st, g0);
-    } else {                          // (cannot happen for these shapes; the separate launches remain the fallback)
-      if (E.error) return OBJNERF_EINVAL;
-      flush_group(E, st, g0);
-      head_snap = nullptr;
-      hipLaunchKernelGGL(featg_wb_kernel, dim3(H + 1, K), dim3(64), 0, st, P, ps, (int)off[16], (int)off[17], C, H, w.gram, gst);
-      hipLaunchKernelGGL(featg_rowstats_kernel, dim3((unsigned)((R + 15) / 16), K), dim3(256), 0, st, P, ps, (int)off[17], C,
-                         (int)R, H + 2, a->gt_feat, w.rayin);
-    }
-    E.group = nullptr;
-  }
-  SmallFused f;
-  f.K = K; f.R = a->R; f.S = S; f.rpw = rpw;
-  f.fs = a->feat_scaling; f.o_fl_w = (int)off[14]; f.o_fl_b = (int)off[15];
-  f.rayin = w.rayin; f.gram = w.gram; f.hf = w.hf; f.d_hf = w.d_hf; f.rayfeat = w.rayfeat; f.X1 = w.X1; f.X2 = w.X2;
-  f.params = P; f.ps = ps; f.scale = a->scale;
-  f.pts = a->pts; f.origins = a->origins; f.dirs = a->dirs; f.z = a->z; f.centre = a->obj_center;
-  f.gt_depth = a->gt_depth; f.gt_rgb = a->gt_rgb; f.labels = a->labels;
-  f.counts = const_cast<int*>(a->counts); f.flags = const_cast<int*>(a->flags); f.self_counts = (self_counts && K == 1) ? 1 : 0;
-  f.cs = a->color_scaling; f.os = a->opacity_scaling;
-  f.emb = w.emb; f.h1 = w.h1; f.h2 = w.h2; f.h3 = w.h3; f.h4 = w.h4; f.hc = w.hc;
-  f.d_hc = w.dA; f.d_h4 = w.dB_; f.d_h3 = w.dC; f.d_h2 = w.dD; f.d_h1 = w.dE;
-  // per-workgroup partials live in workspace regions this path does not use otherwise (d_emb: K n 129 floats, dhead:
-  // K n 4, loss_part: K R 4): objnerf_train_step's applicability test checked that they fit
-  float* hp = w.d_emb;
-  f.partA = hp; hp += (size_t)K * nwg * H;
-  f.partW = hp; hp += (size_t)K * nwg * 3 * H;
-  f.rsA = hp; hp += (size_t)K * nwg;
-  f.rsW = hp;
-  f.pe_part = w.dhead;
-  f.loss_part = w.loss_part;
-  f.o_in_w = (int)off[0]; f.o_in_b = (int)off[1]; f.o_m1_w = (int)off[2]; f.o_m1_b = (int)off[3];
-  f.o_cat_w = (int)off[4]; f.o_cat_b = (int)off[5]; f.o_m2_w = (int)off[6]; f.o_m2_b = (int)off[7];
-  f.o_a_w = (int)off[8]; f.o_a_b = (int)off[9]; f.o_cl_w = (int)off[10]; f.o_cl_b = (int)off[11];
-  f.o_oc_w = (int)off[12]; f.o_oc_b = (int)off[13]; f.o_B = (int)off[18];
-  if (feat) {
-    if (rpw * S <= 64) launch_train_small<4, true>(st, f, nwg, bf);
-    else launch_train_small<5, true>(st, f, nwg, bf);
-  } else {
-    if (rpw * S <= 64) launch_train_small<4, false>(st, f, nwg, bf);
-    else launch_train_small<5, false>(st, f, nwg, bf);
-  }
-  if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
-  if (a->relu_masks) {       // test hook: the ReLU branch bits of this iteration, from the stored activations
-    const float* acts[6] = {w.h1, w.h2, w.h3, w.h4, w.hc, feat ? w.hf : nullptr};
-    const long nb = (long)K * n * (H / 8);
-    for (int l = 0; l < 6; ++l)
-      if (acts[l])
-        hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, nb, H, acts[l], a->relu_masks, l,
-                           bf ? 1 : 0);
-  }
-  if (bf) {
-    // bf16 mode: the kernel above stored h1 .. hc (hf, d_hf) and d_hc .. d_h1 as bf16 (objnerf_small_body.h, `hst`); gemm(E, )
-    // recognises 16-bit operands by address and the grouped launch passes them through unconverted
-    E.act16_lo = (const char*)w.h1;
-    E.act16_hi = feat ? (const char*)(w.d_hf + (size_t)K * n * H) : (const char*)(w.hc + w.act_floats);
-    E.grad16_lo = (const char*)w.dA; E.grad16_hi = (const char*)(w.dE + w.act_floats);
-  }
-  // ---- the step's reductions, collected: head partials, d B partials, the weight gradients' split-K slices
-  RedGroup red;
-  red.count = 0;
-  {
-    RedItem a0;
-    a0.part = f.partA; a0.rs_part = f.rsA; a0.C = G + off[8]; a0.rowsum = G + off[9];
-    a0.M = 1; a0.N = H; a0.sk = nwg; a0.batch = K; a0.scm = H; a0.bsc = ps; a0.bsrs = ps;
-    RedItem a1;
-    a1.part = f.partW; a1.rs_part = f.rsW; a1.C = G + off[12]; a1.rowsum = G + off[13];
-    a1.M = 3; a1.N = H; a1.sk = nwg; a1.batch = K; a1.scm = H; a1.bsc = ps; a1.bsrs = ps;
-    RedItem r;
-    r.part = f.pe_part; r.rs_part = nullptr; r.C = G + off[18]; r.rowsum = nullptr;
-    r.M = 1; r.N = 63; r.sk = nwg; r.batch = K; r.scm = 63; r.bsc = ps; r.bsrs = 0;
-    red_append(red, a0); red_append(red, a1); red_append(red, r);
-  }
-  E.operands = 0;                   // (the grouped launch picks its operand type through group16)
-  E.a_scale = 1.0f;
-  GemmGroup group;
-  group.count = 0;
-  E.group = &group;
-  E.group16 = bf;
-  E.red_group = &red;
-  E.need_parts = true;              // no zero-filled gradient arena here: the deterministic slab form or an error
-  // Split-K slices of the grouped launch: its seven GEMMs are ONE 128 x 128 tile each, so `slices` is also the number of
-  // workgroups per GEMM.  ~2 rounds of the chip (7 x 37 = 259 workgroups at least), at most ~1024 samples per slice
-  // beyond that: every slice writes its partial tile to HBM and the reduction reads it back -- 128 slices at the
-  // benchmark's 76 800 background samples were 48 MB each way for 0.4 MB of gradient (reduction 131 us).
-  {
-    long want = (n + 1023) / 1024;
-    if (want < 36) want = 36;
-    // whole rounds of the chip: 7 GEMMs x slices workgroups on num_cu compute units (75 slices = 525 workgroups left a
-    // third round for 13 of them: 260 us against 227)
-    const int cu = 256, ng = feat ? 9 : 7;
-    long rounds = (want * ng + cu / 2) / cu;
-    if (rounds < 1) rounds = 1;
-    E.max_slices = (int)(rounds * cu / ng);
-  }
-  wgrad(E, st, K, H, H, n, f.d_hc, 1, H, nH, w.h4, H, 1, nH, G + off[10], H + E2, ps, G + off[11]);
-  wgrad(E, st, K, H, E2, n, f.d_hc, 1, H, nH, w.emb + E1, EM, 1, n * EM, G + off[10] + H, H + E2, ps);
-  wgrad(E, st, K, H, H, n, f.d_h4, 1, H, nH, w.h3, H, 1, nH, G + off[6], H, ps, G + off[7]);
-  wgrad(E, st, K, H, H, n, f.d_h3, 1, H, nH, w.h2, H, 1, nH, G + off[4], H + E1, ps, G + off[5]);
-  wgrad(E, st, K, H, E1, n, f.d_h3, 1, H, nH, w.emb, EM, 1, n * EM, G + off[4] + H, H + E1, ps);
-  wgrad(E, st, K, H, H, n, f.d_h2, 1, H, nH, w.h1, H, 1, nH, G + off[2], H, ps, G + off[3]);
-  wgrad(E, st, K, H, E1, n, f.d_h1, 1, H, nH, w.emb, EM, 1, n * EM, G + off[0], E1, ps, G + off[1]);
-  if (feat) {
-    // feature layer
-    wgrad(E, st, K, H, H, n, f.d_hf, 1, H, nH, w.h4, H, 1, nH, G + off[14], H + E2, ps, G + off[15]);
-    wgrad(E, st, K, H, E2, n, f.d_hf, 1, H, nH, w.emb + E1, EM, 1, n * EM, G + off[14] + H, H + E2, ps);
-  }
-  if (E.parts_failed || E.error) return OBJNERF_EINVAL;
-  flush_group(E, st, group);
-  if (feat) {
-    // the 512-d head's moments over the RAYS: T = gt_feat^T [a fh | a O], M = [c fh | c O]^T [fh | O] (featg_finish_kernel
-    // turns them into d W_of, d b_of after the reduction).  Two launches of their own: inside the grouped launch their
-    // 512-row output made it 5x slower (1.82 against 0.35 ms at the benchmark's background batch -- every GEMM of the
-    // group is then launched over four row tiles)
-    // (round 6: the two as ONE grouped launch of their own)
-    GemmGroup g2;
-    g2.count = 0;
-    E.group = &g2; E.group16 = false; E.operands = 0; E.red_group = &red; E.max_slices = 0;
-    wgrad(E, st, K, C, XC, R, a->gt_feat, 1, C, R * C, w.X1, XC, 1, R * XC, w.Tm, XC, (long)C * XC);
-    wgrad(E, st, K, XC, XC, R, w.X2, 1, XC, R * XC, w.rayfeat, H + 3, 1, R * (H + 3), w.mom, XC, (long)XC * XC);
-    if (E.parts_failed || E.error) return OBJNERF_EINVAL;
-    RedGroup* keep = E.red_group;
-    flush_group(E, st, g2);              // (launches whatever was collected; GEMMs the group does not take were launched at once)
-    E.red_group = keep;
-  }
-  red.tail.loss_part = f.loss_part; red.tail.loss_blocks = nwg; red.tail.K = K; red.tail.loss_terms = a->loss_terms;
-  red.tail.status = a->status;
-  if (a->optim) {
-    const objnerf_adamw_args* o = a->optim;
-    RedTail& t = red.tail;
-    t.params = const_cast<float*>(a->params); t.grads = G; t.m = o->exp_avg; t.v = o->exp_avg_sq; t.flags = a->flags;
-    t.steps = o->group_steps; t.bank = o->bank; t.p_stride = ps; t.arena_floats = (long)K * ps;
-    t.lo1 = off[10]; t.lo2 = off[14]; t.hi2 = off[18];
-    t.lr = (double)o->lr; t.b1 = (double)o->beta1; t.b2 = (double)o->beta2; t.wd = (double)o->weight_decay; t.eps = o->eps;
-    if (done) *done |= 2;
-  }
-  launch_reductions(st, red);
-  if (feat && a->optim && head_snap) {
-    // the head's gradient AND its AdamW step in one launch, from the copy of [W_of | b_of] (round 6)
-    const objnerf_adamw_args* o = a->optim;
-    FeatFinishOpt fo;
-    fo.params = const_cast<float*>(a->params); fo.m = o->exp_avg; fo.v = o->exp_avg_sq; fo.flags = a->flags;
-    fo.steps = o->group_steps; fo.bank = o->bank;
-    fo.lr = (double)o->lr; fo.b1 = (double)o->beta1; fo.b2 = (double)o->beta2; fo.wd = (double)o->weight_decay; fo.eps = o->eps;
-    hipLaunchKernelGGL(featg_finish_adamw_kernel, dim3((unsigned)(((long)C * XC + 255) / 256), K), dim3(256), 0, st, head_snap, ps,
-                       (int)off[16], (int)off[17], C, H, w.Tm, w.mom, G, fo);
-  } else if (feat) {
-    hipLaunchKernelGGL(featg_finish_kernel, dim3((unsigned)(((long)C * XC + 255) / 256), K), dim3(256), 0, st, P, ps,
-                       (int)off[16], (int)off[17], C, H, w.Tm, w.mom, G);
-    if (a->optim) {               // the head's own entries [of_w, pe_b): their gradient exists only now
-      const objnerf_adamw_args* o = a->optim;
-      // (entries [off[16], off[18]) only: "P" = off[18] with [0, off[16]) skipped -- B's gradient behind them was stepped
-      // by the reduction launch)
-      const int rc = objmisc::adamw_flags_range(K, off[18], ps, const_cast<float*>(a->params), G, o->exp_avg,
-                                                o->exp_avg_sq, nullptr, a->flags, o->group_steps, o->bank, off[10], off[14],
-                                                off[18], 0, off[16], o->lr, o->beta1, o->beta2, o->eps, o->weight_decay,
-                                                (void*)st);
-      if (rc) return rc;
-    }
-  }
-  if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
   return OBJNERF_OK;
 }
 
@@ -2792,35 +2846,20 @@ int eval_points(const objnerf_net* net, int K, long N, const float* params, long
   float* bA = (float*)p;  p += al((size_t)K * N * H * 4);
   float* bB = (float*)p;  p += al((size_t)K * N * H * 4);
   float* bC = (float*)p;
-  const float* P = params;
-  const long ps = p_stride, n = N, nH = N * H;
-  const int E1 = OBJ_E1, E2 = OBJ_E2, EM = OBJ_EMB;
   const float* emb = emb_in;
   if (!emb_in) {
     int rc = objnerf_embed(net, K, N, params, p_stride, scale, pts, emb_ws, stream);
     if (rc) return rc;
     emb = emb_ws;
   }
-  float *h1 = bA, *h2 = bB, *h3 = bA, *h4 = bB, *hc = bA;
-  gemm(E, st, K, n, H, E1, emb, EM, 1, n * EM, P + off[0], 1, E1, ps, h1, H, 1, nH, false, P + off[1], ps, true);
-  gemm(E, st, K, n, H, H, h1, H, 1, nH, P + off[2], 1, H, ps, h2, H, 1, nH, false, P + off[3], ps, true);
-  gemm(E, st, K, n, H, H, h2, H, 1, nH, P + off[4], 1, H + E1, ps, h3, H, 1, nH);
-  gemm(E, st, K, n, H, E1, emb, EM, 1, n * EM, P + off[4] + H, 1, H + E1, ps, h3, H, 1, nH, true, P + off[5], ps, true);
-  gemm(E, st, K, n, H, H, h3, H, 1, nH, P + off[6], 1, H, ps, h4, H, 1, nH, false, P + off[7], ps, true);
-  gemm(E, st, K, n, H, H, h4, H, 1, nH, P + off[10], 1, H + E2, ps, hc, H, 1, nH);
-  gemm(E, st, K, n, H, E2, emb + E1, EM, 1, n * EM, P + off[10] + H, 1, H + E2, ps, hc, H, 1, nH, true, P + off[11], ps,
-       true);
-  dim3 eg((unsigned)((n + 15) / 16), (unsigned)K);
-  hipLaunchKernelGGL(heads_fwd_kernel, eg, dim3(256), (size_t)4 * H * sizeof(float), st, H, n, h4, hc, P, ps,
-                     (int)off[8], (int)off[9], (int)off[12], (int)off[13], out_alpha, out_color, 0);
-  if (out_hfeat || out_clip) {
-    float* hf = out_hfeat ? out_hfeat : bC;
-    gemm(E, st, K, n, H, H, h4, H, 1, nH, P + off[14], 1, H + E2, ps, hf, H, 1, nH);
-    gemm(E, st, K, n, H, E2, emb + E1, EM, 1, n * EM, P + off[14] + H, 1, H + E2, ps, hf, H, 1, nH, true, P + off[15], ps,
-         true);
-    if (out_clip)
-      gemm(E, st, K, n, C, H, hf, H, 1, nH, P + off[16], 1, H, ps, out_clip, C, 1, n * C, false, P + off[17], ps, false);
-  }
+  NetView c = {};
+  c.P = params; c.ps = p_stride; c.off = off; c.K = K; c.n = N; c.H = H; c.emb = emb;
+  c.h1 = bA; c.h2 = bB; c.h3 = bA; c.h4 = bB; c.hc = bA;
+  float* hf = (out_hfeat || out_clip) ? (out_hfeat ? out_hfeat : bC) : nullptr;
+  forward_chain(E, st, c, out_alpha, out_color, hf, 0);
+  if (out_clip)
+    gemm(E, st, K, N, C, H, hf, H, 1, N * H, params + off[OBJNERF_T_OF_W], 1, H, p_stride, out_clip, C, 1, N * C, false,
+         params + off[OBJNERF_T_OF_B], p_stride, false);
   if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
   return OBJNERF_OK;
 }
@@ -2856,58 +2895,28 @@ int mlp_backward(const objnerf_net* net, int K, long N, const float* params, lon
   E.parts = w.parts; E.parts_cap = w.parts_floats; E.parts_off = 0;
   const float* P = params;
   float* G = grads;
-  const int E1 = OBJ_E1, E2 = OBJ_E2, EM = OBJ_EMB;
+  NetView c = net_view(w, P, G, ps, off, K, n, H);
+  c.emb = emb; c.d_emb = d_emb;
   for (int k = 0; k < K; ++k)      // feature-branch entries only when they receive a gradient ("no gradient" = untouched)
-    (void)hipMemsetAsync(G + (long)k * ps, 0, (size_t)(feat ? off[18] : off[14]) * 4, st);
+    (void)hipMemsetAsync(G + (long)k * ps, 0, (size_t)(feat ? off[T_FEAT_END] : off[T_TRAINED_END]) * 4, st);
   // ---- forward (recompute)
-  gemm(E, st, K, n, H, E1, emb, EM, 1, n * EM, P + off[0], 1, E1, ps, w.h1, H, 1, nH, false, P + off[1], ps, true);
-  gemm(E, st, K, n, H, H, w.h1, H, 1, nH, P + off[2], 1, H, ps, w.h2, H, 1, nH, false, P + off[3], ps, true);
-  gemm(E, st, K, n, H, H, w.h2, H, 1, nH, P + off[4], 1, H + E1, ps, w.h3, H, 1, nH);
-  gemm(E, st, K, n, H, E1, emb, EM, 1, n * EM, P + off[4] + H, 1, H + E1, ps, w.h3, H, 1, nH, true, P + off[5], ps, true);
-  gemm(E, st, K, n, H, H, w.h3, H, 1, nH, P + off[6], 1, H, ps, w.h4, H, 1, nH, false, P + off[7], ps, true);
-  gemm(E, st, K, n, H, H, w.h4, H, 1, nH, P + off[10], 1, H + E2, ps, w.hc, H, 1, nH);
-  gemm(E, st, K, n, H, E2, emb + E1, EM, 1, n * EM, P + off[10] + H, 1, H + E2, ps, w.hc, H, 1, nH, true, P + off[11], ps, true);
-  dim3 eg((unsigned)((n + 15) / 16), (unsigned)K);
-  const size_t head_lds = (size_t)4 * H * sizeof(float);
-  hipLaunchKernelGGL(heads_fwd_kernel, eg, dim3(256), head_lds, st, H, n, w.h4, w.hc, P, ps, (int)off[8], (int)off[9],
-                     (int)off[12], (int)off[13], w.alpha, w.color, 0);
-  if (feat) {
-    gemm(E, st, K, n, H, H, w.h4, H, 1, nH, P + off[14], 1, H + E2, ps, w.hf, H, 1, nH);
-    gemm(E, st, K, n, H, E2, emb + E1, EM, 1, n * EM, P + off[14] + H, 1, H + E2, ps, w.hf, H, 1, nH, true, P + off[15], ps, true);
-  }
+  forward_chain(E, st, c, w.alpha, w.color, w.hf, 0);
   // ---- backward
-  float *d_hc = w.dA, *d_h4 = w.dB_, *d_h3 = w.dC, *d_h2 = w.dD, *d_h1 = w.dE;
-  hipLaunchKernelGGL(heads_bwd_kernel, eg, dim3(256), head_lds, st, H, n, w.hc, w.color, d_alpha, d_color, P, ps, (int)off[8],
-                     (int)off[12], w.dhead, d_hc, d_h4, 0, 1.0f);
-  wgrad(E, st, K, 1, H, n, w.dhead, 1, 4, n * 4, w.h4, H, 1, nH, G + off[8], H, ps, G + off[9]);
-  wgrad(E, st, K, 3, H, n, w.dhead + 1, 1, 4, n * 4, w.hc, H, 1, nH, G + off[12], H, ps, G + off[13]);
+  hipLaunchKernelGGL(heads_bwd_kernel, dim3((unsigned)((n + 15) / 16), (unsigned)K), dim3(256), (size_t)4 * H * sizeof(float),
+                     st, H, n, w.hc, w.color, d_alpha, d_color, P, ps, (int)off[OBJNERF_T_ALPHA_W], (int)off[OBJNERF_T_OC_W],
+                     w.dhead, c.d_hc, c.d_h4, 0, 1.0f);
+  wgrad(E, st, K, 1, H, n, w.dhead, 1, 4, n * 4, w.h4, H, 1, nH, G + off[OBJNERF_T_ALPHA_W], H, ps, G + off[OBJNERF_T_ALPHA_B]);
+  wgrad(E, st, K, 3, H, n, w.dhead + 1, 1, 4, n * 4, w.hc, H, 1, nH, G + off[OBJNERF_T_OC_W], H, ps, G + off[OBJNERF_T_OC_B]);
   if (feat) {
     // 512-d head: d W_of = d_clip^T hf, d b_of = column sums, d_hf = (d_clip W_of) o [hf > 0]
-    float* extra = (float*)((char*)workspace + w.bytes);
-    float* keep = E.parts; const size_t keep_cap = E.parts_cap, keep_off = E.parts_off;
-    E.parts = extra; E.parts_cap = (size_t)K * wgrad_slices(K, C, H, n) * ((size_t)C * H + C) + 256; E.parts_off = 0;
-    wgrad(E, st, K, C, H, n, d_clip, 1, C, n * C, w.hf, H, 1, nH, G + off[16], H, ps, G + off[17]);
-    E.parts = keep; E.parts_cap = keep_cap; E.parts_off = keep_off;
-    gemm(E, st, K, n, H, C, d_clip, C, 1, n * C, P + off[16], H, 1, ps, w.d_hf, H, 1, nH, false, nullptr, 0, false, w.hf, H, 1, nH);
-    wgrad(E, st, K, H, H, n, w.d_hf, 1, H, nH, w.h4, H, 1, nH, G + off[14], H + E2, ps, G + off[15]);
-    wgrad(E, st, K, H, E2, n, w.d_hf, 1, H, nH, emb + E1, EM, 1, n * EM, G + off[14] + H, H + E2, ps);
-    gemm(E, st, K, n, H, H, w.d_hf, H, 1, nH, P + off[14], H + E2, 1, ps, d_h4, H, 1, nH, true);
-    gemm(E, st, K, n, E2, H, w.d_hf, H, 1, nH, P + off[14] + H, H + E2, 1, ps, d_emb + E1, EM, 1, n * EM, false);
+    GemmEnv Eh;                       // (its slabs have a region of their own behind the carve)
+    Eh.parts = (float*)((char*)workspace + w.bytes);
+    Eh.parts_cap = (size_t)K * wgrad_slices(K, C, H, n) * ((size_t)C * H + C) + 256;
+    wgrad(Eh, st, K, C, H, n, d_clip, 1, C, n * C, w.hf, H, 1, nH, G + off[OBJNERF_T_OF_W], H, ps, G + off[OBJNERF_T_OF_B]);
+    gemm(E, st, K, n, H, C, d_clip, C, 1, n * C, P + off[OBJNERF_T_OF_W], H, 1, ps, w.d_hf, H, 1, nH, false, nullptr, 0, false,
+         w.hf, H, 1, nH);
   }
-  wgrad(E, st, K, H, H, n, d_hc, 1, H, nH, w.h4, H, 1, nH, G + off[10], H + E2, ps, G + off[11]);
-  wgrad(E, st, K, H, E2, n, d_hc, 1, H, nH, emb + E1, EM, 1, n * EM, G + off[10] + H, H + E2, ps);
-  gemm(E, st, K, n, H, H, d_hc, H, 1, nH, P + off[10], H + E2, 1, ps, d_h4, H, 1, nH, true, nullptr, 0, false, w.h4, H, 1, nH);
-  gemm(E, st, K, n, E2, H, d_hc, H, 1, nH, P + off[10] + H, H + E2, 1, ps, d_emb + E1, EM, 1, n * EM, feat);
-  wgrad(E, st, K, H, H, n, d_h4, 1, H, nH, w.h3, H, 1, nH, G + off[6], H, ps, G + off[7]);
-  gemm(E, st, K, n, H, H, d_h4, H, 1, nH, P + off[6], H, 1, ps, d_h3, H, 1, nH, false, nullptr, 0, false, w.h3, H, 1, nH);
-  wgrad(E, st, K, H, H, n, d_h3, 1, H, nH, w.h2, H, 1, nH, G + off[4], H + E1, ps, G + off[5]);
-  wgrad(E, st, K, H, E1, n, d_h3, 1, H, nH, emb, EM, 1, n * EM, G + off[4] + H, H + E1, ps);
-  gemm(E, st, K, n, H, H, d_h3, H, 1, nH, P + off[4], H + E1, 1, ps, d_h2, H, 1, nH, false, nullptr, 0, false, w.h2, H, 1, nH);
-  gemm(E, st, K, n, E1, H, d_h3, H, 1, nH, P + off[4] + H, H + E1, 1, ps, d_emb, EM, 1, n * EM, false);
-  wgrad(E, st, K, H, H, n, d_h2, 1, H, nH, w.h1, H, 1, nH, G + off[2], H, ps, G + off[3]);
-  gemm(E, st, K, n, H, H, d_h2, H, 1, nH, P + off[2], H, 1, ps, d_h1, H, 1, nH, false, nullptr, 0, false, w.h1, H, 1, nH);
-  wgrad(E, st, K, H, E1, n, d_h1, 1, H, nH, emb, EM, 1, n * EM, G + off[0], E1, ps, G + off[1]);
-  gemm(E, st, K, n, E1, H, d_h1, H, 1, nH, P + off[0], E1, 1, ps, d_emb, EM, 1, n * EM, true);
+  backward_chain(E, st, st, c, feat, nullptr, [] {});
   if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
   return OBJNERF_OK;
 }
@@ -2919,19 +2928,16 @@ int embed_backward(const objnerf_net* net, int K, long N, const float* params, l
   int64_t off[OBJNERF_N_TENSORS + 1];
   objnerf_param_layout(net, off);
   hipStream_t st = (hipStream_t)stream;
-  int pg = (int)((N + 47) / 48);
-  if (pg > 1024) pg = 1024;
-  if (pg < 1) pg = 1;
+  const int pg = pe_bwd_blocks(N);
   (void)hipMemsetAsync(scratch, 0, (size_t)K * 64 * 4, st);
-  hipLaunchKernelGGL(pe_bwd_kernel, dim3(pg, K), dim3(256), 0, st, N, params, p_stride, (int)off[18], scale, pts, d_emb, scratch,
-                     (float*)nullptr);
+  hipLaunchKernelGGL(pe_bwd_kernel, dim3(pg, K), dim3(256), 0, st, N, params, p_stride, (int)off[OBJNERF_T_PE_B], scale, pts,
+                     d_emb, scratch, (float*)nullptr);
   hipLaunchKernelGGL(copy_cols_kernel, dim3((unsigned)((K * 63 + 255) / 256)), dim3(256), 0, st, (long)K, 63, scratch, 63L, d_B,
                      63L);
   if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
   return OBJNERF_OK;
 }
 
-// G = W_of^T W_of, wb = W_of^T b_of, bb = b_of . b_of of K objects: gram[k][Hh * Hh | Hh | 1], batch stride gstride
 // ---- the hoisted 512-d feature head around a fused kernel of another width (objnerf_generic.h)
 size_t feat_head_workspace_bytes(int K, int R, int Hh, int C) {
   const size_t XC = (size_t)Hh + 1;
@@ -2960,14 +2966,7 @@ int feat_head_prep(void* stream, int K, int R, int Hh, int C, const float* param
                    const float* gt_feat, const FeatHead& f, int operands) {
   GemmEnv E;
   E.operands = operands;
-  hipStream_t st = (hipStream_t)stream;
-  const long gst = (long)Hh * Hh + Hh + 1;
-  const float* P = params;
-  gemm(E, st, K, Hh, Hh, C, P + off_w, 1, Hh, p_stride, P + off_w, Hh, 1, p_stride, f.gram, Hh, 1, gst);
-  hipLaunchKernelGGL(featg_wb_kernel, dim3(Hh + 1, K), dim3(64), 0, st, P, p_stride, (int)off_w, (int)off_b, C, Hh, f.gram, gst);
-  gemm(E, st, K, R, Hh, C, gt_feat, C, 1, (long)R * C, P + off_w, Hh, 1, p_stride, f.rayin, Hh + 2, 1, (long)R * (Hh + 2));
-  hipLaunchKernelGGL(featg_rowstats_kernel, dim3((unsigned)((R + 15) / 16), K), dim3(256), 0, st, P, p_stride, (int)off_b, C, R,
-                     Hh + 2, gt_feat, f.rayin);
+  feat_prep_enqueue(E, (hipStream_t)stream, FeatHeadArgs{K, R, Hh, C, params, p_stride, (int)off_w, (int)off_b, gt_feat}, f);
   if (E.error) return OBJNERF_EINVAL;
   return hipGetLastError() == hipSuccess ? OBJNERF_OK : OBJNERF_ELAUNCH;
 }
@@ -2977,25 +2976,18 @@ int feat_head_grads(void* stream, int K, int R, int Hh, int C, const float* para
   E.operands = operands;
   E.parts = f.parts; E.parts_cap = f.parts_floats; E.parts_off = 0;
   E.need_parts = true;
-  hipStream_t st = (hipStream_t)stream;
-  const int XC = Hh + 1;
-  // T = gt_feat^T [a fh | a O], M = [c fh | c O]^T [fh | O] over the rays (X1 / X2 written by the fused kernel), then
-  // d W_of = T + W_of M + b_of m^T, d b_of likewise (featg_finish_kernel)
-  wgrad(E, st, K, C, XC, R, gt_feat, 1, C, (long)R * C, f.X1, XC, 1, (long)R * XC, f.Tm, XC, (long)C * XC);
-  wgrad(E, st, K, XC, XC, R, f.X2, 1, XC, (long)R * XC, f.rayfeat, Hh + 3, 1, (long)R * (Hh + 3), f.mom, XC, (long)XC * XC);
+  const FeatHeadArgs h = {K, R, Hh, C, params, p_stride, (int)off_w, (int)off_b, gt_feat};
+  feat_moments_enqueue(E, (hipStream_t)stream, h, f);
   if (E.parts_failed || E.error) return OBJNERF_EINVAL;
-  hipLaunchKernelGGL(featg_finish_kernel, dim3((unsigned)(((long)C * XC + 255) / 256), K), dim3(256), 0, st, params, p_stride,
-                     (int)off_w, (int)off_b, C, Hh, f.Tm, f.mom, grads);
+  feat_finish_enqueue((hipStream_t)stream, h, f, grads);
   return hipGetLastError() == hipSuccess ? OBJNERF_OK : OBJNERF_ELAUNCH;
 }
 
+// G = W_of^T W_of, wb = W_of^T b_of, bb = b_of . b_of of K objects: gram[k][Hh * Hh | Hh | 1], batch stride gstride
 void feat_gram(void* stream, int K, const float* params, long p_stride, int off_w, int off_b, int C, int Hh, float* gram,
                long gstride) {
   GemmEnv E;
-  gemm(E, (hipStream_t)stream, K, Hh, Hh, C, params + off_w, 1, Hh, p_stride, params + off_w, Hh, 1, p_stride, gram, Hh, 1,
-       gstride);
-  hipLaunchKernelGGL(featg_wb_kernel, dim3(Hh + 1, K), dim3(64), 0, (hipStream_t)stream, params, p_stride, off_w, off_b, C,
-                     Hh, gram, gstride);
+  feat_gram_enqueue(E, (hipStream_t)stream, FeatHeadArgs{K, 0, Hh, C, params, p_stride, off_w, off_b, nullptr}, gram, gstride);
 }
 // out[k][m][:] = W_of[k] hfeat[k][m] + b_of[k] * weight[k][m]   (model.py:101 applied after compositing; weight NULL = 1)
 void feature_head(void* stream, int K, long n, int Hh, int C, const float* params, long p_stride, long off_w, long off_b,

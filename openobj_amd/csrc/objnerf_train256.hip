@@ -2169,10 +2169,12 @@ static int run(const objnerf_net* net, const objnerf_train_args* a, hipStream_t 
   int64_t off[OBJNERF_N_TENSORS + 1];
   objnerf_param_layout(net, off);
   Lay256 L;
-  L.in_w = (int)off[0]; L.in_b = (int)off[1]; L.m1_w = (int)off[2]; L.m1_b = (int)off[3]; L.cat_w = (int)off[4];
-  L.cat_b = (int)off[5]; L.m2_w = (int)off[6]; L.m2_b = (int)off[7]; L.a_w = (int)off[8]; L.a_b = (int)off[9];
-  L.cl_w = (int)off[10]; L.cl_b = (int)off[11]; L.oc_w = (int)off[12]; L.oc_b = (int)off[13]; L.pe_b = (int)off[18];
-  L.fl_w = (int)off[14]; L.fl_b = (int)off[15];
+  L.in_w = (int)off[OBJNERF_T_IN_W]; L.in_b = (int)off[OBJNERF_T_IN_B]; L.m1_w = (int)off[OBJNERF_T_M1_W];
+  L.m1_b = (int)off[OBJNERF_T_M1_B]; L.cat_w = (int)off[OBJNERF_T_CAT_W]; L.cat_b = (int)off[OBJNERF_T_CAT_B];
+  L.m2_w = (int)off[OBJNERF_T_M2_W]; L.m2_b = (int)off[OBJNERF_T_M2_B]; L.a_w = (int)off[OBJNERF_T_ALPHA_W];
+  L.a_b = (int)off[OBJNERF_T_ALPHA_B]; L.cl_w = (int)off[OBJNERF_T_CL_W]; L.cl_b = (int)off[OBJNERF_T_CL_B];
+  L.oc_w = (int)off[OBJNERF_T_OC_W]; L.oc_b = (int)off[OBJNERF_T_OC_B]; L.pe_b = (int)off[OBJNERF_T_PE_B];
+  L.fl_w = (int)off[OBJNERF_T_FL_W]; L.fl_b = (int)off[OBJNERF_T_FL_B];
   OT* img = (OT*)(base + p.off_img);
   float* part = (float*)(base + p.off_part);
   float* slabs = (float*)(base + p.off_slabs);
@@ -2202,8 +2204,8 @@ static int run(const objnerf_net* net, const objnerf_train_args* a, hipStream_t 
     // the hoisted 512-d head: per object G = W_of^T W_of (+ wb, bb), per ray u = W_of^T g, beta, |g| -- ahead
     // of kernel A, with the operand type of the mode (16-bit GEMM operands, like the layer-wise path)
     fh = objgen::feat_head_carve(base + p.off_feat, K, a->R, HID, C);
-    const int rc = objgen::feat_head_prep(st, K, a->R, HID, C, a->params, (long)a->p_stride, off[16], off[17], a->gt_feat, fh,
-                                          (a->mode & OBJNERF_TRAIN_FP16) ? 2 : 1);
+    const int rc = objgen::feat_head_prep(st, K, a->R, HID, C, a->params, (long)a->p_stride, off[OBJNERF_T_OF_W],
+                                          off[OBJNERF_T_OF_B], a->gt_feat, fh, (a->mode & OBJNERF_TRAIN_FP16) ? 2 : 1);
     if (rc) return rc;
     const long tot = (long)K * GIMG_PIECES * 64;
     hipLaunchKernelGGL((packg256_kernel<OT>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, K, fh.gram,
@@ -2260,8 +2262,9 @@ static int run(const objnerf_net* net, const objnerf_train_args* a, hipStream_t 
   hipLaunchKernelGGL(finalize256_kernel, dim3((unsigned)((fn.P + 255) / 256), (unsigned)K), dim3(256), 0, st, fn);
   if (FEAT) {
     // d W_of, d b_of from the rays' moments (two GEMMs over the rays + featg_finish_kernel)
-    const int rc = objgen::feat_head_grads(st, K, a->R, HID, C, a->params, (long)a->p_stride, off[16], off[17], a->gt_feat, fh,
-                                           a->grads, (a->mode & OBJNERF_TRAIN_FP16) ? 2 : 1);
+    const int rc = objgen::feat_head_grads(st, K, a->R, HID, C, a->params, (long)a->p_stride, off[OBJNERF_T_OF_W],
+                                           off[OBJNERF_T_OF_B], a->gt_feat, fh, a->grads,
+                                           (a->mode & OBJNERF_TRAIN_FP16) ? 2 : 1);
     if (rc) return rc;
   }
   if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
