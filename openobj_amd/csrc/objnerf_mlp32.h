@@ -135,6 +135,27 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifndef OBJ32_ABL
 #define OBJ32_ABL 0          // objnerf_train32.hip: ceiling-measurement builds only
 #endif
+// Pins the issue order of the MFMAs written around it.  A layer's output pair and a weight-gradient tile pair are two
+// independent accumulator chains written alternately (A B A B); the pre-RA scheduler otherwise pairs up the k-steps of one
+// accumulator (A A B B, every second MFMA then waits for the one just ahead of it) and reads the operands right ahead of
+// their k-step.  Only MFMAs are held in place, so the operand reads move up: pinned, the weight-gradient rounds have 5 - 9
+// ds_reads in flight at an MFMA instead of 1 - 3.  Every chain keeps its k-order: results are bit-equal with and without.
+// OFF unless the including unit defines OBJ32_PIN 1 ahead of this header: only objnerf_train32.hip does (the unit it was
+// measured in); the renderer and the eval kernels, which share mma_f16, keep the code they had.
+#ifndef OBJ32_PIN
+#define OBJ32_PIN 0
+#endif
+// sched_barrier mask: a set bit lets that class cross.  Bit 0 (all ALU) is clear and bits 1 (VALU), 2 (SALU), 10 (TRANS)
+// are set, which by LLVM's rule for a mask that names ALU sub-classes leaves bit 3 (MFMA) as the one ALU class that may
+// not cross; bits 4 - 9 (all VMEM, VMEM read, VMEM write, all DS, DS read, DS write) are set.
+#define OBJ32_SCHED_VALU 0x002
+#define OBJ32_SCHED_SALU 0x004
+#define OBJ32_SCHED_VMEM 0x070
+#define OBJ32_SCHED_DS 0x380
+#define OBJ32_SCHED_TRANS 0x400
+#define OBJ32_ALL_BUT_MFMA (OBJ32_SCHED_VALU | OBJ32_SCHED_SALU | OBJ32_SCHED_VMEM | OBJ32_SCHED_DS | OBJ32_SCHED_TRANS)
+static_assert(OBJ32_ALL_BUT_MFMA == 0x7f6, "sched_barrier mask: everything but MFMA may cross");
+#define OBJ32_PIN_MFMA() do { if (OBJ32_PIN) __builtin_amdgcn_sched_barrier(OBJ32_ALL_BUT_MFMA); } while (0)
 __device__ __forceinline__ void mma_f16(T32& acc, const float* wf, const int row0, const f32x4& xt) {
   if ((OBJ32_ABL) & 64) { asm volatile("" :: "v"(xt)); return; }
   f32x2 a[4];
@@ -143,7 +164,9 @@ __device__ __forceinline__ void mma_f16(T32& acc, const float* wf, const int row
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     acc.t[0] = OBJ_MFMA(a[r][0], xt[r], acc.t[0]);
+    OBJ32_PIN_MFMA();
     acc.t[1] = OBJ_MFMA(a[r][1], xt[r], acc.t[1]);
+    OBJ32_PIN_MFMA();
   }
 }
 __device__ __forceinline__ void mma_f32(T32& acc, const float* wf, const int row0, const T32& x) {

@@ -8,6 +8,7 @@
 // all octaves) and the in-major conflict-free weight image (one ds_read_b64 per forward k-step, two ds_read_b128 per
 // transposed tile).  Per tile and wave: 560 MFMAs (602 before) and ~40 % fewer VALU instructions.
 #include <mutex>
+#define OBJ32_PIN 1        // this unit pins the MFMA issue order of mma_f16 and wg_pair (objnerf_mlp32.h)
 #include "objnerf_mlp32.h"
 #include "objnerf_train_common.h"
 #include "../../include/objnerf_hip.h"
@@ -66,9 +67,13 @@ __device__ __forceinline__ void wg_pair(f32x4& acc0, f32x4& acc1, const float* d
     const f32x2 a0 = *reinterpret_cast<const f32x2*>(dT + st);
     const f32x2 a1 = *reinterpret_cast<const f32x2*>(dT + 16 * STG_LD + st);
     acc0 = OBJ_MFMA(a0[0], b[0], acc0);
+    OBJ32_PIN_MFMA();
     acc1 = OBJ_MFMA(a1[0], b[0], acc1);
+    OBJ32_PIN_MFMA();
     acc0 = OBJ_MFMA(a0[1], b[1], acc0);
+    OBJ32_PIN_MFMA();
     acc1 = OBJ_MFMA(a1[1], b[1], acc1);
+    OBJ32_PIN_MFMA();
   }
 }
 
