@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define OBJNERF_ABI_VERSION 10
+#define OBJNERF_ABI_VERSION 11
 
 #define OBJNERF_OK 0
 #define OBJNERF_EINVAL (-22)       /* bad shape / null pointer / unsupported size        */
@@ -616,6 +616,109 @@ int objnerf_vertex_colors(const objnerf_color_args* a, void* stream);
 /* host only: the "rainbow" table the colour kernel uses, out [256][3] fp32 (matplotlib's _lut[:256, :3] rounded to
  * fp32).  Returns 256. */
 int objnerf_rainbow_lut(float* out);
+
+/* ABI 11 -- cross-frame mask association (objnerf_maskgraph.hip): the data-parallel parts of
+ * maskclustering/mask_graph.py.  All pointers are device pointers; point sets are fp64 [n][3] rows grouped into
+ * segments, segment s = rows seg_off[s] .. seg_off[s+1]-1 (device int64 [S+1], seg_off[0] = 0, seg_off[S] = n, an empty
+ * segment is allowed), n < 2^31.  No float atomics; integer atomics only where the result does not depend on their
+ * order; fp64 point arithmetic without contraction; two calls with the same inputs write the same bytes.
+ *
+ * objnerf_cell_keys: out_min [S][3] = the minimum corner of every segment (+inf for an empty one), out_keys [n] =
+ * ix << 42 | iy << 21 | iz with i = floor((p - (min - shift)) / cell) per axis (shift >= 0: 0 for the two searches
+ * below; voxel / 2 with cell = voxel gives open3d's voxel_down_sample indices, mask_graph.py:410, :1178).  status (one int32) is set to 1 when a point
+ * is not finite or lies more than 2^21 - 1 cells from the corner (its key is then meaningless), else 0.  The caller
+ * sorts the keys per segment (stable; rows stay inside their segment) and passes sorted keys and permutation
+ * (perm[t] = the row at sorted position t) to the two entries below.  cell must be >= the search radius; pass the radius
+ * times (1 + 2^-20) so that the rounding of the division cannot put two points within the radius two cells apart.
+ *
+ * objnerf_dbscan: pcd.cluster_dbscan(eps, min_points) (pcd_denoise_dbscan, mask_graph.py:244-316) for S point sets at
+ * once.  A point is core when at least min_points[s] points of its segment, itself included, have d^2 <= eps^2;
+ * clusters are the connected components of the core points, numbered per segment from 0 by their smallest core row,
+ * ascending; a border point takes the lowest cluster id among its core neighbours; a point without core neighbour gets
+ * -1: the labels of a sequential DBSCAN that visits the points in row order (scikit-learn's DBSCAN on the same
+ * input).  labels int32 [n].  A segment with min_points[s] <= 0 is skipped and its labels are left as they are (the
+ * fallback chain 100 -> 20 -> 10 re-runs only the segments that found no cluster, on the same sorted keys).
+ * ws: objnerf_dbscan_workspace_bytes(n).
+ *
+ * objnerf_cloud_overlap: compute_similarity_matrix_thre's compute_point_cloud_distance(...) < dis_thre counts
+ * (mask_graph.py:835-846) for all ordered pairs of C clouds (C <= 65535) in one launch: out_count [C][C] int64,
+ * out_count[a][b] = the points of cloud a that have some point of cloud b at distance < dis_thre (strict; by
+ * d^2 < dis_thre^2).  The keys come from objnerf_cell_keys with ONE segment over all rows (one grid for every cloud),
+ * sorted per cloud. */
+int objnerf_cell_keys(int64_t n, int32_t S, const double* pts, const int64_t* seg_off, double cell, double shift,
+                      double* out_min, int64_t* out_keys, int32_t* status, void* stream);
+size_t objnerf_dbscan_workspace_bytes(int64_t n);
+int objnerf_dbscan(int64_t n, int32_t S, const double* pts, const int64_t* seg_off, const int64_t* sorted_keys,
+                   const int64_t* perm, const int32_t* min_points, double eps, void* ws, size_t ws_bytes, int32_t* labels,
+                   void* stream);
+int objnerf_cloud_overlap(int64_t n, int32_t C, const double* pts, const int64_t* cloud_off, const int64_t* sorted_keys,
+                          const int64_t* perm, double dis_thre, int64_t* out_count, void* stream);
+
+/* objnerf_mask_ray_boxes: the ray / box pass of compute_2d_iou_matrix (mask_graph.py:683-710 with get_rays :562-571,
+ * ray_box_intersection :634-643 and min_rect_bbox :660-680) for F frames and N mask boxes in one launch.  For frame f
+ * a ray per 10th pixel: d = ((ix - cx) / fx, (iy - cy) / fy, 1) in fp32, widened to fp64 and multiplied by
+ * depth[f][iy][ix] / 1000.0 (depth: the raw uint16 image [F][H][W]; 1000 is the reference's literal), rotated by
+ * twc[f][:3,:3] (twc [F][4][4] fp64 row-major), origin twc[f][:3,3].  Slab test in fp64, IEEE semantics followed
+ * literally (a zero depth gives infinities and NaNs; a NaN makes the comparisons false): t = (bound - origin) / d,
+ * near = max over axes of min(tmin, tmax), far = min of max, hit = near <= far && far > 0.  boxes [N][6] fp64 (min, max).
+ * out [F][N][4] int32 = (row_min, col_min, row_max + 1, col_max + 1) of the hit rays in the H/10 x W/10 ray grid, zeros
+ * when no ray hits.  W or H not a multiple of 10: OBJNERF_EINVAL (the reference's view() fails on them).  F <= 65535. */
+typedef struct objnerf_ray_boxes_args {
+  int32_t F, N, W, H;
+  double fx, fy, cx, cy;
+  const uint16_t* depth; const double* twc; const double* boxes;
+  int32_t* out;
+} objnerf_ray_boxes_args;
+int objnerf_mask_ray_boxes(const objnerf_ray_boxes_args* a, void* stream);
+
+/* Mask clouds of one frame (project_mask_pc, mask_graph.py:337-462).  objnerf_mask_points: pix [n] int32 = v * W + u
+ * of the pixels (the caller lists them in raster order per (mask, connected component) segment), depth [H][W] fp32
+ * (already depth / depth_scale with values outside [0.07, 10] set to 0, :342-350), pose fp64 [4][4] row-major:
+ * x = (u - cx) * d / fx, y = (v - cy) * d / fy, z = d in fp32, left to right without contraction (:375-377), then
+ * out [n][3] fp64 = pose * (x, y, z, 1) (pcd.transform, :382), every product and sum rounded on its own.
+ * objnerf_mask_hist: out [M][96] fp32 = per mask the 3 x 32 histogram (bins of width 8; channel order of img [H][W][3]
+ * uint8, the reference's B, G, R) over the pixels pix[mask_off[m] .. mask_off[m+1]) -- the caller passes mask & depth > 0,
+ * the mask before filtering (:451) -- integer counts written as fp32 (cv2.calcHist).
+ * objnerf_point_bounds: out [S][6] fp64 = (min, max) of every segment's points (:441-442; +inf / -inf when empty). */
+typedef struct objnerf_mask_points_args {
+  int64_t n;
+  int32_t W, H;
+  double fx, fy, cx, cy;
+  const int32_t* pix; const float* depth; const double* pose;
+  double* out;
+} objnerf_mask_points_args;
+int objnerf_mask_points(const objnerf_mask_points_args* a, void* stream);
+int objnerf_mask_hist(int64_t n, int32_t M, const int32_t* pix, const int64_t* mask_off, const uint8_t* img, int32_t W,
+                      int32_t H, float* out, void* stream);
+int objnerf_point_bounds(int64_t n, int32_t S, const double* pts, const int64_t* seg_off, double* out, void* stream);
+
+/* objnerf_mask_affinity: the five N x N affinity matrices of mask_graph.py:1047-1054 and MaskGraph.__init__'s weighted
+ * sum (:46) in one pass, W [N][N] fp32:
+ *   geo    compute_3d_iou_matrix (:501-530): box intersection volume / the smaller volume in fp64, NaN -> 0;
+ *          boxes [N][6] fp64;
+ *   cap, clip  adjacent_matrix_feat (:573-584): x_i . x_j / (|x_i| |x_j|) in fp32, products on v_mfma_f32_16x16x4_f32,
+ *          no epsilon (a zero row gives NaN, which makes no edge); cap [N][d_cap], clip [N][d_clip], widths 1 .. 1024;
+ *   color  compute_color_matrix (:592-601): rows divided by their norm first, then the products; color [N][96];
+ *   geo2d  compute_2d_iou_matrix's running mean m = (m * f + iou_f) / (f + 1) in fp32 in frame order (:712), iou_f =
+ *          compute_iou_2d (:533-558) of boxes2d [F][N][4] int32 (objnerf_mask_ray_boxes): int32 areas, a true
+ *          division in fp32, NaN -> 0; bit-equal to the recurrence.  Skipped (boxes2d may be NULL) when w_geo2d == 0.
+ *   W = fp32(geo * w_geo + fp64(cap *f32 w_cap) + fp64(clip *f32 w_clip) + fp64(color *f32 w_color)
+ *            + fp64(geo2d *f32 w_geo2d)): numpy's fp64 matrix plus float32 matrices times Python floats.
+ * terms (NULL: not written) [5][N][N] fp32 = geo, cap, clip, color, geo2d.  Norms are fp32(sqrt(fp64 sum of squares)).
+ * row_off [N+1] int64 = exclusive offsets of the rows' edge counts, edges being the pairs i < j with W[i][j] >= 1.0
+ * (get_edges, :57-80; tested on the fp32 W); row_off[N] = their number.  objnerf_mask_edges then writes them in
+ * row-major order: out_ij [E][2] int32, out_w [E] fp32 (entries past max_edges are dropped).
+ * ws: objnerf_affinity_workspace_bytes(N).  No atomics; two calls write the same bytes. */
+typedef struct objnerf_affinity_args {
+  int32_t N, F, d_cap, d_clip;
+  double w_geo, w_cap, w_clip, w_color, w_geo2d;
+  const double* boxes; const float* cap; const float* clip; const float* color; const int32_t* boxes2d;
+  float* W; float* terms;
+} objnerf_affinity_args;
+size_t objnerf_affinity_workspace_bytes(int32_t N);
+int objnerf_mask_affinity(const objnerf_affinity_args* a, void* ws, size_t ws_bytes, int64_t* row_off, void* stream);
+int objnerf_mask_edges(int32_t N, const float* W, const int64_t* row_off, int64_t max_edges, int32_t* out_ij, float* out_w,
+                       void* stream);
 
 #ifdef __cplusplus
 }

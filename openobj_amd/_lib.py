@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OBJNERF_LIB") or os.path.join(_HERE, "csrc", "libobjnerf_hip.so")   # OBJNERF_LIB: diagnostic builds
 
 OBJNERF_N_TENSORS = 19
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class ObjnerfError(RuntimeError):
@@ -131,6 +131,26 @@ class ColorArgs(C.Structure):
                 ("out", C.c_void_p)]
 
 
+class RayBoxesArgs(C.Structure):
+    _fields_ = [("F", C.c_int32), ("N", C.c_int32), ("W", C.c_int32), ("H", C.c_int32),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("depth", C.c_void_p), ("twc", C.c_void_p), ("boxes", C.c_void_p), ("out", C.c_void_p)]
+
+
+class MaskPointsArgs(C.Structure):
+    _fields_ = [("n", C.c_int64), ("W", C.c_int32), ("H", C.c_int32),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("pix", C.c_void_p), ("depth", C.c_void_p), ("pose", C.c_void_p), ("out", C.c_void_p)]
+
+
+class AffinityArgs(C.Structure):
+    _fields_ = [("N", C.c_int32), ("F", C.c_int32), ("d_cap", C.c_int32), ("d_clip", C.c_int32),
+                ("w_geo", C.c_double), ("w_cap", C.c_double), ("w_clip", C.c_double), ("w_color", C.c_double),
+                ("w_geo2d", C.c_double),
+                ("boxes", C.c_void_p), ("cap", C.c_void_p), ("clip", C.c_void_p), ("color", C.c_void_p),
+                ("boxes2d", C.c_void_p), ("W", C.c_void_p), ("terms", C.c_void_p)]
+
+
 PROJ_COSINE = 1          # OBJNERF_PROJ_COSINE
 PROJ_PER_SEGMENT = 2     # OBJNERF_PROJ_PER_SEGMENT
 COLOR_RGB, COLOR_CONSTANT, COLOR_RAINBOW, COLOR_PCA = 0, 1, 2, 3      # OBJNERF_COLOR_*
@@ -232,6 +252,22 @@ SIGNATURES = {
     "objnerf_moments": (C.c_int, [C.POINTER(MomentsArgs), C.c_void_p, C.c_size_t, C.c_void_p]),
     "objnerf_vertex_colors": (C.c_int, [C.POINTER(ColorArgs), C.c_void_p]),
     "objnerf_rainbow_lut": (C.c_int, [C.c_void_p]),
+    # ABI 11: cross-frame mask association (objnerf_maskgraph.hip)
+    "objnerf_cell_keys": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_dbscan_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "objnerf_dbscan": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "objnerf_cloud_overlap": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                        C.c_void_p, C.c_void_p]),
+    "objnerf_mask_ray_boxes": (C.c_int, [C.POINTER(RayBoxesArgs), C.c_void_p]),
+    "objnerf_mask_points": (C.c_int, [C.POINTER(MaskPointsArgs), C.c_void_p]),
+    "objnerf_mask_hist": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                    C.c_void_p, C.c_void_p]),
+    "objnerf_point_bounds": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_affinity_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "objnerf_mask_affinity": (C.c_int, [C.POINTER(AffinityArgs), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "objnerf_mask_edges": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

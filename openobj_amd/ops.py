@@ -1157,3 +1157,196 @@ def rainbow_lut() -> np.ndarray:
     if n != 256:
         raise _lib.ObjnerfError("objnerf_rainbow_lut failed")
     return out
+
+
+# ------------------------------------------------------------------ cross-frame mask association (objnerf_maskgraph.hip)
+_CELL_SLACK = 1.0 + 2.0 ** -20      # cell side = radius x this (include/objnerf_hip.h, objnerf_cell_keys)
+
+
+def _point_sets(pts: torch.Tensor, seg_off, name: str):
+    pts = _req(pts, torch.float64, name)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise _lib.ObjnerfError(f"{name}: expected [n, 3] fp64 points")
+    off = torch.as_tensor(seg_off, dtype=torch.int64).cpu()
+    n = int(pts.shape[0])
+    if off.dim() != 1 or off.numel() < 2 or int(off[0]) != 0 or int(off[-1]) != n or bool((off[1:] < off[:-1]).any()):
+        raise _lib.ObjnerfError(f"{name}: seg_off must rise from 0 to the number of points")
+    if n >= 2 ** 31:
+        raise _lib.ObjnerfError(f"{name}: at most 2^31 - 1 points")
+    return pts, off, n
+
+
+def cell_keys(pts: torch.Tensor, seg_off, cell: float, shift: float = 0.0, name: str = "cell_keys"):
+    """objnerf_cell_keys -> (keys int64 [n] = ix << 42 | iy << 21 | iz, the sets' minimum corners fp64 [S, 3])."""
+    pts, off, n = _point_sets(pts, seg_off, name)
+    dev = pts.device
+    S = off.numel() - 1
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    mins = torch.empty(S, 3, dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().objnerf_cell_keys(n, S, _ptr(pts) if n else None, _ptr(off.to(dev)), float(cell), float(shift), _ptr(mins),
+                                  _ptr(keys) if n else None, _ptr(status), _stream()), "objnerf_cell_keys")
+    if int(status.item()) != 0:
+        raise _lib.ObjnerfError(f"{name}: a point is not finite or lies more than 2^21 cells from its set's corner")
+    return keys, mins
+
+
+def _sorted_cells(pts: torch.Tensor, key_off: torch.Tensor, sort_off: torch.Tensor, radius: float, name: str):
+    """Cell keys on one grid per segment of key_off, sorted (stable) inside every segment of sort_off
+    -> (sorted keys, permutation), both int64 [n]."""
+    dev = pts.device
+    keys, _ = cell_keys(pts, key_off, float(radius) * _CELL_SLACK, 0.0, name)
+    sk, perm = torch.sort(keys, stable=True)
+    seg = torch.repeat_interleave(torch.arange(sort_off.numel() - 1, device=dev), (sort_off[1:] - sort_off[:-1]).to(dev))
+    _, order = torch.sort(seg[perm], stable=True)
+    return sk[order].contiguous(), perm[order].contiguous()
+
+
+class DbscanPlan:
+    """The sorted cell keys of S point sets for one eps: dbscan() with several min_points reuses them."""
+
+    def __init__(self, pts: torch.Tensor, seg_off, eps: float):
+        self.pts, self.off, self.n = _point_sets(pts, seg_off, "dbscan")
+        self.eps = float(eps)
+        if not self.eps > 0.0:
+            raise _lib.ObjnerfError("dbscan: eps must be positive")
+        self.S = self.off.numel() - 1
+        self.dev = self.pts.device
+        self.off_dev = self.off.to(self.dev)
+        self.labels = torch.full((self.n,), -1, dtype=torch.int32, device=self.dev)
+        if self.n:
+            self.keys, self.perm = _sorted_cells(self.pts, self.off, self.off, self.eps, "dbscan")
+            self.ws = torch.empty(int(lib().objnerf_dbscan_workspace_bytes(self.n)), dtype=torch.uint8, device=self.dev)
+
+    def run(self, min_points) -> torch.Tensor:
+        """objnerf_dbscan: labels int32 [n] (per set, from 0; -1 noise); min_points: one int, or one per set, <= 0
+        leaving that set's labels as the previous run wrote them."""
+        mp = torch.as_tensor(min_points, dtype=torch.int32).reshape(-1)
+        if mp.numel() == 1:
+            mp = mp.expand(self.S)
+        if mp.numel() != self.S:
+            raise _lib.ObjnerfError("dbscan: one min_points per point set")
+        mp = mp.contiguous().to(self.dev)
+        if self.n:
+            check(lib().objnerf_dbscan(self.n, self.S, _ptr(self.pts), _ptr(self.off_dev), _ptr(self.keys), _ptr(self.perm),
+                                       _ptr(mp), self.eps, _ptr(self.ws), self.ws.numel(), _ptr(self.labels), _stream()),
+                  "objnerf_dbscan")
+        return self.labels
+
+
+def dbscan(pts: torch.Tensor, seg_off, eps: float, min_points) -> torch.Tensor:
+    """Segmented DBSCAN of the point sets pts[seg_off[s] : seg_off[s+1]] -> labels int32 [n], scikit-learn's."""
+    return DbscanPlan(pts, seg_off, eps).run(min_points).clone()
+
+
+def cloud_overlap(pts: torch.Tensor, cloud_off, dis_thre: float) -> torch.Tensor:
+    """objnerf_cloud_overlap -> count int64 [C, C]: points of cloud a with a point of cloud b nearer than dis_thre."""
+    pts, off, n = _point_sets(pts, cloud_off, "cloud_overlap")
+    if not float(dis_thre) > 0.0:
+        raise _lib.ObjnerfError("cloud_overlap: dis_thre must be positive")
+    Cn = off.numel() - 1
+    dev = pts.device
+    out = torch.empty(Cn, Cn, dtype=torch.int64, device=dev)
+    keys = perm = None
+    if n:
+        keys, perm = _sorted_cells(pts, torch.tensor([0, n]), off, float(dis_thre), "cloud_overlap")
+    check(lib().objnerf_cloud_overlap(n, Cn, _ptr(pts) if n else None, _ptr(off.to(dev)), _ptr(keys), _ptr(perm),
+                                      float(dis_thre), _ptr(out), _stream()), "objnerf_cloud_overlap")
+    return out
+
+
+def mask_ray_boxes(depth_raw: torch.Tensor, twc: torch.Tensor, boxes: torch.Tensor, fx: float, fy: float, cx: float,
+                   cy: float) -> torch.Tensor:
+    """objnerf_mask_ray_boxes: depth_raw [F, H, W] int16 holding the uint16 image's bits, twc [F, 4, 4] fp64,
+    boxes [N, 6] fp64 -> [F, N, 4] int32 (row_min, col_min, row_max + 1, col_max + 1) in the every-10th-pixel grid."""
+    depth_raw = _req(depth_raw, torch.int16, "depth_raw")
+    twc = _req(twc, torch.float64, "twc")
+    boxes = _req(boxes, torch.float64, "boxes")
+    if depth_raw.dim() != 3 or tuple(twc.shape) != (depth_raw.shape[0], 4, 4) or boxes.dim() != 2 or boxes.shape[1] != 6:
+        raise _lib.ObjnerfError("mask_ray_boxes: depth_raw [F, H, W], twc [F, 4, 4], boxes [N, 6]")
+    F, H, W = (int(v) for v in depth_raw.shape)
+    N = int(boxes.shape[0])
+    out = torch.empty(F, N, 4, dtype=torch.int32, device=boxes.device)
+    a = _lib.RayBoxesArgs(F, N, W, H, float(fx), float(fy), float(cx), float(cy), _ptr(depth_raw), _ptr(twc), _ptr(boxes),
+                          _ptr(out))
+    check(lib().objnerf_mask_ray_boxes(C.byref(a), _stream()), "objnerf_mask_ray_boxes")
+    return out
+
+
+def mask_points(pix: torch.Tensor, depth: torch.Tensor, pose: torch.Tensor, fx: float, fy: float, cx: float,
+                cy: float) -> torch.Tensor:
+    """objnerf_mask_points: pix int32 [n] (v * W + u), depth fp32 [H, W], pose fp64 [4, 4] -> world points fp64 [n, 3]."""
+    pix = _req(pix, torch.int32, "pix")
+    depth = _req(depth, torch.float32, "depth")
+    pose = _req(pose, torch.float64, "pose")
+    if depth.dim() != 2 or tuple(pose.shape) != (4, 4) or pix.dim() != 1:
+        raise _lib.ObjnerfError("mask_points: pix [n], depth [H, W], pose [4, 4]")
+    n = int(pix.numel())
+    out = torch.empty(n, 3, dtype=torch.float64, device=depth.device)
+    a = _lib.MaskPointsArgs(n, int(depth.shape[1]), int(depth.shape[0]), float(fx), float(fy), float(cx), float(cy),
+                            _ptr(pix) if n else None, _ptr(depth), _ptr(pose), _ptr(out) if n else None)
+    check(lib().objnerf_mask_points(C.byref(a), _stream()), "objnerf_mask_points")
+    return out
+
+
+def mask_hist(pix: torch.Tensor, mask_off, img: torch.Tensor) -> torch.Tensor:
+    """objnerf_mask_hist: per mask the 3 x 32-bin histogram of img uint8 [H, W, 3] over pix[mask_off[m] : mask_off[m+1]]
+    -> fp32 [M, 96]."""
+    pix = _req(pix, torch.int32, "pix")
+    img = _req(img, torch.uint8, "img")
+    off = torch.as_tensor(mask_off, dtype=torch.int64).cpu()
+    n = int(pix.numel())
+    if img.dim() != 3 or img.shape[2] != 3 or off.numel() < 2 or int(off[0]) != 0 or int(off[-1]) != n or \
+            bool((off[1:] < off[:-1]).any()):
+        raise _lib.ObjnerfError("mask_hist: img [H, W, 3] and mask_off rising from 0 to the number of pixels")
+    M = off.numel() - 1
+    out = torch.empty(M, 96, dtype=torch.float32, device=img.device)
+    check(lib().objnerf_mask_hist(n, M, _ptr(pix) if n else None, _ptr(off.to(img.device)), _ptr(img), int(img.shape[1]),
+                                  int(img.shape[0]), _ptr(out), _stream()), "objnerf_mask_hist")
+    return out
+
+
+def point_bounds(pts: torch.Tensor, seg_off) -> torch.Tensor:
+    """objnerf_point_bounds -> fp64 [S, 6]: (min, max) of every point set (exact)."""
+    pts, off, n = _point_sets(pts, seg_off, "point_bounds")
+    S = off.numel() - 1
+    out = torch.empty(S, 6, dtype=torch.float64, device=pts.device)
+    check(lib().objnerf_point_bounds(n, S, _ptr(pts) if n else None, _ptr(off.to(pts.device)), _ptr(out), _stream()),
+          "objnerf_point_bounds")
+    return out
+
+
+def mask_affinity(boxes: torch.Tensor, cap: torch.Tensor, clip: torch.Tensor, color: torch.Tensor,
+                  boxes2d: Optional[torch.Tensor], weights: Sequence[float], want_terms: bool = False):
+    """objnerf_mask_affinity + objnerf_mask_edges: weights = (w_geo, w_cap, w_clip, w_color, w_geo2d)
+    -> (W fp32 [N, N], edges int32 [E, 2] with i < j in row-major order, their weights fp32 [E], terms [5, N, N] or None)."""
+    boxes = _req(boxes, torch.float64, "boxes")
+    cap, clip, color = (_req(t, torch.float32, n) for t, n in ((cap, "cap"), (clip, "clip"), (color, "color")))
+    N = int(boxes.shape[0])
+    if N < 1 or tuple(boxes.shape) != (N, 6) or cap.dim() != 2 or clip.dim() != 2 or cap.shape[0] != N or \
+            clip.shape[0] != N or tuple(color.shape) != (N, 96):
+        raise _lib.ObjnerfError("mask_affinity: boxes [N, 6], cap [N, Dc], clip [N, Dl], color [N, 96]")
+    wg, wc, wl, wo, w2 = (float(w) for w in weights)
+    F = 0
+    if w2 != 0.0:
+        if boxes2d is None:
+            raise _lib.ObjnerfError("mask_affinity: a 2-D weight needs the 2-D boxes")
+        boxes2d = _req(boxes2d, torch.int32, "boxes2d")
+        if boxes2d.dim() != 3 or boxes2d.shape[1] != N or boxes2d.shape[2] != 4 or boxes2d.shape[0] < 1:
+            raise _lib.ObjnerfError("mask_affinity: boxes2d [F, N, 4]")
+        F = int(boxes2d.shape[0])
+    dev = boxes.device
+    W = torch.empty(N, N, dtype=torch.float32, device=dev)
+    terms = torch.empty(5, N, N, dtype=torch.float32, device=dev) if want_terms else None
+    row_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    nbytes = int(lib().objnerf_affinity_workspace_bytes(N))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    a = _lib.AffinityArgs(N, F, int(cap.shape[1]), int(clip.shape[1]), wg, wc, wl, wo, w2, _ptr(boxes), _ptr(cap), _ptr(clip),
+                          _ptr(color), _ptr(boxes2d) if w2 != 0.0 else None, _ptr(W), _ptr(terms))
+    check(lib().objnerf_mask_affinity(C.byref(a), _ptr(ws), nbytes, _ptr(row_off), _stream()), "objnerf_mask_affinity")
+    E = int(row_off[-1].item())
+    ij = torch.empty(E, 2, dtype=torch.int32, device=dev)
+    ew = torch.empty(E, dtype=torch.float32, device=dev)
+    if E:
+        check(lib().objnerf_mask_edges(N, _ptr(W), _ptr(row_off), E, _ptr(ij), _ptr(ew), _stream()), "objnerf_mask_edges")
+    return W, ij, ew, terms
