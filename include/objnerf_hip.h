@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define OBJNERF_ABI_VERSION 11
+#define OBJNERF_ABI_VERSION 12
 
 #define OBJNERF_OK 0
 #define OBJNERF_EINVAL (-22)       /* bad shape / null pointer / unsupported size        */
@@ -120,6 +120,11 @@ typedef struct objnerf_sample_args {
    * the map are clamped (the reference raises IndexError; the host wrapper checks the frame range). */
   const float* global_partfeat; const int32_t* use_frame; float* out_partfeat;
   int32_t pf_frames, pf_w, pf_h, pf_c, pf_stride; float part_down;
+  /* ABI 12 -- the same gather through an index image (part_index == NULL: the dense form above, unchanged).
+   * part_index [pf_frames][pf_w][pf_h] int32 holds, for the pixel the dense form would read, a row number of
+   * global_partfeat, which is then the row TABLE [pf_rows][pf_c] (row 0 = zeros: a pixel no mask covers); frame and
+   * pixel are computed as above, the row number is clamped to [0, pf_rows). */
+  const int32_t* part_index; int32_t pf_rows; int32_t reserved_pf;
 } objnerf_sample_args;
 int objnerf_sample_rays(const objnerf_sample_args* a, void* stream);
 
@@ -718,6 +723,17 @@ typedef struct objnerf_affinity_args {
 size_t objnerf_affinity_workspace_bytes(int32_t N);
 int objnerf_mask_affinity(const objnerf_affinity_args* a, void* ws, size_t ws_bytes, int64_t* row_off, void* stream);
 int objnerf_mask_edges(int32_t N, const float* W, const int64_t* row_off, int64_t max_edges, int32_t* out_ij, float* out_w,
+                       void* stream);
+
+/* ABI 12 -- compact part-level feature maps (objnerf_partmap.hip; partlevel/sam_clip_dir.py:113-133 of the reference).
+ * objnerf_part_index: masks [M][Hp][Wp] uint8 (non-zero = set; already taken on the stride, mask[::d, ::d]) ->
+ * out [Hp][Wp] int32 = the number of the LAST mask that covers the pixel (the reference assigns mask after mask, a later
+ * one overwrites an earlier one), -1 where none does.  M = 0 is allowed (masks may then be NULL): all -1.
+ * objnerf_part_dense: out [n_px][C] = table[index[p]], table [rows][C] fp32, index [n_px] int32 clamped to [0, rows):
+ * with row 0 of the table zero and the index image shifted by one (0 = none) this is the reference's dense map.  A wave
+ * per pixel, 16-byte lanes when C % 4 == 0 and table / out are 16-byte aligned.  No atomics in either. */
+int objnerf_part_index(int32_t M, int32_t Hp, int32_t Wp, const uint8_t* masks, int32_t* out, void* stream);
+int objnerf_part_dense(int64_t n_px, int32_t C, int32_t rows, const int32_t* index, const float* table, float* out,
                        void* stream);
 
 #ifdef __cplusplus

@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OBJNERF_LIB") or os.path.join(_HERE, "csrc", "libobjnerf_hip.so")   # OBJNERF_LIB: diagnostic builds
 
 OBJNERF_N_TENSORS = 19
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class ObjnerfError(RuntimeError):
@@ -50,7 +50,9 @@ class SampleArgs(C.Structure):
                 # ABI 6: the part-feature gather (vmap.py:437-452)
                 ("global_partfeat", C.c_void_p), ("use_frame", C.c_void_p), ("out_partfeat", C.c_void_p),
                 ("pf_frames", C.c_int32), ("pf_w", C.c_int32), ("pf_h", C.c_int32), ("pf_c", C.c_int32),
-                ("pf_stride", C.c_int32), ("part_down", C.c_float)]
+                ("pf_stride", C.c_int32), ("part_down", C.c_float),
+                # ABI 12: the gather through an index image (trailing, zero when not given: the dense form)
+                ("part_index", C.c_void_p), ("pf_rows", C.c_int32), ("reserved_pf", C.c_int32)]
 
 
 class IngestItem(C.Structure):
@@ -268,6 +270,9 @@ SIGNATURES = {
     "objnerf_affinity_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "objnerf_mask_affinity": (C.c_int, [C.POINTER(AffinityArgs), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "objnerf_mask_edges": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ABI 12: compact part-level feature maps (objnerf_partmap.hip)
+    "objnerf_part_index": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_part_dense": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -550,7 +550,10 @@ __global__ __launch_bounds__(256) void sample_gather_kernel(const objnerf_sample
       fid = min(max(fid, 0l), (long)a.pf_frames - 1);
       pw = min(max(pw, 0l), (long)a.pf_w - 1);
       ph = min(max(ph, 0l), (long)a.pf_h - 1);
-      pf_row[threadIdx.x] = (fid * a.pf_w + pw) * a.pf_h + ph;
+      long row = (fid * a.pf_w + pw) * a.pf_h + ph;
+      // ABI 12: the map is an index image over a row table (objnerf_partmap.hip); row 0 of the table is the zero row
+      if (a.part_index) row = min(max((long)a.part_index[row], 0l), (long)a.pf_rows - 1);
+      pf_row[threadIdx.x] = row;
     }
   }
   if (!a.out_partfeat) return;                                     // (uniform over the launch)
@@ -991,6 +994,7 @@ static bool sample_args_ok(const objnerf_sample_args* a) {
   if ((a->out_origins != nullptr) != (a->out_dirs != nullptr)) return false;
   if (a->out_partfeat && (!a->global_partfeat || !a->use_frame || a->pf_frames <= 0 || a->pf_w <= 0 || a->pf_h <= 0 ||
                           a->pf_c <= 0 || a->pf_stride <= 0 || !(a->part_down > 0.0f))) return false;
+  if (a->out_partfeat && a->part_index && a->pf_rows <= 0) return false;
   return a->rays_dir_cache && a->out_rgb && a->out_depth && a->out_valid && a->out_labels && a->out_z &&
          a->max_depth_ws && a->n_frames > 0 && a->n_px > 0 && a->n_cam2surf > 0 && a->n_bins > 0;
 }

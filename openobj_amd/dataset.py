@@ -6,7 +6,8 @@ Every sample is the reference's dict (dataset.py:175-190, 404-412), arrays TRANS
     image u8 [W,H,3] (RGB) | depth f32 [W,H] metres, > max_depth zeroed | T f64 [4,4] camera->world | T_obj eye(4)
     obj i32 [W,H]: instance id per pixel, 0 = background, -1 = unknown
     bbox_dict {id: int64 tensor [w_min, w_max, h_min, h_max]} (object boxes enlarged by 20 %) | frame_id
-    obj_clip / obj_cap {id: feature}      (+ part_feat [W',H',C] in part mode)
+    obj_clip / obj_cap {id: feature}      (+ part_feat [W',H',C] in part mode; from a compact partlevel/<i>.npz
+                                           instead part_index i32 [W',H'] (0 = none) + part_table f32 [M+1,C], row 0 zero)
 
 Images are decoded with Pillow (the reference uses OpenCV, which this build does not depend on); PNG / JPEG decode
 to the same pixels.  The one resampling step -- ScanNet colour frames resized to the depth resolution
@@ -166,18 +167,30 @@ class _FrameSet(Dataset):
         sample = {"image": image, "depth": depth, "T": self.Twc[idx], "T_obj": np.eye(4), "obj": obj,
                   "bbox_dict": bbox_dict, "frame_id": idx, "obj_clip": clip_dict, "obj_cap": cap_dict}
         if self.part_mode:
-            sample["part_feat"] = part_feat
+            if isinstance(part_feat, tuple):             # the compact form: the dense map is never built
+                sample["part_index"], sample["part_table"] = part_feat
+            else:
+                sample["part_feat"] = part_feat
         return sample
 
     def _part_feat(self, idx):
+        """The frame's part map: the reference's dense partlevel/<idx>.npy as a [W', H', C] tensor if that file exists,
+        else the compact partlevel/<idx>.npz (part_maps.py) as the pair (part_index i32 [W', H'], 0 = none;
+        part_table f32 [M + 1, C], row 0 zero)."""
         if not self.part_mode:
             return None
-        return torch.tensor(np.load(os.path.join(self.root_dir, "partlevel", str(idx) + ".npy")).transpose((1, 0, 2)))
+        stem = os.path.join(self.root_dir, "partlevel", str(idx))
+        if os.path.exists(stem + ".npy") or not os.path.exists(stem + ".npz"):
+            return torch.tensor(np.load(stem + ".npy").transpose((1, 0, 2)))
+        from . import part_maps                          # (imports the GPU bindings: only when a compact file is read)
+        idx_t, table = part_maps.shifted(*part_maps.load_compact(stem + ".npz"))
+        return idx_t.t().contiguous(), table
 
 
 class Replica(_FrameSet):
     """dataset.py:43-190: rgb/rgb_<i>.png, depth/depth_<i>.png (u16), instance_our/semantic_instance_<i//10>.png,
-    class_our/semantic_class_<i//10>.png, traj_w_c.txt, object_{clip,cap}feat.pkl, partlevel/<i>.npy."""
+    class_our/semantic_class_<i//10>.png, traj_w_c.txt, object_{clip,cap}feat.pkl, partlevel/<i>.npy (or the compact
+    partlevel/<i>.npz of part_maps.py when there is no .npy)."""
 
     def __init__(self, cfg):
         self._common_init(cfg)
@@ -214,6 +227,11 @@ class ScanNet(_FrameSet):
 
     def _part_feat(self, idx):
         pf = super()._part_feat(idx)
+        if isinstance(pf, tuple) and self.part_down == 10:
+            # A compact file is made dense here, on the host, before the halving below: every output pixel of the
+            # bilinear halving is a blend of up to four rows, so each mask boundary would need table rows of its own,
+            # and the halved map is 6.3 MB (64 x 48 x 512 fp32) against 67 MB -- an index form has nothing to gain there.
+            pf = pf[1][pf[0].long()]
         if pf is not None and self.part_down == 10:      # dataset.py:305-309
             pf = pf.permute(2, 0, 1).unsqueeze(0)
             pf = torch.nn.functional.interpolate(pf, scale_factor=0.5, mode="bilinear", align_corners=False)

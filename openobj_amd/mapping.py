@@ -65,6 +65,7 @@ class IncrementalMapper:
         self.scene_bg: Optional[sceneObject] = None
         self.global_partfeat: Optional[torch.Tensor] = None
         self._partfeat_buf: Optional[torch.Tensor] = None
+        self.part_store = None                  # part_maps.PartStore: the compact form (index images + one row table)
         self.loop: Optional[otrain.HipTrainLoop] = None
         self.bg_loop: Optional[otrain.BackgroundLoop] = None
         self._restack = False
@@ -84,7 +85,18 @@ class IncrementalMapper:
         twc = _to_dev(sample["T"], dev, torch.float32)
         bbox_dict, obj_clip, obj_cap = sample["bbox_dict"], sample["obj_clip"], sample["obj_cap"]
         live_frame_id = int(sample["frame_id"]) if "frame_id" in sample else frame_id
-        if cfg.part_mode:
+        if cfg.part_mode and "part_feat" not in sample:
+            # a compact part map (dataset.py read partlevel/<frame>.npz): an index image and its rows, never made dense
+            if self.global_partfeat is not None:
+                raise ValueError("dense and compact part maps in one run")
+            if self.part_store is None:
+                from .part_maps import PartStore
+                self.part_store = PartStore(dev)
+            self.part_store.append(_to_dev(sample["part_index"], dev, torch.int32),
+                                   _to_dev(sample["part_table"], dev, torch.float32))
+        elif cfg.part_mode:
+            if self.part_store is not None:
+                raise ValueError("dense and compact part maps in one run")
             # train.py:187-191 grows the [frames, W', H', C] tensor with torch.cat every frame (67 MB per frame at
             # 240 x 136 x 512: quadratic copying); here the buffer doubles its capacity and the frame is copied once
             part = _to_dev(sample["part_feat"], dev, torch.float32)
@@ -156,10 +168,14 @@ class IncrementalMapper:
             self._restack = False
 
     # ------------------------------------------------------------------ train.py:297-392
+    def part_source(self):
+        """What the samplers gather part features from: the dense tensor or the PartStore, whichever this run holds."""
+        return self.global_partfeat if self.global_partfeat is not None else self.part_store
+
     def _pool_of(self, so: sceneObject, n_frames: int, n_samples: int):
         # seeded draws generated inside the sampler kernels; origins + directions instead of the point tensor
         rgb, depth, _valid, labels, (origins, dirs), z, feat = so.get_training_samples(
-            n_frames, n_samples, self.cam_info.rays_dir_cache, self.global_partfeat, compact=True)
+            n_frames, n_samples, self.cam_info.rays_dir_cache, self.part_source(), compact=True)
         n = n_frames * n_samples
         tdev = self.cfg.training_device
         pool = {"origins": origins.to(tdev), "dirs": dirs.to(tdev),
@@ -188,7 +204,7 @@ class IncrementalMapper:
             self._sampler_ids = tuple(self.obj_dict)
         rgb, depth, _valid, labels, (origins, dirs), z, feat = self._sampler.sample(
             cfg.n_iter_per_frame * cfg.win_size, cfg.n_samples_per_frame, self.cam_info.rays_dir_cache,
-            self.global_partfeat, compact=True)
+            self.part_source(), compact=True)
         tdev = cfg.training_device
         pool = {"origins": origins.to(tdev), "dirs": dirs.to(tdev), "z": z.to(tdev), "gt_depth": depth.to(tdev),
                 "gt_rgb": rgb.to(tdev).float() / 255.0, "labels": labels.to(tdev)}

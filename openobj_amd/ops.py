@@ -675,26 +675,67 @@ def _partfeat_fields(a: SampleArgs, partfeat, K, F, n, dev, stacked):
     """ABI 6 fields of the part-feature gather (vmap.py:437-452).  partfeat = (global_partfeat [Fn, Wp, Hp, C] fp32,
     use_frame [F] | [K, F] (dataset frame id of every keyframe slot), stride, part_down) or None.  Returns the output
     tensor ([n, C] | [K, n, C]) the launch fills; the frame range is checked here (the reference would raise an
-    IndexError from its advanced indexing, the kernel clamps)."""
+    IndexError from its advanced indexing, the kernel clamps).
+    ABI 12: a part_maps.PartStore in place of the dense tensor gathers through its index image (index int32
+    [Fn, Wp, Hp] of global row numbers, table fp32 [rows, C] with row 0 zero); the dense map never exists."""
     if partfeat is None:
         return None
+    from .part_maps import PartStore               # (part_maps imports this module)
     gpf, use_frame, stride, part_down = partfeat
-    gpf = _req(gpf, torch.float32, "global_partfeat")
-    if gpf.dim() != 4:
-        raise ObjnerfError("global_partfeat must be [frames, W / part_down, H / part_down, C]")
+    index = None
+    if isinstance(gpf, PartStore):
+        if gpf.index is None or gpf.table is None:
+            raise IndexError("use_frame / stride outside the part store (it holds no frame)")
+        index = _req(gpf.index, torch.int32, "part_index")
+        gpf = _req(gpf.table, torch.float32, "part_table")
+        if index.dim() != 3 or gpf.dim() != 2 or gpf.shape[0] < 1 or gpf.shape[1] < 1 or index.device != gpf.device:
+            raise ObjnerfError("part store: index [frames, W / part_down, H / part_down] and table [rows, C] expected")
+        shape = tuple(index.shape) + (gpf.shape[1],)
+    else:
+        gpf = _req(gpf, torch.float32, "global_partfeat")
+        if gpf.dim() != 4:
+            raise ObjnerfError("global_partfeat must be [frames, W / part_down, H / part_down, C]")
+        shape = tuple(gpf.shape)
     uf = torch.as_tensor(np.asarray(use_frame.cpu() if torch.is_tensor(use_frame) else use_frame))   # host bookkeeping
     if int(stride) != stride or int(stride) <= 0 or bool((uf != uf.round()).any()):
         raise ObjnerfError("part features: integer frame ids and stride expected")
     if uf.numel() != K * F:
         raise ObjnerfError("use_frame must hold one frame id per keyframe slot")
-    if int(uf.min()) < 0 or int(uf.max()) // int(stride) >= gpf.shape[0]:
+    if int(uf.min()) < 0 or int(uf.max()) // int(stride) >= shape[0]:
         raise IndexError("use_frame / stride outside global_partfeat")
     uf = uf.to(torch.int32).contiguous().to(dev)
-    out = torch.empty(*((K,) if stacked else ()), n, gpf.shape[3], device=dev)
+    out = torch.empty(*((K,) if stacked else ()), n, shape[3], device=dev)
     a.global_partfeat, a.use_frame, a.out_partfeat = _ptr(gpf), _ptr(uf), _ptr(out)
-    a.pf_frames, a.pf_w, a.pf_h, a.pf_c = gpf.shape
+    a.pf_frames, a.pf_w, a.pf_h, a.pf_c = shape
     a.pf_stride, a.part_down = int(stride), float(part_down)
-    a._keep = (gpf, uf)
+    if index is not None:
+        a.part_index, a.pf_rows = _ptr(index), int(gpf.shape[0])
+    a._keep = (gpf, uf, index)
+    return out
+
+
+def part_index(masks: torch.Tensor) -> torch.Tensor:
+    """objnerf_part_index: masks [M, Hp, Wp] uint8 on the device (already taken on the stride) -> int32 [Hp, Wp], the
+    number of the last mask that covers each pixel, -1 where none does (sam_clip_dir.py:118-125).  M may be 0."""
+    masks = _req(masks, torch.uint8, "masks")
+    if masks.dim() != 3 or masks.shape[1] < 1 or masks.shape[2] < 1:
+        raise ObjnerfError("part_index: masks must be [M, Hp, Wp]")
+    M, Hp, Wp = masks.shape
+    out = torch.empty(Hp, Wp, dtype=torch.int32, device=masks.device)
+    check(lib().objnerf_part_index(M, Hp, Wp, _ptr(masks) if M else None, _ptr(out), _stream()), "objnerf_part_index")
+    return out
+
+
+def part_dense(index: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """objnerf_part_dense: index int32 [...] (0 = the zero row), table fp32 [rows, C] -> fp32 [..., C] = table[index]
+    (values outside the table are clamped into it)."""
+    index = _req(index, torch.int32, "index")
+    table = _req(table, torch.float32, "table")
+    if table.dim() != 2 or table.shape[0] < 1 or table.shape[1] < 1 or index.numel() < 1 or index.device != table.device:
+        raise ObjnerfError("part_dense: index [...] and table [rows, C] on one device expected")
+    out = torch.empty(*index.shape, table.shape[1], device=table.device)
+    check(lib().objnerf_part_dense(index.numel(), table.shape[1], table.shape[0], _ptr(index), _ptr(table), _ptr(out),
+                                   _stream()), "objnerf_part_dense")
     return out
 
 

@@ -183,7 +183,8 @@ class sceneObject:
                [int(self.obj_id) & 0x7FFFFFFF]
 
     def _partfeat_args(self, global_partfeat):
-        """The part-feature gather of vmap.py:437-452 as arguments of the sampler launch (ops._partfeat_fields)."""
+        """The part-feature gather of vmap.py:437-452 as arguments of the sampler launch (ops._partfeat_fields);
+        global_partfeat is the dense [frames, W', H', C] tensor or a part_maps.PartStore (gather through its index)."""
         if not (self.part_mode and global_partfeat is not None):
             return None
         return (global_partfeat, self.use_frame, self.stride, self.part_down)
