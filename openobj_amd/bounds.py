@@ -37,6 +37,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import ops
 from ._lib import ObbArgs, ObjnerfError, VoxelArgs, check, lib
 from .utils import BoundingBox
 
@@ -160,14 +161,8 @@ def _voxels_group(objs, F, W, H, intr, voxel, budget, stats):
                                        _ptr(pts), _ptr(keys), _stream()), "objnerf_voxel_emit")
         skeys, perm = torch.sort(keys, stable=True)          # equal keys keep the points' (slot, row, column) order
         del keys
-        hws = torch.empty(int(lib().objnerf_voxel_heads_workspace_bytes(n)) // 8, dtype=torch.int64, device=dev)
-        check(lib().objnerf_voxel_heads(n, _ptr(skeys), _ptr(hws), _stream()), "objnerf_voxel_heads")
-        V = int(hws[-1].item())
-        cen = torch.empty(V, 3, dtype=torch.float64, device=dev)
-        vkeys = torch.empty(V, dtype=torch.int64, device=dev)
-        first = torch.full((k1 - k0,), -1, dtype=torch.int64, device=dev)
-        check(lib().objnerf_voxel_centroids(n, _ptr(skeys), _ptr(perm), _ptr(pts), _ptr(hws), V, _ptr(cen), _ptr(vkeys),
-                                            _ptr(first), _stream()), "objnerf_voxel_centroids")
+        cen, vkeys, first = ops.run_centroids(skeys, perm, pts, k1 - k0)
+        V = int(cen.shape[0])
         if ev:
             ev[1].record()
             ev[1].synchronize()

@@ -11,7 +11,7 @@
 //   voxel_emit_kernel      recomputes each point (same code, same rounding) and writes it with its voxel key at
 //                          base + segment offset + prefix in the row: the compacted cloud is in the reference's order;
 //   (host: torch.sort(keys, stable=True) -- equal keys keep that order)
-//   voxel_heads_kernel / voxel_scan_heads_kernel / voxel_centroid_kernel
+//   voxel_heads_kernel / wg_scan_kernel (objnerf_wg.h) / voxel_centroid_kernel
 //                          voxel heads of the sorted keys, their offsets, and for every head the in-order double sum
 //                          of its points / count -- open3d's AddPoint / GetAveragePoint.
 // (b) Oriented-box search over K objects' hull candidates (normal n, edge e) in one launch:
@@ -27,11 +27,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
-#include "../../include/objnerf_hip.h"
+#include "objnerf_wg.h"
 
 namespace {
-
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH; } while (0)
 
 constexpr int VX_WG = 256;            // lanes = columns of a tile
 constexpr int VX_BY = 32;             // rows of a tile
@@ -42,8 +40,6 @@ constexpr int VX_HEAD_BLOCK = VX_HEAD_WG * VX_HEAD_PER;
 constexpr int OBB_WG = 256;
 constexpr int OBB_TILE = 2048;        // hull vertices per LDS tile (48 KiB: 3 workgroups per CU)
 constexpr int KEY_SHIFT = 42;         // sort key = (object in chunk) << 42 | linear voxel index
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct VxLayout {
   long nxc, nyb, ntiles, rows;        // column chunks, row bands, tiles per keyframe, segments per object
@@ -163,27 +159,9 @@ __global__ void __launch_bounds__(VX_SCAN_WG) voxel_finish_kernel(const objnerf_
   const long n = (long)nk * a.H * L.nxc;                  // the live slots' segments: a prefix of the object's array
   const int32_t* counts = (const int32_t*)(ws + L.counts) + (long)k * L.rows;
   int64_t* offs = (int64_t*)(ws + L.offsets) + (long)k * L.rows;
-  __shared__ int64_t part[VX_SCAN_WG];
-  __shared__ int64_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (long c0 = 0; c0 < n; c0 += VX_SCAN_WG) {
-    const long i = c0 + threadIdx.x;
-    const int64_t v = i < n ? counts[i] : 0;
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < VX_SCAN_WG; o <<= 1) {             // Hillis-Steele inclusive scan (integers: exact)
-      const int64_t t = threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-      __syncthreads();
-      part[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < n) offs[i] = carry + part[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 0) carry += part[VX_SCAN_WG - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out_total[k] = carry;
+  int64_t total[1];
+  wg_scan_exclusive<VX_SCAN_WG, 1>(counts, offs, n, total);
+  if (threadIdx.x == 0) out_total[k] = total[0];
   if (threadIdx.x < 6) {
     const double* mm = (const double*)(ws + L.minmax) + (long)k * a.F * L.ntiles * 6;
     const bool is_min = threadIdx.x < 3;
@@ -225,12 +203,11 @@ __global__ void __launch_bounds__(VX_WG) voxel_emit_kernel(const objnerf_voxel_a
     bal[r] = __ballot(col && m[r] && d[r] > 0.f);
     if (lane == 0) wcnt[wv][r] = __popcll(bal[r]);
   }
-  __syncthreads();
-  const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  __syncthreads();                                       // (32 rows through one barrier: wg_exclusive_flag's two halves)
 #pragma unroll
   for (int r = 0; r < VX_BY; ++r) {
     if (!((bal[r] >> lane) & 1ull)) continue;
-    int pre = __popcll(bal[r] & below);
+    int pre = wave_rank(bal[r]);
     for (int w = 0; w < wv; ++w) pre += wcnt[w][r];
     const int64_t pos = base[k] + offs[((long)kf * a.H + y0 + r) * L.nxc + xc] + pre;
     if (pos < 0 || pos >= n_points) continue;             // (cannot happen with the scan's counts; never write past)
@@ -255,39 +232,8 @@ __global__ void __launch_bounds__(VX_HEAD_WG) voxel_heads_kernel(const int64_t n
   for (int q = 0; q < VX_HEAD_PER; ++q)
     if (i0 + q < n) c += is_head(keys, i0 + q);
   __shared__ int wsum[VX_HEAD_WG / 64];
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int w = 0; w < VX_HEAD_WG / 64; ++w) t += wsum[w];
-    blk[blockIdx.x] = t;
-  }
-}
-
-// one workgroup: blk[0 .. nb) -> exclusive offsets, blk[nb] = total
-__global__ void __launch_bounds__(VX_SCAN_WG) voxel_scan_heads_kernel(const int64_t nb, int64_t* __restrict__ blk) {
-  __shared__ int64_t part[VX_SCAN_WG];
-  __shared__ int64_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t c0 = 0; c0 < nb; c0 += VX_SCAN_WG) {
-    const int64_t i = c0 + threadIdx.x;
-    const int64_t v = i < nb ? blk[i] : 0;
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < VX_SCAN_WG; o <<= 1) {
-      const int64_t t = threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-      __syncthreads();
-      part[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < nb) blk[i] = carry + part[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 0) carry += part[VX_SCAN_WG - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) blk[nb] = carry;
+  const int t = wg_sum<VX_HEAD_WG>(c, wsum);
+  if (threadIdx.x == 0) blk[blockIdx.x] = t;
 }
 
 __global__ void __launch_bounds__(VX_HEAD_WG) voxel_centroid_kernel(
@@ -301,18 +247,9 @@ __global__ void __launch_bounds__(VX_HEAD_WG) voxel_centroid_kernel(
     h[q] = i0 + q < n && is_head(keys, i0 + q);
     c += h[q];
   }
-  // exclusive prefix of c over the workgroup (wave shuffles + 4 LDS slots)
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = c;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
   __shared__ int wsum[VX_HEAD_WG / 64];
-  if (lane == 63) wsum[wv] = inc;
-  __syncthreads();
-  int64_t j = blk[blockIdx.x] + inc - c;
-  for (int w = 0; w < wv; ++w) j += wsum[w];
+  int total;
+  int64_t j = blk[blockIdx.x] + wg_exclusive<VX_HEAD_WG>(c, wsum, total);
   for (int q = 0; q < VX_HEAD_PER; ++q) {
     if (!h[q]) continue;
     const int64_t i = i0 + q, key = keys[i];
@@ -509,7 +446,9 @@ int objnerf_voxel_heads(int64_t n, const int64_t* sorted_keys, int64_t* ws, void
   if (nb > 0x7fffffff) return OBJNERF_EINVAL;
   hipLaunchKernelGGL(voxel_heads_kernel, dim3((unsigned)nb), dim3(VX_HEAD_WG), 0, (hipStream_t)stream, n, sorted_keys, ws);
   CHECK_LAUNCH();
-  hipLaunchKernelGGL(voxel_scan_heads_kernel, dim3(1), dim3(VX_SCAN_WG), 0, (hipStream_t)stream, nb, ws);
+  // blk[0 .. nb) -> exclusive offsets, blk[nb] = the number of heads
+  hipLaunchKernelGGL((wg_scan_kernel<VX_SCAN_WG, 1, int64_t>), dim3(1), dim3(VX_SCAN_WG), 0, (hipStream_t)stream, ws, nb,
+                     ws + nb);
   CHECK_LAUNCH();
   return OBJNERF_OK;
 }

@@ -7,11 +7,9 @@
 #include <math.h>
 #include "objnerf_device.h"
 #include "objnerf_philox.h"
-#include "../../include/objnerf_hip.h"
+#include "objnerf_wg.h"
 
 namespace {
-
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH; } while (0)
 
 // residuals of render_rays.py:65-83.  mode 0: |a - b| (L1), 1: (a - b)^2 (L2): n elements; 2: 1 - cos(a, b) over rows
 // of C entries (F.cosine_similarity: each norm clamped at 1e-8): n rows.

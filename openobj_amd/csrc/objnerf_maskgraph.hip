@@ -12,7 +12,7 @@
 //       dbscan_union_kernel    union-find over the core points: every link points from the larger root to the smaller
 //                              (atomicCAS on a root, atomicMin for path halving), so whatever the order of the links
 //                              the final root of a component is its smallest index;
-//       dbscan_flatten_kernel / scan_blocks_kernel / dbscan_rank_kernel
+//       dbscan_flatten_kernel / wg_scan_kernel (objnerf_wg.h) / dbscan_rank_kernel
 //                              roots, and the rank of every root among the roots (count, scan, emit): cluster ids
 //                              ascend with the smallest core index of the cluster;
 //       dbscan_label_kernel    a core point takes its cluster, a border point the lowest cluster among its core
@@ -31,19 +31,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
-#include "../../include/objnerf_hip.h"
+#include "objnerf_wg.h"
 
 namespace {
-
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH; } while (0)
 
 constexpr int MG_WG = 256;
 constexpr int MG_SCAN_WG = 1024;
 constexpr int CELL_BITS = 21;
 constexpr int64_t CELL_MAX = (1ll << CELL_BITS) - 1;
 constexpr int RAY_STEP = 10;          // get_rays: torch.arange(0, w, 10)
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct DbLayout { size_t parent, root, rank, core, blk, total; int64_t nb; };
 
@@ -234,46 +230,19 @@ __global__ void __launch_bounds__(MG_WG) dbscan_flatten_kernel(const DbArgs a) {
     a.root[i] = r;
     is_root = r == (int32_t)i;
   }
-  const int c = __syncthreads_count(is_root);
+  __shared__ int wcnt[MG_WG / 64];
+  int c;
+  wg_exclusive_flag<MG_WG>(is_root, wcnt, c);
   if (threadIdx.x == 0) a.blk[blockIdx.x] = c;
-}
-
-// one workgroup: blk[0 .. nb) -> exclusive offsets, blk[nb] = total
-__global__ void __launch_bounds__(MG_SCAN_WG) scan_blocks_kernel(const int64_t nb, int32_t* __restrict__ blk) {
-  __shared__ int32_t part[MG_SCAN_WG];
-  __shared__ int32_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t c0 = 0; c0 < nb; c0 += MG_SCAN_WG) {
-    const int64_t i = c0 + threadIdx.x;
-    const int32_t v = i < nb ? blk[i] : 0;
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < MG_SCAN_WG; o <<= 1) {             // Hillis-Steele inclusive scan (integers: exact)
-      const int32_t t = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-      __syncthreads();
-      part[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < nb) blk[i] = carry + part[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 0) carry += part[MG_SCAN_WG - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) blk[nb] = carry;
 }
 
 // rank[i] = roots among the points before i
 __global__ void __launch_bounds__(MG_WG) dbscan_rank_kernel(const DbArgs a) {
   const int64_t i = (int64_t)blockIdx.x * MG_WG + threadIdx.x;
   const bool is_root = i < a.n && a.root[i] == (int32_t)i;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(is_root);
   __shared__ int wcnt[MG_WG / 64];
-  if (lane == 0) wcnt[wv] = __popcll(bal);
-  __syncthreads();
-  int pre = __popcll(bal & (lane == 0 ? 0ull : (~0ull >> (64 - lane))));
-  for (int w = 0; w < wv; ++w) pre += wcnt[w];
+  int total;
+  const int pre = wg_exclusive_flag<MG_WG>(is_root, wcnt, total);
   if (i < a.n) a.rank[i] = a.blk[blockIdx.x] + pre;
 }
 
@@ -443,7 +412,6 @@ __global__ void __launch_bounds__(MG_WG) mask_hist_kernel(const int64_t n, const
 }
 
 // --------------------------------------------------------------------------------------------------------- affinity
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 constexpr int AF_T = 32;              // a workgroup's block of W: 2 x 2 tiles of 16 x 16, one per wave
 
 // a wave per row: |x| = fp32(sqrt(fp64 sum of squares)), the lanes' partial sums combined in a fixed order
@@ -460,18 +428,6 @@ __global__ void __launch_bounds__(MG_WG) row_norm_kernel(const int N, const int 
   if (lane == 0) out[row] = (float)sqrt(s);
 }
 
-__device__ __forceinline__ float4 load_row4(const float* __restrict__ p, const int k0, const int D, const bool ok,
-                                            const bool vec) {
-  float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (!ok || k0 >= D) return f;
-  if (vec) return *(const float4*)(p + k0);               // D % 4 == 0: the whole float4 is in the row
-  f.x = p[k0];
-  if (k0 + 1 < D) f.y = p[k0 + 1];
-  if (k0 + 2 < D) f.z = p[k0 + 2];
-  if (k0 + 3 < D) f.w = p[k0 + 3];
-  return f;
-}
-
 // acc[e] = x[i0 + 4 g + e] . x[j0 + q] (g = lane >> 4, q = lane & 15) on v_mfma_f32_16x16x4_f32: k-step t of chunk c
 // takes column 16 c + 4 g + t from lane group g, for both operands; pre: each element divided by its row's norm first
 __device__ __forceinline__ floatx4 gram_tile(const float* __restrict__ x, const int D, const int N, const int i0,
@@ -485,7 +441,8 @@ __device__ __forceinline__ floatx4 gram_tile(const float* __restrict__ x, const 
   floatx4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int c = 0; c < (D + 15) / 16; ++c) {                // (a wave-uniform trip count; lane groups past D hold zeros)
     const int k0 = 16 * c + 4 * g;
-    float4 fa = load_row4(pa, k0, D, va, vec), fb = load_row4(pb, k0, D, vb, vec);
+    float4 fa = vec ? load_row4<true>(pa, k0, D, va) : load_row4<false>(pa, k0, D, va);
+    float4 fb = vec ? load_row4<true>(pb, k0, D, vb) : load_row4<false>(pb, k0, D, vb);
     if (pre) {
       fa.x = fa.x / na; fa.y = fa.y / na; fa.z = fa.z / na; fa.w = fa.w / na;
       fb.x = fb.x / nb; fb.y = fb.y / nb; fb.z = fb.z / nb; fb.w = fb.w / nb;
@@ -575,39 +532,8 @@ __global__ void __launch_bounds__(MG_WG) edge_count_kernel(const int N, const fl
   int c = 0;
   for (int j = i + 1 + threadIdx.x; j < N; j += MG_WG) c += W[(int64_t)i * N + j] >= 1.0f;
   __shared__ int wsum[MG_WG / 64];
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int w = 0; w < MG_WG / 64; ++w) t += wsum[w];
-    row_off[i] = t;
-  }
-}
-
-// one workgroup: v[0 .. n) -> exclusive offsets, v[n] = total
-__global__ void __launch_bounds__(MG_SCAN_WG) scan64_kernel(const int64_t n, int64_t* __restrict__ v) {
-  __shared__ int64_t part[MG_SCAN_WG];
-  __shared__ int64_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int64_t c0 = 0; c0 < n; c0 += MG_SCAN_WG) {
-    const int64_t i = c0 + threadIdx.x;
-    const int64_t x = i < n ? v[i] : 0;
-    part[threadIdx.x] = x;
-    __syncthreads();
-    for (int o = 1; o < MG_SCAN_WG; o <<= 1) {
-      const int64_t t = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-      __syncthreads();
-      part[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < n) v[i] = carry + part[threadIdx.x] - x;
-    __syncthreads();
-    if (threadIdx.x == 0) carry += part[MG_SCAN_WG - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) v[n] = carry;
+  const int t = wg_sum<MG_WG>(c, wsum);
+  if (threadIdx.x == 0) row_off[i] = t;
 }
 
 // one workgroup per row: its edges in column order at row_off[i] ..
@@ -615,21 +541,15 @@ __global__ void __launch_bounds__(MG_WG) edge_emit_kernel(const int N, const flo
                                                           const int64_t* __restrict__ row_off, const int64_t max_edges,
                                                           int32_t* __restrict__ out_ij, float* __restrict__ out_w) {
   const int i = blockIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   __shared__ int wcnt[MG_WG / 64];
   int64_t base = row_off[i];
   for (int j0 = i + 1; j0 < N; j0 += MG_WG) {
     const int j = j0 + threadIdx.x;
     const float w = j < N ? W[(int64_t)i * N + j] : 0.f;
     const bool e = j < N && w >= 1.0f;
-    const unsigned long long bal = __ballot(e);
-    __syncthreads();
-    if (lane == 0) wcnt[wv] = __popcll(bal);
-    __syncthreads();
-    int pre = __popcll(bal & (lane == 0 ? 0ull : (~0ull >> (64 - lane))));
-    int tot = 0;
-    for (int k = 0; k < MG_WG / 64; ++k) { if (k < wv) pre += wcnt[k]; tot += wcnt[k]; }
-    const int64_t pos = base + pre;
+    __syncthreads();                                       // (the tile before has read wcnt)
+    int tot;
+    const int64_t pos = base + wg_exclusive_flag<MG_WG>(e, wcnt, tot);
     if (e && pos >= 0 && pos < max_edges) { out_ij[2 * pos] = i; out_ij[2 * pos + 1] = j; out_w[pos] = w; }
     base += tot;
   }
@@ -683,7 +603,8 @@ int objnerf_dbscan(int64_t n, int32_t S, const double* pts, const int64_t* seg_o
   CHECK_LAUNCH();
   hipLaunchKernelGGL(dbscan_flatten_kernel, grid, wg, 0, st, a);
   CHECK_LAUNCH();
-  hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(MG_SCAN_WG), 0, st, L.nb, a.blk);
+  // blk[0 .. nb) -> exclusive offsets, blk[nb] = the number of roots
+  hipLaunchKernelGGL((wg_scan_kernel<MG_SCAN_WG, 1, int32_t>), dim3(1), dim3(MG_SCAN_WG), 0, st, a.blk, L.nb, a.blk + L.nb);
   CHECK_LAUNCH();
   hipLaunchKernelGGL(dbscan_rank_kernel, grid, wg, 0, st, a);
   CHECK_LAUNCH();
@@ -770,7 +691,9 @@ int objnerf_mask_affinity(const objnerf_affinity_args* a, void* ws, size_t ws_by
   CHECK_LAUNCH();
   hipLaunchKernelGGL(edge_count_kernel, dim3((unsigned)a->N), dim3(MG_WG), 0, st, a->N, (const float*)a->W, row_off);
   CHECK_LAUNCH();
-  hipLaunchKernelGGL(scan64_kernel, dim3(1), dim3(MG_SCAN_WG), 0, st, (int64_t)a->N, row_off);
+  // row_off[0 .. N) -> exclusive offsets, row_off[N] = the number of edges
+  hipLaunchKernelGGL((wg_scan_kernel<MG_SCAN_WG, 1, int64_t>), dim3(1), dim3(MG_SCAN_WG), 0, st, row_off, (int64_t)a->N,
+                     row_off + a->N);
   CHECK_LAUNCH();
   return OBJNERF_OK;
 }

@@ -6,7 +6,7 @@
 //   mc_count_kernel   one thread per lattice point p (the last axis on the lanes): the 3-bit mask of the +axis edges
 //                     p owns that cross the level, and the triangle count of the cell whose lowest corner is p; each
 //                     256-thread workgroup writes its two totals (int64 [nb][2]);
-//   mc_scan_kernel    one workgroup turns those totals into exclusive offsets and writes V, F;
+//   wg_scan_kernel    (objnerf_wg.h) one workgroup turns those totals into exclusive offsets and writes V, F;
 //   mc_verts_kernel   recomputes the mask, the intra-workgroup prefix (wave ballots + 4 LDS slots), writes the
 //                     vertices and normals and stores (local vertex base << 3 | mask) per point (uint16 [d^3]);
 //   mc_faces_kernel   recomputes the case and the prefix of the triangle counts; a triangle's vertex on cell edge e
@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
-#include "../../include/objnerf_hip.h"
+#include "objnerf_wg.h"
 
 namespace mc_host {
 #define OBJNERF_MC_QUAL static const
@@ -36,12 +36,9 @@ namespace mc_dev {
 
 namespace {
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH; } while (0)
-
 constexpr int MC_WG = 256;                 // points (and cells) per workgroup: 4 waves
 constexpr int MC_SCAN_WG = 1024;
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline long mc_blocks(long n) { return (n + MC_WG - 1) / MC_WG; }
 
 // corner c's linear offset from the cell's lowest point: (c & 1) d^2 + ((c >> 1) & 1) d + ((c >> 2) & 1)
@@ -72,27 +69,18 @@ __device__ __forceinline__ int cell_case(const float* __restrict__ vol, const lo
   return c;
 }
 
-// exclusive prefix over the workgroup of a value of at most 3 bits, and the workgroup total (wave64 ballots)
-__device__ __forceinline__ int wg_prefix3(const int v, int* __restrict__ wsum, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long lt = (1ull << lane) - 1ull;
+// exclusive prefix over the workgroup of a value of at most 3 bits, and the workgroup total: a ballot per bit into
+// objnerf_wg.h's halves, one barrier.  (wg_exclusive's integer form, a wave scan, measured 7 - 8 % slower on each of
+// the three kernels below: profiles/wg_prims_refactor.txt.)
+__device__ __forceinline__ int wg_prefix3(const int v, int* wsum, int& total) {
   int pre = 0, tot = 0;
 #pragma unroll
   for (int b = 0; b < 3; ++b) {
     const unsigned long long bal = __ballot((v >> b) & 1);
-    pre += __popcll(bal & lt) << b;
+    pre += wave_rank(bal) << b;
     tot += __popcll(bal) << b;
   }
-  if (lane == 0) wsum[wave] = tot;
-  __syncthreads();
-  int off = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < MC_WG / 64; ++w) {
-    off += w < wave ? wsum[w] : 0;
-    total += wsum[w];
-  }
-  return off + pre;
+  return wg_fold<MC_WG>((threadIdx.x & 63) == 0, tot, wsum, total) + pre;
 }
 
 __device__ __forceinline__ void point_coords(const long p, const int d, int& i, int& j, int& k) {
@@ -120,44 +108,6 @@ __global__ void __launch_bounds__(MC_WG) mc_count_kernel(const float* __restrict
   if (threadIdx.x == 0) {
     blk[2 * blockIdx.x] = tv;
     blk[2 * blockIdx.x + 1] = tf;
-  }
-}
-
-// one workgroup: blk [nb][2] totals -> exclusive offsets; counts[0] = V, counts[1] = F.  Each thread walks a contiguous
-// chunk of nb / 1024 totals (64 at 256^3, 4096 at 1024^3, uncoalesced across threads): ~0.12 of the 0.45 ms at 256^3,
-// and the first thing to make multi-workgroup if larger grids matter.
-__global__ void __launch_bounds__(MC_SCAN_WG) mc_scan_kernel(long nb, long long* __restrict__ blk,
-                                                             long long* __restrict__ counts) {
-  __shared__ long long sv[MC_SCAN_WG], sf[MC_SCAN_WG];
-  const int t = threadIdx.x;
-  const long chunk = (nb + MC_SCAN_WG - 1) / MC_SCAN_WG;
-  const long b0 = (long)t * chunk, b1 = b0 + chunk < nb ? b0 + chunk : nb;
-  long long v = 0, f = 0;
-  for (long b = b0; b < b1; ++b) {
-    v += blk[2 * b];
-    f += blk[2 * b + 1];
-  }
-  sv[t] = v;
-  sf[t] = f;
-  __syncthreads();
-  for (int s = 1; s < MC_SCAN_WG; s <<= 1) {       // Hillis-Steele inclusive scan
-    const long long av = t >= s ? sv[t - s] : 0, af = t >= s ? sf[t - s] : 0;
-    __syncthreads();
-    sv[t] += av;
-    sf[t] += af;
-    __syncthreads();
-  }
-  long long ov = sv[t] - v, of = sf[t] - f;
-  for (long b = b0; b < b1; ++b) {
-    const long long cv = blk[2 * b], cf = blk[2 * b + 1];
-    blk[2 * b] = ov;
-    blk[2 * b + 1] = of;
-    ov += cv;
-    of += cf;
-  }
-  if (t == MC_SCAN_WG - 1) {
-    counts[0] = sv[t];
-    counts[1] = sf[t];
   }
 }
 
@@ -273,8 +223,10 @@ int objnerf_mc_count(int32_t dim, float level, const float* vol, void* ws, size_
   long long* blk = (long long*)ws;
   hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)nb), dim3(MC_WG), 0, (hipStream_t)stream, vol, dim, level, n, blk);
   CHECK_LAUNCH();
-  hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(MC_SCAN_WG), 0, (hipStream_t)stream, nb, blk,
-                     (long long*)out_counts);
+  // one workgroup over nb / 4096 tiles (16 at 256^3, 1024 at 1024^3): the first thing to make multi-workgroup if
+  // larger grids matter
+  hipLaunchKernelGGL((wg_scan_kernel<MC_SCAN_WG, 2, long long>), dim3(1), dim3(MC_SCAN_WG), 0, (hipStream_t)stream, blk,
+                     (int64_t)nb, (long long*)out_counts);
   CHECK_LAUNCH();
   return OBJNERF_OK;
 }

@@ -4,7 +4,7 @@
 // rounds where the reference's separate ATen ops round; fused multiply-adds are written as fmaf.
 #include "objnerf_device.h"
 #include "objnerf_philox.h"
-#include "../../include/objnerf_hip.h"
+#include "objnerf_wg.h"
 #include "objnerf_generic.h"
 
 namespace {
@@ -741,7 +741,6 @@ __global__ void sample_prepare_kernel(const objnerf_sample_args a, const uint8_t
 
 }  // namespace
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH; } while (0)
 // a stale non-sticky error of another HIP user of this thread (e.g. hipErrorNotReady from event polling)
 // must not be mistaken for a launch failure
 #define CLEAR_STALE() (void)hipGetLastError()

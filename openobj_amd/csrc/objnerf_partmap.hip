@@ -9,11 +9,10 @@
 // Both clamp what they read into the table; plain stores, no atomics; two calls write the same bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/objnerf_hip.h"
+#include "objnerf_wg.h"
 
 namespace {
 
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH; } while (0)
 #define CLEAR_STALE() (void)hipGetLastError()
 
 constexpr int PM_WG = 256;

@@ -24,13 +24,9 @@
 #include <stdint.h>
 #include <math.h>
 #include <algorithm>
-#include "../../include/objnerf_hip.h"
+#include "objnerf_wg.h"
 
 namespace {
-
-#define CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH; } while (0)
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int PJ_WG = 256;                      // 4 waves
 constexpr int PJ_RB = 4;                        // 16-row blocks per wave and pass
@@ -46,9 +42,7 @@ constexpr int SC_TARGET = 1024;
 constexpr int SC_MAX_SPLIT = 16;
 constexpr int CL_WG = 256;
 
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // workgroups per segment: enough in total to fill the GPU, never more passes than rows
 inline int pj_split(int S, int64_t V) {
@@ -65,21 +59,6 @@ __device__ __forceinline__ int64_t seg_at(const int64_t* off, int s, int64_t V) 
 }
 
 // ------------------------------------------------------------------------------------------------ projection
-template <bool VEC>
-__device__ __forceinline__ float4 load_f4(const float* __restrict__ p, const int k0, const int D, const bool ok) {
-  float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (!ok) return f;
-  if (VEC) {
-    if (k0 < D) f = *(const float4*)(p + k0);           // D % 4 == 0: the whole float4 is in the row
-  } else {
-    if (k0 < D) f.x = p[k0];
-    if (k0 + 1 < D) f.y = p[k0 + 1];
-    if (k0 + 2 < D) f.z = p[k0 + 2];
-    if (k0 + 3 < D) f.w = p[k0 + 3];
-  }
-  return f;
-}
-
 // NCH: 16-column chunks the LDS copy of W holds (D <= 16 NCH)
 template <int NCH, bool VEC>
 __global__ void __launch_bounds__(PJ_WG) project_kernel(const objnerf_project_args a, float* __restrict__ part) {
@@ -151,7 +130,7 @@ __global__ void __launch_bounds__(PJ_WG) project_kernel(const objnerf_project_ar
       const int k0 = 16 * c + 4 * g;
       float4 f[PJ_RB];
 #pragma unroll
-      for (int b = 0; b < PJ_RB; ++b) f[b] = load_f4<VEC>(rp[b], k0, D, rv[b]);
+      for (int b = 0; b < PJ_RB; ++b) f[b] = load_row4<VEC>(rp[b], k0, D, rv[b]);
 #pragma unroll
       for (int b = 0; b < PJ_RB; ++b) {
         if (cosine) {
@@ -284,14 +263,14 @@ __global__ void __launch_bounds__(256) moments_scatter_kernel(const objnerf_mome
       const int64_t row = kb + rr + 16 * h;
       const bool ok = row < hi;
       const float* p = a.feat + (ok ? row : r0) * a.row_stride;
-      const float4 fa = load_f4<VEC>(p, ca, D, ok);       // zero past D and past the chunk: adds nothing
+      const float4 fa = load_row4<VEC>(p, ca, D, ok);       // zero past D and past the chunk: adds nothing
       float* da = sa[rr + 16 * h] + cc;
       da[0] = ok && ca < D ? fa.x - ma[0] : 0.f;
       da[1] = ok && ca + 1 < D ? fa.y - ma[1] : 0.f;
       da[2] = ok && ca + 2 < D ? fa.z - ma[2] : 0.f;
       da[3] = ok && ca + 3 < D ? fa.w - ma[3] : 0.f;
       if (!diag) {
-        const float4 fb = load_f4<VEC>(p, cb, D, ok);
+        const float4 fb = load_row4<VEC>(p, cb, D, ok);
         float* db = sb[rr + 16 * h] + cc;
         db[0] = ok && cb < D ? fb.x - mb[0] : 0.f;
         db[1] = ok && cb + 1 < D ? fb.y - mb[1] : 0.f;

@@ -17,7 +17,7 @@
 #include "objnerf_mlp32.h"
 #include "objnerf_train_common.h"
 #include "objnerf_generic.h"
-#include "../../include/objnerf_hip.h"
+#include "objnerf_wg.h"
 
 using namespace obj32;
 using namespace objtrain;
@@ -599,8 +599,6 @@ int num_cu() {
   }
   return g_num_cu;
 }
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int eval_launch(const objnerf_net* net, int32_t K, int64_t N, const float* params, int64_t p_stride,
                 const float* scale, const float* pts, const float* emb, float* out_alpha, float* out_color,

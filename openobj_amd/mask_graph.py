@@ -224,16 +224,8 @@ def voxel_down(pts: torch.Tensor, seg_off, voxel: float):
         raise ops.ObjnerfError("voxel_down: a cloud spans more than 2^42 voxels")
     lin = (seg << 42) | (ix + nx[seg] * (iy + ny[seg] * iz))
     skeys, perm = torch.sort(lin, stable=True)                 # equal keys keep the points' order
-    lib = ops.lib()
-    hws = torch.empty(int(lib.objnerf_voxel_heads_workspace_bytes(n)) // 8, dtype=torch.int64, device=dev)
-    ops.check(lib.objnerf_voxel_heads(n, skeys.data_ptr(), hws.data_ptr(), ops._stream()), "objnerf_voxel_heads")
-    V = int(hws[-1].item())
-    cen = torch.empty(V, 3, dtype=torch.float64, device=dev)
-    vkeys = torch.empty(V, dtype=torch.int64, device=dev)
-    first = torch.full((S,), -1, dtype=torch.int64, device=dev)
-    ops.check(lib.objnerf_voxel_centroids(n, skeys.data_ptr(), perm.data_ptr(), pts.contiguous().data_ptr(), hws.data_ptr(),
-                                          V, cen.data_ptr(), vkeys.data_ptr(), first.data_ptr(), ops._stream()),
-              "objnerf_voxel_centroids")
+    cen, _, first = ops.run_centroids(skeys, perm, pts, S)
+    V = int(cen.shape[0])
     first_h = first.cpu().numpy()
     new_off = np.full(S + 1, V, np.int64)
     for s in range(S - 1, -1, -1):                             # an empty cloud starts where the next one does

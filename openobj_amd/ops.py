@@ -1064,6 +1064,24 @@ def marching_cubes(volume: torch.Tensor, level: float = 0.5, gradient_direction:
     return verts, faces, normals
 
 
+def run_centroids(skeys: torch.Tensor, perm: torch.Tensor, pts: torch.Tensor, n_groups: int):
+    """Centroids of the runs of equal keys in skeys (int64 [n], stable-sorted; perm the sort's permutation of the rows
+    of pts fp64 [n, 3]): objnerf_voxel_heads, one read-back of the run count V, objnerf_voxel_centroids
+    -> (centroids fp64 [V, 3] = the in-order fp64 sum of a run's points / their count, keys int64 [V] without the
+    group bits (key >> 42), first int64 [n_groups] = the first run of every group, -1 for a group without points)."""
+    n, dev = int(skeys.numel()), skeys.device
+    pts = _req(pts, torch.float64, "pts")
+    hws = torch.empty(int(lib().objnerf_voxel_heads_workspace_bytes(n)) // 8, dtype=torch.int64, device=dev)
+    check(lib().objnerf_voxel_heads(n, _ptr(skeys), _ptr(hws), _stream()), "objnerf_voxel_heads")
+    V = int(hws[-1].item())
+    cen = torch.empty(V, 3, dtype=torch.float64, device=dev)
+    vkeys = torch.empty(V, dtype=torch.int64, device=dev)
+    first = torch.full((n_groups,), -1, dtype=torch.int64, device=dev)
+    check(lib().objnerf_voxel_centroids(n, _ptr(skeys), _ptr(perm), _ptr(pts), _ptr(hws), V, _ptr(cen), _ptr(vkeys),
+                                        _ptr(first), _stream()), "objnerf_voxel_centroids")
+    return cen, vkeys, first
+
+
 def objects_voxels(objects, intrinsics=None, voxel: float = 0.05, **kw):
     """Voxel-down-sampled keyframe point clouds of sceneObjects (vmap.py:303-320) -> per object (voxel indices int64
     [n,3], centroids fp64 [n,3]); objnerf_voxel_scan / _emit / _heads / _centroids (openobj_amd/bounds.py)."""

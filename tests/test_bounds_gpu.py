@@ -76,6 +76,60 @@ def test_voxel_centroids_match_the_statement(dev):
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
+def _run_lengths(rs, m):
+    """Seeded run lengths 1 .. 7 that sum to m (the last one cut to fit)."""
+    ln = rs.randint(1, 8, size=m)
+    ln = ln[:int(np.searchsorted(np.cumsum(ln), m)) + 1]
+    ln[-1] -= ln.sum() - m
+    return ln
+
+
+@pytest.mark.parametrize("tile", [1024, 4096])
+def test_heads_scan_carries_across_tiles(dev, tile):
+    """objnerf_voxel_heads + objnerf_voxel_centroids called directly on tile * 1024 + 1029 sorted keys: tile + 2 head
+    blocks of 1024 keys, so a one-workgroup scan of the block counts in tiles of `tile` elements carries from its first
+    tile into a second (4096 = objnerf_wg.h's 1024 threads x 4 elements; 1024 = a tile of one element a thread).
+    One run straddles a block boundary (keys 1022 .. 1025), one the tile boundary (keys 1024 tile - 2 .. + 2).
+    Integer coordinates: the fp64 sums are exact, every output is compared bit for bit."""
+    from openobj_amd._lib import check, lib
+    rs = np.random.RandomState(7)
+    B, n = 1024, tile * 1024 + 1029
+    t0 = tile * B - 2
+    ln = np.concatenate([_run_lengths(rs, 1022), [4], _run_lengths(rs, t0 - 1026), [5], _run_lengths(rs, n - t0 - 5)])
+    assert ln.sum() == n and ln.min() >= 1 and ln.max() <= 7
+    V = len(ln)
+    start = np.concatenate([[0], np.cumsum(ln)[:-1]])
+    assert 1022 in start and t0 in start
+    local = np.cumsum(rs.randint(1, 4, size=V)).astype(np.int64)            # ascending voxel keys with gaps
+    group = np.repeat(np.array([0, 2, 3], np.int64), [V // 3, V // 3, V - 2 * (V // 3)])    # group 1 has no key
+    keys = np.repeat((group << 42) | local, ln)
+    pts = rs.randint(-8, 9, size=(n, 3)).astype(np.float64)
+    head = np.zeros(n, np.int64)
+    head[start] = 1
+    nb = (n + B - 1) // B
+    blk = np.add.reduceat(head, np.arange(0, n, B))
+    assert nb == tile + 2 and blk.sum() == V
+    keys_d, pts_d = torch.from_numpy(keys).to(dev), torch.from_numpy(pts).to(dev)
+    perm_d = torch.arange(n, dtype=torch.int64, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+    assert int(lib().objnerf_voxel_heads_workspace_bytes(n)) == 8 * (nb + 1)
+    ws = torch.full((nb + 1,), -1, dtype=torch.int64, device=dev)
+    check(lib().objnerf_voxel_heads(n, keys_d.data_ptr(), ws.data_ptr(), st), "objnerf_voxel_heads")
+    ws_h = ws.cpu().numpy()
+    assert np.array_equal(ws_h[:nb], np.cumsum(blk) - blk)
+    assert ws_h[nb] == V
+    cen = torch.empty(V, 3, dtype=torch.float64, device=dev)
+    vkeys = torch.empty(V, dtype=torch.int64, device=dev)
+    first = torch.full((4,), -1, dtype=torch.int64, device=dev)
+    check(lib().objnerf_voxel_centroids(n, keys_d.data_ptr(), perm_d.data_ptr(), pts_d.data_ptr(), ws.data_ptr(), V,
+                                        cen.data_ptr(), vkeys.data_ptr(), first.data_ptr(), st), "objnerf_voxel_centroids")
+    uniq = np.unique(keys)
+    assert np.array_equal((group << 42) | vkeys.cpu().numpy(), uniq) and np.array_equal(uniq & ((1 << 42) - 1), local)
+    want = np.add.reduceat(pts, start, axis=0) / ln[:, None].astype(np.float64)
+    assert np.array_equal(cen.cpu().numpy(), want)
+    assert first.cpu().numpy().tolist() == [0, -1, V // 3, 2 * (V // 3)]
+
+
 def test_search_matches_the_statement(dev):
     rs = np.random.RandomState(1)
     clouds = [rs.randn(50, 3) * [0.5, 0.3, 0.1], rs.randn(600, 3) * [1.0, 0.4, 0.3], rs.randn(3000, 3)]

@@ -76,6 +76,28 @@ def test_dbscan_per_segment_min_points_and_determinism(dev):
         assert np.array_equal(got[off[s]:off[s + 1]], w[off[s]:off[s + 1]]), s
 
 
+@pytest.mark.parametrize("tile", [1024, 4096])
+def test_dbscan_root_ranks_carry_across_scan_tiles(dev, tile):
+    """256 tile + 300 points in one set: tile + 2 blocks of 256, so a one-workgroup scan of the blocks' root counts in
+    tiles of `tile` elements carries from its first tile into a second (4096 = objnerf_wg.h's 1024 threads x 4
+    elements; 1024 = a tile of one element a thread).  The points lie site by site in clusters of 4 (1 mm apart, the
+    sites 0.5 m = 10 eps apart) and min_points is 3: every point is core, cluster = site, and clusters are numbered by
+    their smallest core index (maskgraph_util.dbscan_labels' rule), so labels[i] == i // 4.  A second set of the same
+    call holds isolated points only: all noise, and the first set's labels do not move."""
+    n1 = 256 * tile + 300
+    site = np.arange(n1) // 4
+    pts1 = np.stack([site % 65, (site // 65) % 65, site // 4225], 1) * 0.5
+    pts1[:, 0] += (np.arange(n1) % 4) * 0.001
+    pts2 = _line(50, [100.0, 0.0, 0.0], step=1.0)
+    assert n1 // 4 < 65 ** 3
+    off = np.array([0, n1, n1 + 50])
+    got = ops.dbscan(torch.from_numpy(np.concatenate([pts1, pts2])).to(dev), off, EPS, 3).cpu().numpy()
+    assert np.array_equal(got[:n1], site)
+    assert (got[n1:] == -1).all()
+    alone = ops.dbscan(torch.from_numpy(pts1).to(dev), off[:2], EPS, 3).cpu().numpy()
+    assert np.array_equal(alone, got[:n1])
+
+
 def _line(n, start, step=0.0049):
     return np.asarray(start, np.float64) + np.arange(n)[:, None] * np.array([step, 0.0, 0.0])
 
@@ -252,8 +274,10 @@ def _affinity_fp64(boxes, cap, clip, color, b2, w):
 
 
 @pytest.mark.parametrize("N,dc,dl,F", [(1, 96, 384, 1), (15, 384, 512, 2), (16, 98, 96, 7), (17, 512, 384, 2),
-                                        (130, 384, 512, 7)])
+                                        (130, 384, 512, 7), (1030, 8, 8, 1)])
 def test_affinity_terms_sum_and_edges(dev, N, dc, dl, F):
+    """(N = 1030: more rows than 1024, a tile of one element a thread of the one-workgroup scan of the rows' edge
+    counts; test_edges_row_offsets_carry_across_scan_tiles passes objnerf_wg.h's tile of 4096.)"""
     boxes, cap, clip, color, b2 = _affinity_case(N, dc, dl, F, 40 + N)
     w = (0.35, 0.3, 0.3, 0.15, 0.2)
     (geo, tcap, tclip, tcol, g2), W64 = _affinity_fp64(boxes, cap, clip, color, b2, w)
@@ -287,6 +311,9 @@ def test_affinity_terms_sum_and_edges(dev, N, dc, dl, F):
     got_e = [(int(a), int(b)) for a, b in ij]
     assert got_e == sorted(got_e) and all(a < b for a, b in got_e)
     assert np.array_equal(ew, W[ij[:, 0], ij[:, 1]]) if len(ij) else True
+    with np.errstate(invalid="ignore"):                      # against the returned W itself: bit for bit, in order
+        e_w = np.argwhere(np.triu(W >= 1.0, 1))
+    assert np.array_equal(ij, e_w) and np.array_equal(ew, W[e_w[:, 0], e_w[:, 1]])
     skip = {(a, b) for a, b, nr in zip(iu, ju, near) if nr}
     assert set(got_e) - skip == want_e
     print("edges", len(got_e), "of", len(iu), "pairs; left out", int(near.sum()))
@@ -298,6 +325,22 @@ def test_affinity_terms_sum_and_edges(dev, N, dc, dl, F):
     assert np.nanmax(np.abs(W0 - W064), initial=0.0) <= bound
     again = ops.mask_affinity(t(boxes), t(cap), t(clip), t(color), t(b2), w)
     assert np.array_equal(again[0].cpu().numpy(), W, equal_nan=True) and np.array_equal(again[1].cpu().numpy(), ij)
+
+
+def test_edges_row_offsets_carry_across_scan_tiles(dev):
+    """N = 4100 masks: more rows than the 4096 elements of a tile of the one-workgroup scan of the rows' edge counts
+    (objnerf_wg.h: 1024 threads x 4), with edges on both sides of the boundary.  The edges and their order are those of
+    the returned W itself, bit for bit: np.argwhere(np.triu(W >= 1, 1)) is row-major."""
+    N = 4100
+    boxes, cap, clip, color, b2 = _affinity_case(N, 8, 8, 1, 40 + N)
+    cap[4097], clip[4097], color[4097], boxes[4097] = cap[4099], clip[4099], color[4099], boxes[4099]   # one object
+    t = lambda a: torch.from_numpy(a).to(dev)
+    W, ij, ew, _ = ops.mask_affinity(t(boxes), t(cap), t(clip), t(color), t(b2), (0.35, 0.3, 0.3, 0.15, 0.2))
+    W, ij, ew = W.cpu().numpy(), ij.cpu().numpy(), ew.cpu().numpy()
+    with np.errstate(invalid="ignore"):
+        e_w = np.argwhere(np.triu(W >= 1.0, 1))
+    assert (e_w[:, 0] < 4096).any() and (e_w[:, 0] >= 4096).any()
+    assert np.array_equal(ij, e_w) and np.array_equal(ew, W[e_w[:, 0], e_w[:, 1]])
 
 
 # ---------------------------------------------------------------------------------------------------------- end to end
