@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define OBJNERF_ABI_VERSION 12
+#define OBJNERF_ABI_VERSION 13
 
 #define OBJNERF_OK 0
 #define OBJNERF_EINVAL (-22)       /* bad shape / null pointer / unsupported size        */
@@ -137,6 +137,10 @@ typedef struct objnerf_kf_store {
   const uint8_t* rgbs; const float* depth; const float* t_wc; const float* bbox;
 } objnerf_kf_store;
 int objnerf_sample_rays_stacked(const objnerf_sample_args* a, int32_t K, const objnerf_kf_store* table, void* stream);
+/* ABI 13 -- the descriptor of a cropped keyframe store (described with its entry points at the end of this file) */
+typedef struct objnerf_kf_crops {
+  uint8_t* base; int64_t cap; int32_t* rect; float* t_wc; float* bbox;
+} objnerf_kf_crops;
 
 /* A4 alone (ABI 7): sceneObject.sample_3d_points(sampled_rgbs, sampled_depth, origins, dirs_w) (vmap.py:456-554) on
  * pixels the caller has already gathered: sampled_rgbs [n_frames][n_px][4] u8 (rgb + state, vmap.py:421),
@@ -528,6 +532,10 @@ typedef struct objnerf_voxel_args {
   int32_t K, F, W, H;
   double fx, fy, cx, cy, voxel;
   const objnerf_kf_store* table; const int32_t* n_keyframes; const double* camera_pose;
+  /* ABI 13 -- crops [K] (device) in place of table (which may then be NULL): the objects' cropped keyframe stores.  Scan
+   * and emit read only the pixels inside each slot's rect, a tile that does not meet the rect is not loaded at all; the
+   * points, their order and every output are those of the dense store with the same pixels. */
+  const objnerf_kf_crops* crops;
 } objnerf_voxel_args;
 size_t objnerf_voxel_workspace_bytes(int32_t K, int32_t F, int32_t W, int32_t H);
 int objnerf_voxel_scan(const objnerf_voxel_args* a, void* ws, size_t ws_bytes, int64_t* out_total, double* out_minmax,
@@ -735,6 +743,35 @@ int objnerf_mask_edges(int32_t N, const float* W, const int64_t* row_off, int64_
 int objnerf_part_index(int32_t M, int32_t Hp, int32_t Wp, const uint8_t* masks, int32_t* out, void* stream);
 int objnerf_part_dense(int64_t n_px, int32_t C, int32_t rows, const int32_t* index, const float* table, float* out,
                        void* stream);
+
+/* ABI 13 -- cropped keyframe stores (openobj_amd/kf_store.py): an object keeps, per keyframe slot, only the pixels of
+ * the slot's rect = the pixels the sampler can draw inside the slot's 2-D box (columns trunc(box[0]) .. trunc(box[1]),
+ * rows trunc(box[2]) .. trunc(box[3]), clipped to the image).  base: the object's byte arena of F slots of cap * 8
+ * bytes; slot s holds cap * 4 bytes of rgb + state followed by cap floats of depth, the crop row-major [cw][ch] (the
+ * transposed orientation of the dense store): pixel (iw, ih) of the image is element (iw - x0) * ch + (ih - y0).
+ * rect [F][4] int32 = {x0, y0, cw, ch} (cw * ch <= cap), t_wc [F][4][4] and bbox [F][4] as in objnerf_kf_store.
+ *
+ * objnerf_ingest_frame_crops: objnerf_ingest_frame for cropped stores, one launch for the K visible objects.  The
+ * state byte of every (pixel, object) is computed as there; only the pixels inside items[k].rect are written, with
+ * rect, pose and box of the slot.  A pixel OUTSIDE the rect whose state is 1 adds 1 to outside[k] (device int32 [K],
+ * never cleared here: the caller keeps it across frames) -- such a pixel is lost to get_bound, the caller's box was
+ * narrower than the instance.  The caller guarantees rect inside the image and rect[2] * rect[3] <= store.cap
+ * (EINVAL is returned for what can be checked on the host: null pointers, sizes, K).
+ *
+ * objnerf_sample_rays_crops: objnerf_sample_rays_stacked reading cropped stores: same arguments, same draws, same
+ * outputs stacked [K][...] (K = 1: the layouts of objnerf_sample_rays).  A pixel index outside the slot's rect (only
+ * possible when the caller changed the box after ingest) is clamped into it; ray directions and the part-feature
+ * gather use the image coordinates. */
+typedef struct objnerf_ingest_crop_item {
+  objnerf_kf_crops store;
+  int32_t slot, obj_id;
+  float box[4];
+  int32_t rect[4];
+} objnerf_ingest_crop_item;
+int objnerf_ingest_frame_crops(int32_t W, int32_t H, const uint8_t* rgb, const float* depth, const int32_t* inst,
+                               const float* t_wc, int32_t K, const objnerf_ingest_crop_item* items, int32_t* outside,
+                               void* stream);
+int objnerf_sample_rays_crops(const objnerf_sample_args* a, int32_t K, const objnerf_kf_crops* table, void* stream);
 
 #ifdef __cplusplus
 }

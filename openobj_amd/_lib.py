@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OBJNERF_LIB") or os.path.join(_HERE, "csrc", "libobjnerf_hip.so")   # OBJNERF_LIB: diagnostic builds
 
 OBJNERF_N_TENSORS = 19
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class ObjnerfError(RuntimeError):
@@ -102,10 +102,21 @@ class KfStore(C.Structure):
     _fields_ = [("rgbs", C.c_void_p), ("depth", C.c_void_p), ("t_wc", C.c_void_p), ("bbox", C.c_void_p)]
 
 
+class KfCrops(C.Structure):        # ABI 13: objnerf_kf_crops, a cropped keyframe store (kf_store.KeyframeCropStore)
+    _fields_ = [("base", C.c_void_p), ("cap", C.c_int64), ("rect", C.c_void_p), ("t_wc", C.c_void_p),
+                ("bbox", C.c_void_p)]
+
+
+class IngestCropItem(C.Structure):
+    _fields_ = [("store", KfCrops), ("slot", C.c_int32), ("obj_id", C.c_int32), ("box", C.c_float * 4),
+                ("rect", C.c_int32 * 4)]
+
+
 class VoxelArgs(C.Structure):
     _fields_ = [("K", C.c_int32), ("F", C.c_int32), ("W", C.c_int32), ("H", C.c_int32),
                 ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("voxel", C.c_double),
-                ("table", C.c_void_p), ("n_keyframes", C.c_void_p), ("camera_pose", C.c_void_p)]
+                ("table", C.c_void_p), ("n_keyframes", C.c_void_p), ("camera_pose", C.c_void_p),
+                ("crops", C.c_void_p)]      # ABI 13 (trailing; None = the dense tables)
 
 
 class ObbArgs(C.Structure):
@@ -273,6 +284,10 @@ SIGNATURES = {
     # ABI 12: compact part-level feature maps (objnerf_partmap.hip)
     "objnerf_part_index": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "objnerf_part_dense": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ABI 13: cropped keyframe stores (objnerf_misc.hip, objnerf_bounds.hip)
+    "objnerf_ingest_frame_crops": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_sample_rays_crops": (C.c_int, [C.POINTER(SampleArgs), C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

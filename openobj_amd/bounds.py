@@ -81,9 +81,11 @@ def objects_voxels(objects, intrinsic_open3d=None, voxel: float = 0.05, budget: 
     out: List[Optional[Tuple[np.ndarray, np.ndarray]]] = [None] * len(objects)
     groups = {}
     for i, o in enumerate(objects):
-        key = (o.keyframe_buffer_size, o.frames_width, o.frames_height, intrinsics_of(intrinsic_open3d, o))
+        # (dense and cropped keyframe stores go to separate launches: they are read through different descriptors)
+        key = (o.keyframe_buffer_size, o.frames_width, o.frames_height, intrinsics_of(intrinsic_open3d, o),
+               getattr(o, "crops", None) is not None)
         groups.setdefault(key, []).append(i)
-    for (F, W, H, intr), idx in groups.items():
+    for (F, W, H, intr, _), idx in groups.items():
         res = _voxels_group([objects[i] for i in idx], F, W, H, intr, float(voxel), int(budget), stats)
         for i, r in zip(idx, res):
             out[i] = r
@@ -106,7 +108,9 @@ def _voxels_group(objs, F, W, H, intr, voxel, budget, stats):
     poses_d = torch.from_numpy(poses).to(dev)
     nk_d = torch.tensor(nk, dtype=torch.int32).to(dev)
     fx, fy, cx, cy = intr
-    a = VoxelArgs(K, F, W, H, fx, fy, cx, cy, voxel, table.data_ptr(), nk_d.data_ptr(), poses_d.data_ptr())
+    cropped = table.shape[1] == 5                   # ops.keyframe_table of KeyframeCropStores: objnerf_kf_crops rows
+    a = VoxelArgs(K, F, W, H, fx, fy, cx, cy, voxel, None if cropped else table.data_ptr(), nk_d.data_ptr(),
+                  poses_d.data_ptr(), table.data_ptr() if cropped else None)
     nbytes = int(lib().objnerf_voxel_workspace_bytes(K, F, W, H))
     if nbytes == 0:
         raise ObjnerfError("objnerf_voxel_workspace_bytes returned 0")
@@ -123,7 +127,8 @@ def _voxels_group(objs, F, W, H, intr, voxel, budget, stats):
     tot = total.cpu().numpy()                                                 # the scan's one host sync
     if ev:
         stats["scan_ms"] = stats.get("scan_ms", 0.0) + ev[0].elapsed_time(ev[1])
-        stats["scan_bytes"] = stats.get("scan_bytes", 0) + sum(nk) * W * H * 8     # depth + the rgbs line of the state
+        px = sum(int(o.crops.rect_host[:n, 2:].prod(axis=1).sum()) for o, n in zip(objs, nk)) if cropped else sum(nk) * W * H
+        stats["scan_bytes"] = stats.get("scan_bytes", 0) + px * 8                  # depth + the rgbs line of the state
         stats["points"] = stats.get("points", 0) + int(tot.sum())
     mm = minmax.cpu().numpy()
     vmin = np.zeros((K, 3), np.float64)

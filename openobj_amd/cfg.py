@@ -45,6 +45,13 @@ _PLAIN = {
     **{name: ("vis", name) for name in ("vis_device", "bg_id", "n_vis_iter", "eps_fine_vis", "n_bins_fine_vis",
                                          "live_voxel_size", "grid_dim")},
 }
+# Keys the reference does not have: attribute -> (section, key, default, accepted values).  Optional, so every config
+# written for the reference reads as before.
+KEYFRAME_STORES = ("dense", "crop")
+_OPTIONAL = {
+    # "dense": full frames per keyframe slot (the reference's layout); "crop": only each slot's 2-D box (kf_store.py)
+    "keyframe_store": ("model", "keyframe_store", "dense", KEYFRAME_STORES),
+}
 _DISTORTION_KEYS = ("k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6")
 
 
@@ -58,6 +65,11 @@ class Config:
         for attr, (section, key, *conv) in _PLAIN.items():
             value = config[section][key]
             setattr(self, attr, conv[0](value) if conv else value)
+        for attr, (section, key, default, accepted) in _OPTIONAL.items():
+            value = config.get(section, {}).get(key, default)
+            if value not in accepted:
+                raise ValueError("%s.%s = %r: one of %s expected" % (section, key, value, list(accepted)))
+            setattr(self, attr, value)
         self.obj_id = -1
         self.depth_scale = 1 / config["trainer"]["scale"]
         self.min_depth, self.max_depth = config["render"]["depth_range"][0], config["render"]["depth_range"][1]

@@ -99,13 +99,61 @@ __device__ __forceinline__ void load_column(const objnerf_kf_store& s, const lon
   }
 }
 
+// The same column of a cropped store (ABI 13): slot kf holds the pixels of its rect {x0, y0, cw, ch} only, pixel (x, y) at
+// element (x - x0) * ch + (y - y0); every other pixel of the image reads as "not this object" without touching memory.
+// The element index is also held below the slot's capacity, so that a rect the caller corrupted cannot leave the arena.
+__device__ __forceinline__ void load_column(const objnerf_kf_crops& s, const long kf, const int x, const int y0,
+                                            const int W, const int H, float d[VX_BY], bool m[VX_BY]) {
+  const int4 rc = *(const int4*)(s.rect + kf * 4);
+  const uint8_t* sp = s.base + kf * s.cap * 8;
+  const float* dp = (const float*)(sp + s.cap * 4);
+  const int cx = x - rc.x;
+  const bool colin = cx >= 0 && cx < rc.z;
+#pragma unroll
+  for (int r = 0; r < VX_BY; ++r) {
+    const int cy = y0 + r - rc.y;
+    const long e = (long)cx * rc.w + cy;
+    const bool in = colin && y0 + r < H && cy >= 0 && cy < rc.w && e < s.cap;
+    d[r] = in ? dp[e] : 0.f;
+    m[r] = in && sp[4 * e + 3] == 1;
+  }
+}
+
+// the tile's rectangle of columns x .. x + VX_WG - 1, rows y0 .. y0 + VX_BY - 1 holds no pixel of slot kf's crop
+__device__ __forceinline__ bool tile_outside(const objnerf_kf_crops& s, const long kf, const int x_lo, const int y0) {
+  const int4 rc = *(const int4*)(s.rect + kf * 4);
+  return x_lo >= rc.x + rc.z || x_lo + VX_WG <= rc.x || y0 >= rc.y + rc.w || y0 + VX_BY <= rc.y;
+}
+
+// CROP: the objects' stores are a.crops (objnerf_kf_crops), else a.table (objnerf_kf_store)
+template <bool CROP> struct VxStore;
+template <> struct VxStore<false> {
+  typedef objnerf_kf_store type;
+  static __device__ __forceinline__ type of(const objnerf_voxel_args& a, const int k) { return a.table[k]; }
+};
+template <> struct VxStore<true> {
+  typedef objnerf_kf_crops type;
+  static __device__ __forceinline__ type of(const objnerf_voxel_args& a, const int k) { return a.crops[k]; }
+};
+
+template <bool CROP>
 __global__ void __launch_bounds__(VX_WG) voxel_scan_kernel(const objnerf_voxel_args a, char* __restrict__ ws,
                                                            const VxLayout L) {
   const int k = blockIdx.z, kf = blockIdx.y;
   if (kf >= a.n_keyframes[k]) return;                     // only the live slots are read
   const int tile = blockIdx.x, xc = tile % L.nxc, yb = tile / L.nxc;
   const int x = xc * VX_WG + threadIdx.x, y0 = yb * VX_BY;
-  const objnerf_kf_store s = a.table[k];
+  const typename VxStore<CROP>::type s = VxStore<CROP>::of(a, k);
+  if constexpr (CROP) {
+    if (tile_outside(s, kf, xc * VX_WG, y0)) {            // nothing of the crop here: no points, and nothing is loaded
+      int32_t* counts = (int32_t*)(ws + L.counts) + (long)k * L.rows;
+      if (threadIdx.x < VX_BY && y0 + threadIdx.x < a.H) counts[((long)kf * a.H + y0 + threadIdx.x) * L.nxc + xc] = 0;
+      if (threadIdx.x < 6)
+        ((double*)(ws + L.minmax))[(((long)k * a.F + kf) * L.ntiles + tile) * 6 + threadIdx.x] =
+            threadIdx.x < 3 ? INFINITY : -INFINITY;
+      return;
+    }
+  }
   const double* P = a.camera_pose + ((long)k * a.F + kf) * 16;
   float d[VX_BY];
   bool m[VX_BY];
@@ -172,6 +220,7 @@ __global__ void __launch_bounds__(VX_SCAN_WG) voxel_finish_kernel(const objnerf_
   }
 }
 
+template <bool CROP>
 __global__ void __launch_bounds__(VX_WG) voxel_emit_kernel(const objnerf_voxel_args a, const char* __restrict__ ws,
                                                            const VxLayout L, const int k0, const int64_t* __restrict__ base,
                                                            const double* __restrict__ vmin,
@@ -186,7 +235,7 @@ __global__ void __launch_bounds__(VX_WG) voxel_emit_kernel(const objnerf_voxel_a
   const int r_t = threadIdx.x;
   const bool any = r_t < VX_BY && y0 + r_t < a.H && counts[((long)kf * a.H + y0 + r_t) * L.nxc + xc] != 0;
   if (!__syncthreads_or(any)) return;                    // most tiles of a small object hold none of its pixels
-  const objnerf_kf_store s = a.table[k];
+  const typename VxStore<CROP>::type s = VxStore<CROP>::of(a, k);
   const double* P = a.camera_pose + ((long)k * a.F + kf) * 16;
   float d[VX_BY];
   bool m[VX_BY];
@@ -405,13 +454,15 @@ size_t objnerf_voxel_workspace_bytes(int32_t K, int32_t F, int32_t W, int32_t H)
 
 int objnerf_voxel_scan(const objnerf_voxel_args* a, void* ws, size_t ws_bytes, int64_t* out_total, double* out_minmax,
                        void* stream) {
-  if (!a || !ws || !out_total || !out_minmax || !a->table || !a->n_keyframes || !a->camera_pose) return OBJNERF_EINVAL;
+  if (!a || !ws || !out_total || !out_minmax || (!a->table && !a->crops) || !a->n_keyframes || !a->camera_pose)
+    return OBJNERF_EINVAL;
   if (a->K <= 0 || a->K > 65535 || a->F <= 0 || a->F > 65535 || a->W <= 0 || a->H <= 0 || !(a->voxel > 0.0))
     return OBJNERF_EINVAL;
   const VxLayout L = vx_layout(a->K, a->F, a->W, a->H);
   if (ws_bytes < L.total) return OBJNERF_EINVAL;
-  hipLaunchKernelGGL(voxel_scan_kernel, dim3((unsigned)L.ntiles, (unsigned)a->F, (unsigned)a->K), dim3(VX_WG), 0,
-                     (hipStream_t)stream, *a, (char*)ws, L);
+  hipLaunchKernelGGL(a->crops ? voxel_scan_kernel<true> : voxel_scan_kernel<false>,
+                     dim3((unsigned)L.ntiles, (unsigned)a->F, (unsigned)a->K), dim3(VX_WG), 0, (hipStream_t)stream, *a,
+                     (char*)ws, L);
   CHECK_LAUNCH();
   hipLaunchKernelGGL(voxel_finish_kernel, dim3((unsigned)a->K), dim3(VX_SCAN_WG), 0, (hipStream_t)stream, *a, (char*)ws,
                      L, out_total, out_minmax);
@@ -422,15 +473,17 @@ int objnerf_voxel_scan(const objnerf_voxel_args* a, void* ws, size_t ws_bytes, i
 int objnerf_voxel_emit(const objnerf_voxel_args* a, const void* ws, size_t ws_bytes, int32_t k0, int32_t k1,
                        const int64_t* base, const double* vmin, const int64_t* dims, int64_t n_points, double* out_pts,
                        int64_t* out_keys, void* stream) {
-  if (!a || !ws || !base || !vmin || !dims || !a->table || !a->n_keyframes || !a->camera_pose) return OBJNERF_EINVAL;
+  if (!a || !ws || !base || !vmin || !dims || (!a->table && !a->crops) || !a->n_keyframes || !a->camera_pose)
+    return OBJNERF_EINVAL;
   if (k0 < 0 || k1 > a->K || k1 <= k0 || k1 - k0 >= (1 << (63 - KEY_SHIFT)) || a->F > 65535 || a->W <= 0 || a->H <= 0)
     return OBJNERF_EINVAL;
   const VxLayout L = vx_layout(a->K, a->F, a->W, a->H);
   if (ws_bytes < L.total) return OBJNERF_EINVAL;
   if (n_points <= 0) return OBJNERF_OK;
   if (!out_pts || !out_keys) return OBJNERF_EINVAL;
-  hipLaunchKernelGGL(voxel_emit_kernel, dim3((unsigned)L.ntiles, (unsigned)a->F, (unsigned)(k1 - k0)), dim3(VX_WG), 0,
-                     (hipStream_t)stream, *a, (const char*)ws, L, k0, base, vmin, dims, n_points, out_pts, out_keys);
+  hipLaunchKernelGGL(a->crops ? voxel_emit_kernel<true> : voxel_emit_kernel<false>,
+                     dim3((unsigned)L.ntiles, (unsigned)a->F, (unsigned)(k1 - k0)), dim3(VX_WG), 0, (hipStream_t)stream, *a,
+                     (const char*)ws, L, k0, base, vmin, dims, n_points, out_pts, out_keys);
   CHECK_LAUNCH();
   return OBJNERF_OK;
 }

@@ -470,32 +470,81 @@ __global__ void rays_dirs_kernel(int W, int H, float fx, float fy, float cx, flo
 // ------------------------------------------------------------------------------------------------
 // vmap.py:386-554: pixel gather (pass 1, also the batch depth maximum) and z placement (pass 2).
 // ------------------------------------------------------------------------------------------------
+// object k of a stacked call: its slices of the stacked arrays
+__device__ __forceinline__ void sample_slices_of(objnerf_sample_args& b, const objnerf_sample_args& a, const int k) {
+  const long n = (long)a.n_frames * a.n_px, S = a.n_cam2surf + a.n_bins;
+  if (b.kf_ids) b.kf_ids += (long)k * a.n_frames;
+  if (b.u_w) { b.u_w += k * n; b.u_h += k * n; b.u += k * n * S; b.g += k * n * a.n_bins; }
+  if (b.kf_meta) b.kf_meta += 4 * k;
+  if (b.out_kf) b.out_kf += (long)k * a.n_frames;
+  if (b.out_px) b.out_px += k * n * 2;
+  if (b.out_origins) { b.out_origins += k * n * 3; b.out_dirs += k * n * 3; }
+  if (b.out_partfeat) { b.out_partfeat += k * n * b.pf_c; b.use_frame += (long)k * a.F; }
+  if (b.out_pts) b.out_pts += k * n * S * 3;
+  b.obj_index = a.obj_index + k;
+  b.out_rgb += k * n * 3; b.out_depth += k * n; b.out_valid += k * n; b.out_labels += k * n;
+  b.out_z += k * n * S;
+  b.max_depth_ws += k * (1 + 6 * n);
+}
+
 // object blockIdx.y of a stacked call: its keyframe store from the table, its slices of the stacked arrays
 __device__ __forceinline__ objnerf_sample_args sample_args_of(const objnerf_sample_args& a, const objnerf_kf_store* table,
                                                               const int k) {
   objnerf_sample_args b = a;
   if (table) {
     b.rgbs = table[k].rgbs; b.depth = table[k].depth; b.t_wc = table[k].t_wc; b.bbox = table[k].bbox;
-    const long n = (long)a.n_frames * a.n_px, S = a.n_cam2surf + a.n_bins;
-    if (b.kf_ids) b.kf_ids += (long)k * a.n_frames;
-    if (b.u_w) { b.u_w += k * n; b.u_h += k * n; b.u += k * n * S; b.g += k * n * a.n_bins; }
-    if (b.kf_meta) b.kf_meta += 4 * k;
-    if (b.out_kf) b.out_kf += (long)k * a.n_frames;
-    if (b.out_px) b.out_px += k * n * 2;
-    if (b.out_origins) { b.out_origins += k * n * 3; b.out_dirs += k * n * 3; }
-    if (b.out_partfeat) { b.out_partfeat += k * n * b.pf_c; b.use_frame += (long)k * a.F; }
-    if (b.out_pts) b.out_pts += k * n * S * 3;
-    b.obj_index = a.obj_index + k;
-    b.out_rgb += k * n * 3; b.out_depth += k * n; b.out_valid += k * n; b.out_labels += k * n;
-    b.out_z += k * n * S;
-    b.max_depth_ws += k * (1 + 6 * n);
+    sample_slices_of(b, a, k);
   }
   if (b.kf_meta) b.obj_index = b.kf_meta[3];      // the object's own random-stream id
   return b;
 }
 
-__global__ __launch_bounds__(256) void sample_gather_kernel(const objnerf_sample_args a_, const objnerf_kf_store* table) {
+// the same for a table of cropped stores (always a stacked call); pixels are then read through CropPixels
+__device__ __forceinline__ objnerf_sample_args sample_args_of(const objnerf_sample_args& a, const objnerf_kf_crops* table,
+                                                              const int k) {
+  objnerf_sample_args b = a;
+  b.rgbs = nullptr; b.depth = nullptr; b.t_wc = table[k].t_wc; b.bbox = table[k].bbox;
+  sample_slices_of(b, a, k);
+  if (b.kf_meta) b.obj_index = b.kf_meta[3];
+  return b;
+}
+
+// How the gather addresses pixel (iw, ih) of keyframe slot kf: the dense store [F][W][H] ...
+struct DensePixels {
+  typedef objnerf_kf_store table_t;
+  const uint8_t* rgbs; const float* depth; long W, H;
+  __device__ __forceinline__ DensePixels(const objnerf_sample_args& a, const table_t*, int)
+      : rgbs(a.rgbs), depth(a.depth), W(a.W), H(a.H) {}
+  __device__ __forceinline__ void at(const long kf, const long iw, const long ih, const uint8_t*& px, const float*& d) const {
+    const long pix = (kf * W + iw) * H + ih;
+    px = rgbs + pix * 4;
+    d = depth + pix;
+  }
+};
+
+// ... or the slot's crop [cw][ch] (rgb + state, then depth, cap pixels each); an index outside the rect is clamped into
+// it, and the element index into the slot's capacity: a rect that a caller corrupted cannot make the read leave the arena
+struct CropPixels {
+  typedef objnerf_kf_crops table_t;
+  const uint8_t* base; long cap; const int32_t* rect;
+  __device__ __forceinline__ CropPixels(const objnerf_sample_args&, const table_t* table, const int k)
+      : base(table[k].base), cap(table[k].cap), rect(table[k].rect) {}
+  __device__ __forceinline__ void at(const long kf, const long iw, const long ih, const uint8_t*& px, const float*& d) const {
+    const int4 r = *(const int4*)(rect + kf * 4);                  // x0, y0, cw, ch
+    const long cw = r.z, ch = r.w;
+    const long x = min(max(iw - r.x, 0l), cw - 1), y = min(max(ih - r.y, 0l), ch - 1);
+    const long e = min(max(x * ch + y, 0l), cap - 1);
+    const uint8_t* slot = base + kf * cap * 8;
+    px = slot + e * 4;
+    d = (const float*)(slot + cap * 4) + e;
+  }
+};
+
+template <class Pixels>
+__global__ __launch_bounds__(256) void sample_gather_kernel(const objnerf_sample_args a_,
+                                                            const typename Pixels::table_t* table) {
   const objnerf_sample_args a = sample_args_of(a_, table, blockIdx.y);
+  const Pixels pixels(a, table, blockIdx.y);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int n = a.n_frames * a.n_px;
   __shared__ long pf_row[256];                                   // source row of every ray of the block (part features)
@@ -531,11 +580,12 @@ __global__ __launch_bounds__(256) void sample_gather_kernel(const objnerf_sample
     const float fh = uh * (bb[3] - bb[2]) + bb[2];
     const long iw = (long)fw, ih = (long)fh;                       // .long() truncation (vmap.py:418-419)
     if (a.out_px) { a.out_px[2 * i] = (int)iw; a.out_px[2 * i + 1] = (int)ih; }
-    const long pix = (kf * a.W + iw) * a.H + ih;
-    const uint8_t* px = a.rgbs + pix * 4;
+    const uint8_t* px;
+    const float* dp;
+    pixels.at(kf, iw, ih, px, dp);
     a.out_rgb[i * 3] = px[0]; a.out_rgb[i * 3 + 1] = px[1]; a.out_rgb[i * 3 + 2] = px[2];
     a.out_labels[i] = px[3];
-    const float d = a.depth[pix];
+    const float d = *dp;
     a.out_depth[i] = d;
     atomicMax((int*)a.max_depth_ws, __float_as_int(fmaxf(d, 0.0f)));
     const float* dc = a.rays_dir_cache + (iw * a.H + ih) * 3;
@@ -596,6 +646,44 @@ __global__ void ingest_frame_kernel(int W, int H, const uint8_t* rgb, const floa
   it.depth[(long)it.slot * npx + p] = depth[p];
 }
 
+// The same into cropped stores (ABI 13): the state byte of every (pixel, object) as above, but only the pixels inside
+// the item's rect are written, element (iw - x0) * ch + (ih - y0) of the slot's crop; a "this object" pixel outside
+// the rect is counted (one atomic per wave that saw any).  The frame is stored transposed: p = iw * H + ih.
+__global__ __launch_bounds__(256) void ingest_frame_crops_kernel(int W, int H, const uint8_t* rgb, const float* depth,
+                                                                 const int32_t* inst, const float* t_wc,
+                                                                 const objnerf_ingest_crop_item* items, int32_t* outside) {
+  const objnerf_ingest_crop_item it = items[blockIdx.y];
+  const long npx = (long)W * H;
+  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (blockIdx.x == 0) {
+    if (threadIdx.x < 16) it.store.t_wc[(long)it.slot * 16 + threadIdx.x] = t_wc[threadIdx.x];
+    if (threadIdx.x < 4) {
+      it.store.bbox[(long)it.slot * 4 + threadIdx.x] = it.box[threadIdx.x];
+      it.store.rect[(long)it.slot * 4 + threadIdx.x] = it.rect[threadIdx.x];
+    }
+  }
+  bool lost = false;
+  if (p < npx) {
+    const int iw = (int)(p / H), ih = (int)(p % H);
+    const int x = iw - it.rect[0], y = ih - it.rect[1];
+    const int cw = it.rect[2], ch = it.rect[3];
+    const int id = inst[p];
+    const uint32_t state = id == it.obj_id ? 1u : (id == -1 ? 2u : 0u);      // train.py:201-203
+    const long e = (long)x * ch + y;
+    if (x >= 0 && x < cw && y >= 0 && y < ch && e < it.store.cap) {
+      const uint32_t px = (uint32_t)rgb[p * 3] | ((uint32_t)rgb[p * 3 + 1] << 8) | ((uint32_t)rgb[p * 3 + 2] << 16) |
+                          (state << 24);
+      uint8_t* slot = it.store.base + (long)it.slot * it.store.cap * 8;
+      reinterpret_cast<uint32_t*>(slot)[e] = px;
+      reinterpret_cast<float*>(slot + it.store.cap * 4)[e] = depth[p];
+    } else {
+      lost = state == 1u;
+    }
+  }
+  const unsigned long long b = __ballot(lost);
+  if (b != 0ull && (threadIdx.x & 63) == 0) atomicAdd(outside + blockIdx.y, __popcll(b));
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // Trainer.sample_points_bbox (trainer.py:130-198)
@@ -641,7 +729,8 @@ __global__ void box_points_kernel(long n, int n_bins, const float* origin, const
   for (int x = 0; x < 3; ++x) out_pts[idx * 3 + x] = origin[x] + dirs_W[r * 3 + x] * z;   // :176
 }
 
-__global__ void sample_place_kernel(const objnerf_sample_args a_, const objnerf_kf_store* table) {
+template <class Table>
+__global__ void sample_place_kernel(const objnerf_sample_args a_, const Table* table) {
   const objnerf_sample_args a = sample_args_of(a_, table, blockIdx.y);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int n = a.n_frames * a.n_px;
@@ -1005,9 +1094,11 @@ int objnerf_sample_rays(const objnerf_sample_args* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   // (max_depth_ws[0] = the batch depth maximum, then the world-frame origins / directions between the passes)
   (void)hipMemsetAsync(a->max_depth_ws, 0, sizeof(float), st);
-  hipLaunchKernelGGL(sample_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *a, (const objnerf_kf_store*)nullptr);
+  hipLaunchKernelGGL(sample_gather_kernel<DensePixels>, dim3((n + 255) / 256), dim3(256), 0, st, *a,
+                     (const objnerf_kf_store*)nullptr);
   CHECK_LAUNCH();
-  hipLaunchKernelGGL(sample_place_kernel, dim3((n + 255) / 256), dim3(256), 0, st, *a, (const objnerf_kf_store*)nullptr);
+  hipLaunchKernelGGL(sample_place_kernel<objnerf_kf_store>, dim3((n + 255) / 256), dim3(256), 0, st, *a,
+                     (const objnerf_kf_store*)nullptr);
   CHECK_LAUNCH();
   return OBJNERF_OK;
 }
@@ -1032,7 +1123,8 @@ int objnerf_sample_points(const objnerf_sample_args* a, const uint8_t* sampled_r
   hipLaunchKernelGGL(sample_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, st, b, sampled_rgbs, sampled_depth, origins,
                      dirs_w, origins_ws, dirs_ws);
   CHECK_LAUNCH();
-  hipLaunchKernelGGL(sample_place_kernel, dim3((n + 255) / 256), dim3(256), 0, st, b, (const objnerf_kf_store*)nullptr);
+  hipLaunchKernelGGL(sample_place_kernel<objnerf_kf_store>, dim3((n + 255) / 256), dim3(256), 0, st, b,
+                     (const objnerf_kf_store*)nullptr);
   CHECK_LAUNCH();
   return OBJNERF_OK;
 }
@@ -1056,9 +1148,36 @@ int objnerf_sample_rays_stacked(const objnerf_sample_args* a, int32_t K, const o
   // the K depth maxima sit (1 + 6 n) floats apart: clearing the whole scratch is one call
   (void)hipMemsetAsync(a->max_depth_ws, 0, (size_t)K * (1 + 6 * (size_t)n) * sizeof(float), st);
   const dim3 grid((n + 255) / 256, K);
-  hipLaunchKernelGGL(sample_gather_kernel, grid, dim3(256), 0, st, *a, table);
+  hipLaunchKernelGGL(sample_gather_kernel<DensePixels>, grid, dim3(256), 0, st, *a, table);
   CHECK_LAUNCH();
-  hipLaunchKernelGGL(sample_place_kernel, grid, dim3(256), 0, st, *a, table);
+  hipLaunchKernelGGL(sample_place_kernel<objnerf_kf_store>, grid, dim3(256), 0, st, *a, table);
+  CHECK_LAUNCH();
+  return OBJNERF_OK;
+}
+
+int objnerf_ingest_frame_crops(int32_t W, int32_t H, const uint8_t* rgb, const float* depth, const int32_t* inst,
+                               const float* t_wc, int32_t K, const objnerf_ingest_crop_item* items, int32_t* outside,
+                               void* stream) {
+  CLEAR_STALE();
+  if (W <= 0 || H <= 0 || K <= 0 || K > 65535 || !rgb || !depth || !inst || !t_wc || !items || !outside)
+    return OBJNERF_EINVAL;
+  const long npx = (long)W * H;
+  hipLaunchKernelGGL(ingest_frame_crops_kernel, dim3((unsigned)((npx + 255) / 256), K), dim3(256), 0, (hipStream_t)stream,
+                     W, H, rgb, depth, inst, t_wc, items, outside);
+  CHECK_LAUNCH();
+  return OBJNERF_OK;
+}
+
+int objnerf_sample_rays_crops(const objnerf_sample_args* a, int32_t K, const objnerf_kf_crops* table, void* stream) {
+  CLEAR_STALE();
+  if (!a || !table || K <= 0 || K > 65535 || !sample_args_ok(a)) return OBJNERF_EINVAL;
+  const int n = a->n_frames * a->n_px;
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipMemsetAsync(a->max_depth_ws, 0, (size_t)K * (1 + 6 * (size_t)n) * sizeof(float), st);
+  const dim3 grid((n + 255) / 256, K);
+  hipLaunchKernelGGL(sample_gather_kernel<CropPixels>, grid, dim3(256), 0, st, *a, table);
+  CHECK_LAUNCH();
+  hipLaunchKernelGGL(sample_place_kernel<objnerf_kf_crops>, grid, dim3(256), 0, st, *a, table);
   CHECK_LAUNCH();
   return OBJNERF_OK;
 }

@@ -74,6 +74,10 @@ class IncrementalMapper:
         self._side = None
         self.last_twc = None
         self.last_frame_id = None
+        # cfg.keyframe_store "crop": per object, the number of its pixels that fell outside its crop (device int32, in
+        # the order of _outside_ids; objnerf_ingest_frame_crops counts, check_crops() reads)
+        self._outside: Optional[torch.Tensor] = None
+        self._outside_ids: Dict[int, int] = {}        # object id -> its entry of _outside
 
     # ------------------------------------------------------------------ train.py:172-256
     def ingest(self, sample, frame_id: int) -> List[int]:
@@ -148,13 +152,64 @@ class IncrementalMapper:
             self.vis_dict[obj_id] = so
             created.append(obj_id)
         if writes:
-            # state map (1 this object / 2 unknown / 0 other, train.py:201-203) + rgb, depth, pose, box -> the slots
-            ops.ingest_frame(rgb, depth, inst, twc, [(so.keyframe_store(), slot, so.obj_id, box.tolist())
-                                                     for so, slot, box in writes])
+            # state map (1 this object / 2 unknown / 0 other, train.py:201-203) + rgb, depth, pose, box -> the slots:
+            # one launch for the dense stores, one for the cropped ones
+            dense = [(so.keyframe_store(), slot, so.obj_id, box.tolist()) for so, slot, box in writes if so.crops is None]
+            crops = [(so.crops, slot, so.obj_id, box.tolist()) for so, slot, box in writes if so.crops is not None]
+            if dense:
+                ops.ingest_frame(rgb, depth, inst, twc, dense)
+            if crops:
+                self._ingest_crops(rgb, depth, inst, twc, crops)
             for so, _, _ in writes:
                 so._defer = None
         self.last_twc, self.last_frame_id = twc, live_frame_id
         return created
+
+    def _ingest_crops(self, rgb, depth, inst, twc, items):
+        """The frame into the cropped stores.  objnerf_ingest_frame_crops adds item k's lost pixels to entry k of the
+        array it is given: when the frame's objects are the first len(items) of the map in order (every object visible:
+        the usual frame) that array is the running counters themselves, otherwise a scratch array that is scattered
+        into them on the device.  Nothing is read back here."""
+        dev = rgb.device
+        for _, _, obj_id, _ in items:
+            self._outside_ids.setdefault(obj_id, len(self._outside_ids))
+        n = len(self._outside_ids)
+        if self._outside is None or self._outside.numel() < n:
+            grown = torch.zeros(max(64, 2 * n), dtype=torch.int32, device=dev)
+            if self._outside is not None:
+                grown[:self._outside.numel()] = self._outside
+            self._outside = grown
+        where = [self._outside_ids[obj_id] for _, _, obj_id, _ in items]
+        if where == list(range(len(items))):
+            ops.ingest_frame_crops(rgb, depth, inst, twc, items, self._outside)
+            return
+        lost = torch.zeros(len(items), dtype=torch.int32, device=dev)
+        ops.ingest_frame_crops(rgb, depth, inst, twc, items, lost)
+        self._outside.index_add_(0, torch.tensor(where, dtype=torch.int64).to(dev), lost)
+
+    def check_crops(self):
+        """Raise ValueError when pixels of an object fell outside its crop (its 2-D box was narrower than its instance
+        mask: get_bound would miss them).  Reads the device counters: called where the host synchronises anyway.  Under
+        object sharding the finding is MAX-reduced first, so that every rank raises together (a rank-local raise would
+        leave the others hanging in their next collective)."""
+        if getattr(self.cfg, "keyframe_store", "dense") != "crop":
+            return
+        bad = {}
+        if self._outside is not None:
+            cnt = self._outside[:len(self._outside_ids)].cpu().tolist()
+            bad = {i: c for i, c in zip(self._outside_ids, cnt) if c}
+        if odist._active(self.group):
+            flag = torch.tensor([1 if bad else 0], dtype=torch.int32, device=self.cfg.training_device)
+            odist.allreduce_max_(flag, self.group)
+            if int(flag.item()) and not bad:
+                raise ValueError("keyframe_store = 'crop': pixels of objects on another rank lie outside their 2-D boxes")
+        if bad:
+            raise ValueError("keyframe_store = 'crop': pixels of these objects lie outside their 2-D boxes and were not "
+                             "stored {object id: pixels}: %s" % bad)
+
+    def store_bytes(self) -> int:
+        """Bytes of keyframe pixels held by this rank's objects, for either kind of store."""
+        return sum(so.store_bytes() for so in self.vis_dict.values())
 
     # ------------------------------------------------------------------ train.py:272-276
     def _ensure_stack(self):
@@ -356,6 +411,7 @@ class IncrementalMapper:
     def compute_bounds(self, intrinsic_open3d=None, final=False):
         """sceneObject.get_bound for all of this rank's objects in one ops.object_bounds call (train.py:533 calls it per
         object before every checkpoint) -> {obj_id: (bbox3d, bbox) | (None, None)}."""
+        self.check_crops()
         own = self._own_objects()
         return dict(zip(own, get_bounds(list(own.values()), intrinsic_open3d, final)))
 
@@ -365,7 +421,9 @@ class IncrementalMapper:
         None, as in the reference)."""
         own = self._own_objects()
         if need_bound:
-            self.compute_bounds()
+            self.compute_bounds()                   # (checks the crops' counters itself)
+        else:
+            self.check_crops()
         for obj_id, so in own.items():
             d = os.path.join(log_dir, "ckpt", str(obj_id))
             os.makedirs(d, exist_ok=True)
@@ -396,8 +454,12 @@ def main(argv=None):
     ap.add_argument("--frames", default=None, type=int, help="stop after this many frames")
     ap.add_argument("--bf16", action="store_true", help="bf16 MFMA operands (fp32 accumulation and weights)")
     ap.add_argument("--single-worker", action="store_true", help="read frames in this process (no loader workers)")
+    ap.add_argument("--keyframe-store", choices=ocfg.KEYFRAME_STORES, default=None,
+                    help="keyframe store of the foreground objects (default: the config's model.keyframe_store, else dense)")
     args = ap.parse_args(argv)
     cfg = ocfg.Config(args.config)
+    if args.keyframe_store is not None:
+        cfg.keyframe_store = args.keyframe_store
     rank = 0
     if "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) > 1:     # torchrun: one process per GPU
         import torch.distributed as dist

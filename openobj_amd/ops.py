@@ -645,9 +645,59 @@ def ingest_frame(rgb, depth, inst, t_wc, items) -> None:
                                      _stream()), "objnerf_ingest_frame")
 
 
+def ingest_frame_crops(rgb, depth, inst, t_wc, items, outside) -> None:
+    """ingest_frame for cropped stores (objnerf_ingest_frame_crops): items = [(kf_store.KeyframeCropStore, slot,
+    obj_id, box[4])]; every store gets room for the box's crop first (it may grow: its arena then moves).  outside:
+    device int32 [>= len(items)], entry k receives += the number of "this object" pixels of item k outside its crop."""
+    import numpy as np
+    from ._lib import IngestCropItem, KfCrops
+    from .kf_store import crop_rect
+    rgb = _req(rgb, torch.uint8, "rgb")
+    depth = _req(depth, torch.float32, "depth")
+    inst = _req(inst, torch.int32, "inst")
+    t_wc = _req(t_wc, torch.float32, "t_wc")
+    outside = _req(outside, torch.int32, "outside")
+    W, H = depth.shape
+    if outside.numel() < len(items):
+        raise ObjnerfError("ingest_frame_crops: one `outside` counter per item expected")
+    if len({(id(st), int(slot)) for st, slot, _, _ in items}) != len(items):
+        raise ObjnerfError("ingest_frame_crops: a slot is written twice")
+    for st, slot, _, box in items:                             # every item is checked before any store is touched
+        if (st.W, st.H) != (W, H) or not 0 <= slot < st.F or len(box) != 4:
+            raise ObjnerfError("ingest_frame_crops: store / frame shapes do not match")
+    rects = [crop_rect(box, W, H) for _, _, _, box in items]
+    for (st, slot, _, _), rect in zip(items, rects):
+        st.reserve(int(slot), rect)
+    arr = (IngestCropItem * len(items))()
+    for i, (st, slot, obj_id, box) in enumerate(items):        # (after every reserve: a store may be listed twice)
+        _req(st.arena, torch.uint8, "arena"); _req(st.rect, torch.int32, "rect")
+        _req(st.t_wc, torch.float32, "t_wc_batch"); _req(st.bbox, torch.float32, "bbox")
+        if rects[i][2] * rects[i][3] > st.cap or st.arena.numel() != st.F * st.cap * 8:
+            raise ObjnerfError("ingest_frame_crops: the crop does not fit its store")
+        arr[i] = IngestCropItem(KfCrops(*st.descriptor()), int(slot), int(obj_id),
+                                (C.c_float * 4)(*[float(v) for v in box]), (C.c_int32 * 4)(*rects[i]))
+    dev_items = torch.from_numpy(np.frombuffer(arr, dtype=np.uint8).copy()).to(rgb.device)
+    check(lib().objnerf_ingest_frame_crops(W, H, _ptr(rgb), _ptr(depth), _ptr(inst), _ptr(t_wc), len(items),
+                                           _ptr(dev_items), _ptr(outside), _stream()), "objnerf_ingest_frame_crops")
+
+
 def keyframe_table(stores) -> torch.Tensor:
     """Device descriptor table of objnerf_sample_rays_stacked: stores = [(rgbs_batch, depth_batch, t_wc_batch, bbox)]
-    per object (the tensors must stay alive and in place while the table is used).  int64 [K, 4] of device pointers."""
+    per object (the tensors must stay alive and in place while the table is used).  int64 [K, 4] of device pointers.
+    stores = [kf_store.KeyframeCropStore]: the table of objnerf_sample_rays_crops, int64 [K, 5] (objnerf_kf_crops:
+    arena, cap, rect, t_wc, bbox), valid until a store grows (its `version`).  The samplers and object_bounds tell the
+    two apart by the row length."""
+    from .kf_store import KeyframeCropStore
+    if isinstance(stores[0], KeyframeCropStore):
+        for st in stores:
+            if not isinstance(st, KeyframeCropStore):
+                raise ObjnerfError("keyframe_table: dense and cropped stores in one table")
+            _req(st.rect, torch.int32, "rect"); _req(st.t_wc, torch.float32, "t_wc_batch")
+            _req(st.bbox, torch.float32, "bbox")
+            if st.cap <= 0 or st.arena.numel() != st.F * st.cap * 8:
+                raise ObjnerfError("keyframe_table: a cropped store without keyframes")
+            _req(st.arena, torch.uint8, "arena")
+        return torch.tensor([list(st.descriptor()) for st in stores], dtype=torch.int64).to(stores[0].arena.device)
     rows = []
     for rgbs, depth, t_wc, bbox in stores:
         _req(rgbs, torch.uint8, "rgbs_batch"); _req(depth, torch.float32, "depth_batch")
@@ -743,6 +793,14 @@ def _seed_of(seed):
     return (torch.initial_seed() if seed is None else int(seed)) & (2 ** 64 - 1)
 
 
+def _sample_stacked_call(a: SampleArgs, K: int, table: torch.Tensor) -> None:
+    """The stacked sampler launch for either table kind (keyframe_table): [K, 4] dense stores, [K, 5] cropped ones."""
+    if table.shape[1] == 5:
+        check(lib().objnerf_sample_rays_crops(C.byref(a), K, _ptr(table), _stream()), "objnerf_sample_rays_crops")
+    else:
+        check(lib().objnerf_sample_rays_stacked(C.byref(a), K, _ptr(table), _stream()), "objnerf_sample_rays_stacked")
+
+
 def sample_rays_stacked(table: torch.Tensor, F: int, W: int, H: int, rays_dir_cache, kf_ids, u_w, u_h, u, g,
                         n_cam2surf: int, n_bins: int, surface_eps: float, stop_eps: float, min_bound: float = 0.0,
                         obj_center: float = 0.0, partfeat=None):
@@ -755,7 +813,7 @@ def sample_rays_stacked(table: torch.Tensor, F: int, W: int, H: int, rays_dir_ca
     u_w, u_h = _req(u_w, torch.float32, "u_w"), _req(u_h, torch.float32, "u_h")
     u, g = _req(u, torch.float32, "u"), _req(g, torch.float32, "g")
     K, n_frames, n_px = u_w.shape
-    if table.shape != (K, 4) or kf_ids.shape != (K, n_frames):
+    if table.shape not in ((K, 4), (K, 5)) or kf_ids.shape != (K, n_frames):
         raise ObjnerfError("sample_rays_stacked: table / kf_ids do not match the draws")
     n = n_frames * n_px
     S = n_cam2surf + n_bins
@@ -767,7 +825,7 @@ def sample_rays_stacked(table: torch.Tensor, F: int, W: int, H: int, rays_dir_ca
                    _ptr(o["rgb"]), _ptr(o["depth"]), _ptr(o["valid"]), _ptr(o["labels"]), _ptr(o["z"]), _ptr(o["pts"]),
                    _ptr(o["ws"]), 0, 0, 0, None, None, None, None, None)
     pf = _partfeat_fields(a, partfeat, K, F, n, table.device, True)
-    check(lib().objnerf_sample_rays_stacked(C.byref(a), K, _ptr(table), _stream()), "objnerf_sample_rays_stacked")
+    _sample_stacked_call(a, K, table)
     r = (o["rgb"], o["depth"], o["valid"].bool(), o["labels"], o["pts"], o["z"])
     return r if partfeat is None else r + (pf,)
 
@@ -787,15 +845,24 @@ def sample_rays_seeded(stores, F: int, W: int, H: int, rays_dir_cache, kf_meta: 
     partfeat = (global_partfeat, use_frame, stride, part_down): the part-level feature of every ray (vmap.py:437-452)
     is gathered by the same launch -> key "partfeat" [.., n, C].
     Returns a dict: rgb u8, depth, valid (bool), labels u8, z, pts | origins + dirs, kf, px."""
+    from .kf_store import KeyframeCropStore
     stacked = torch.is_tensor(stores)
     rays_dir_cache = _req(rays_dir_cache, torch.float32, "rays_dir_cache")
     kf_meta = _req(kf_meta, torch.int32, "kf_meta") if kf_meta is not None else None
     kf_ids = _req(kf_ids, torch.int64, "kf_ids") if kf_ids is not None else None
+    table = None
     if stacked:
         table = _req(stores, torch.int64, "table")
         K, dev = table.shape[0], table.device
         if (kf_meta is not None and kf_meta.shape != (K, 4)) or (kf_ids is not None and kf_ids.shape != (K, n_frames)):
             raise ObjnerfError("sample_rays_seeded: kf_meta / kf_ids do not match the table")
+        ptrs = [None] * 4
+    elif isinstance(stores, KeyframeCropStore):
+        # ONE object's cropped store: the crops entry point with K = 1, whose [1][...] layouts are the single call's
+        table = keyframe_table([stores])
+        K, dev = 1, table.device
+        if (kf_meta is not None and kf_meta.shape != (4,)) or (kf_ids is not None and kf_ids.shape != (n_frames,)):
+            raise ObjnerfError("sample_rays_seeded: kf_meta / kf_ids do not match the store")
         ptrs = [None] * 4
     else:
         rgbs, depth, t_wc, bbox = stores
@@ -811,8 +878,8 @@ def sample_rays_seeded(stores, F: int, W: int, H: int, rays_dir_cache, kf_meta: 
                    _ptr(o["ws"]), _seed_of(seed), (_next_offset() if draw is None else int(draw)) & 0x1FFFFFFF, 0,
                    _ptr(kf_meta), _ptr(o["kf"]), _ptr(o["px"]), _ptr(o["origins"]), _ptr(o["dirs"]))
     o["partfeat"] = _partfeat_fields(a, partfeat, K, F, n_frames * n_px, dev, stacked)
-    if stacked:
-        check(lib().objnerf_sample_rays_stacked(C.byref(a), K, _ptr(table), _stream()), "objnerf_sample_rays_stacked")
+    if table is not None:
+        _sample_stacked_call(a, K, table)
     else:
         check(lib().objnerf_sample_rays(C.byref(a), _stream()), "objnerf_sample_rays")
     if kf_ids is not None and record:

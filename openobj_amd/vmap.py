@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import ops, trainer
+from .kf_store import KeyframeCropStore, crop_rect
 
 
 class cameraInfo:
@@ -81,18 +82,29 @@ class sceneObject:
         if defer is None:
             self.bbox[0] = bbox_2d
         self.rgb_idx, self.state_idx = slice(0, 3), slice(3, 4)
-        self.rgbs_batch = torch.empty(self.keyframe_buffer_size, self.frames_width, self.frames_height, 4,
-                                      dtype=torch.uint8, device=dev)
+        # cfg.keyframe_store "crop": the slots keep only their box crops (kf_store.KeyframeCropStore); the background's
+        # box is the whole image, it stays dense
+        self.crops = None
+        if getattr(cfg, "keyframe_store", "dense") == "crop" and not (self.do_bg and self.obj_id == 0):
+            self.t_wc_batch = torch.empty(self.keyframe_buffer_size, 4, 4, dtype=torch.float32, device=dev)
+            self.crops = KeyframeCropStore(self.keyframe_buffer_size, self.frames_width, self.frames_height, dev,
+                                           t_wc=self.t_wc_batch, bbox=self.bbox)
+        else:
+            self.rgbs_batch = torch.empty(self.keyframe_buffer_size, self.frames_width, self.frames_height, 4,
+                                          dtype=torch.uint8, device=dev)
         if self.part_mode:
             self.part_down = cfg.part_down
             self.use_frame = np.zeros(self.keyframe_buffer_size)
             self.use_frame[0] = live_frame_id
         self.other_obj, self.this_obj, self.unknown_obj = 0, 1, 2
         self.semantic_id = None
-        self.depth_batch = torch.empty(self.keyframe_buffer_size, self.frames_width, self.frames_height,
-                                       dtype=torch.float32, device=dev)
-        self.t_wc_batch = torch.empty(self.keyframe_buffer_size, 4, 4, dtype=torch.float32, device=dev)
-        if defer is None:
+        if self.crops is None:
+            self.depth_batch = torch.empty(self.keyframe_buffer_size, self.frames_width, self.frames_height,
+                                           dtype=torch.float32, device=dev)
+            self.t_wc_batch = torch.empty(self.keyframe_buffer_size, 4, 4, dtype=torch.float32, device=dev)
+        if defer is None and self.crops is not None:
+            self.crops.write(0, rgb, depth, mask, bbox_2d, t_wc)
+        elif defer is None:
             self.rgbs_batch[0, :, :, self.rgb_idx] = rgb
             self.rgbs_batch[0, :, :, self.state_idx] = mask[..., None]
             self.depth_batch[0] = depth
@@ -114,6 +126,11 @@ class sceneObject:
     def _write_slot(self, slot, rgb, depth, mask, bbox_2d, t_wc, frame_id):
         if self._defer is not None:             # the caller writes all objects' slots of this frame in one launch
             self._defer.append((self, slot, bbox_2d))
+            if self.part_mode:
+                self.use_frame[slot] = frame_id
+            return
+        if self.crops is not None:
+            self.crops.write(slot, rgb, depth, mask, bbox_2d, t_wc)
             if self.part_mode:
                 self.use_frame[slot] = frame_id
             return
@@ -214,6 +231,16 @@ class sceneObject:
             return (o["rgb"].reshape(n_frames, n_samples, 3), o["depth"].reshape(n_frames, n_samples), o["valid"],
                     o["labels"], pcs, o["z"].reshape(n_frames, n_samples, S), partfeat)
         pf = self._partfeat_args(global_partfeat)                   # vmap.py:437-452: gathered by the same launch
+        if self.crops is not None:                                  # the stacked entry point with K = 1
+            r = ops.sample_rays_stacked(
+                ops.keyframe_table([self.crops]), self.keyframe_buffer_size, self.frames_width, self.frames_height,
+                cached_rays_dir, draws["kf_ids"][None], draws["u_w"][None], draws["u_h"][None], draws["u"][None],
+                draws["g"][None], N, M, self.surface_eps, self.stop_eps, float(self.min_bound), float(self.obj_center),
+                partfeat=pf)
+            r = (r[0].reshape(n_frames, n_samples, 3), r[1].reshape(n_frames, n_samples), r[2][0], r[3][0],
+                 r[4].reshape(n_frames, n_samples, N + M, 3), r[5].reshape(n_frames, n_samples, N + M)) + \
+                ((r[6].reshape(n_frames, n_samples, -1),) if pf is not None else ())
+            return r if pf is not None else r + (None,)
         r = ops.sample_rays(
             self.rgbs_batch, self.depth_batch, self.t_wc_batch, self.bbox, cached_rays_dir, draws["kf_ids"],
             draws["u_w"], draws["u_h"], draws["u"], draws["g"], N, M, self.surface_eps, self.stop_eps,
@@ -236,8 +263,17 @@ class sceneObject:
         return r + (sampled_partfeat,)
 
     def keyframe_store(self):
-        """The four device tensors the sampler reads (fixed addresses for the life of the object)."""
+        """What the sampler reads: the four device tensors of the dense store (fixed addresses for the life of the
+        object), or the object's KeyframeCropStore (its arena moves when it grows: see its `version`)."""
+        if self.crops is not None:
+            return self.crops
         return self.rgbs_batch, self.depth_batch, self.t_wc_batch, self.bbox
+
+    def store_bytes(self):
+        """Bytes of keyframe pixels this object holds, for either kind of store."""
+        if self.crops is not None:
+            return self.crops.nbytes
+        return self.rgbs_batch.numel() + 4 * self.depth_batch.numel()
 
     def set_semantic(self, semantic_id):                                  # vmap.py:284-285
         self.semantic_id = semantic_id
@@ -388,7 +424,7 @@ class StackedSampler:
     train.py:368-388): one set of random draws for all objects, objnerf_sample_rays_stacked, outputs already in the
     [K, n, ...] layout of the training step.  The objects must share the sampler configuration (every foreground
     object does, vmap.py:53-62).  Rebuild it when the list of objects changes (the descriptor table holds their
-    keyframe-store addresses)."""
+    keyframe-store addresses).  With cropped stores the table is rebuilt by itself when a store has grown."""
 
     def __init__(self, objs):
         self.objs = list(objs)
@@ -396,7 +432,17 @@ class StackedSampler:
         for x in self.objs:
             assert (x.n_bins_cam2surface, x.n_bins, x.keyframe_buffer_size, x.frames_width, x.frames_height) == \
                    (o.n_bins_cam2surface, o.n_bins, o.keyframe_buffer_size, o.frames_width, o.frames_height)
-        self.table = ops.keyframe_table([x.keyframe_store() for x in self.objs])
+        if len({x.crops is None for x in self.objs}) != 1:
+            raise ValueError("StackedSampler: dense and cropped keyframe stores in one stack")
+        self._versions = None
+        self._refresh()
+
+    def _refresh(self):
+        """(Re)build the device table when a cropped store's arena may have moved (its version changed)."""
+        v = tuple(x.crops.version for x in self.objs) if self.objs[0].crops is not None else ()
+        if v != self._versions:
+            self.table = ops.keyframe_table([x.keyframe_store() for x in self.objs])
+            self._versions = v
 
     def draw(self, n_frames, n_samples):
         """kf_ids as draw_keyframe_ids (uniform over the stored keyframes, the latest two always included, LAST),
@@ -424,6 +470,7 @@ class StackedSampler:
         generated inside the kernels (see sceneObject.get_training_samples).  compact (seeded only): `pts` is the
         pair (origins [K,n,3], dirs [K,n,3])."""
         o = self.objs[0]
+        self._refresh()
         if draws is None:
             dev = o.data_device
             meta = torch.tensor([x.kf_meta() for x in self.objs], dtype=torch.int32).to(dev)   # one small H2D copy
