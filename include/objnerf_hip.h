@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define OBJNERF_ABI_VERSION 13
+#define OBJNERF_ABI_VERSION 14
 
 #define OBJNERF_OK 0
 #define OBJNERF_EINVAL (-22)       /* bad shape / null pointer / unsupported size        */
@@ -772,6 +772,68 @@ int objnerf_ingest_frame_crops(int32_t W, int32_t H, const uint8_t* rgb, const f
                                const float* t_wc, int32_t K, const objnerf_ingest_crop_item* items, int32_t* outside,
                                void* stream);
 int objnerf_sample_rays_crops(const objnerf_sample_args* a, int32_t K, const objnerf_kf_crops* table, void* stream);
+
+/* ABI 14 -- labelling arbitrary points against the whole map (objnerf_mappoints.hip; openobj_amd/map_points.py): for N
+ * world points and K objects in the caller's order, the arg-max over objects of Trainer.eval_points (trainer.py:105-128)
+ * restricted to each object's box -- the 3-D counterpart of the z-buffer merge of train.py:550-612.
+ * boxes [K][16] fp32: center [3] | R [3][3] row-major | extent / 2 [3] | obj_center (the "bbox" of obj_<id>.pth,
+ * vmap.py:556-576; obj_center as map_vis.export passes it to Trainer.meshing, trainer.py:60).
+ *
+ * objnerf_mappoints_count / _emit (two calls, as objnerf_mc_count / _emit): point n is a candidate of object k iff
+ * |R_k^T (p_n - c_k)| <= extent_k / 2 in every component, in fp32.  count writes seg_off [K + 1] (device int64, exclusive,
+ * seg_off [K] = M) and leaves per-workgroup offsets in ws; the caller reads M and allocates; emit (same N, K, pts, boxes
+ * and ws) writes pair_pt [M] int32: object-major, ascending in the point index inside an object.  No atomics.
+ * N <= 2^31 - 1, K <= 65535; EINVAL for M > 2^31 - 1 (the keys below hold a pair in 31 bits). */
+size_t objnerf_mappoints_workspace_bytes(int64_t N, int32_t K);
+int objnerf_mappoints_count(int64_t N, int32_t K, const float* pts, const float* boxes, void* ws, size_t ws_bytes,
+                            int64_t* seg_off, void* stream);
+int objnerf_mappoints_emit(int64_t N, int32_t K, const float* pts, const float* boxes, const void* ws, size_t ws_bytes,
+                           int64_t M, int32_t* pair_pt, void* stream);
+/* OccupancyMap.forward on UniDirsEmbed.forward (model.py:61-103, embedding.py:46-55) for every pair of the hidden-32
+ * objects, at p - obj_center: a flat list of (object, 64-pair tile), weights staged per object, points gathered through
+ * pair_pt.  info [K][2] int32: {row of the object in the arena `params` [rows][p_stride] / `scale` [rows], or -1 for an
+ * object this call leaves out (a wider network); 1 for a background object (bg_ids of render_view), else 0}.
+ * pair_alpha [M] = 10 * raw (model.py:88); pair_color [M][3] (sigmoid applied) and pair_hfeat [M][32] (the input of
+ * out_clip, model.py:100) may be NULL.  best [N] uint64, ZEROED BY THE CALLER before the first eval / merge of a cloud,
+ * receives one atomicMax per pair: bit 63 = foreground and alpha > 0 (train.py:593-594: the background never hides an
+ * object), bits 62..31 = alpha's bits made order-preserving, bits 30..0 = 0x7FFFFFFF - pair (equal alphas: the lowest
+ * pair, i.e. the first object of the list).  A maximum does not depend on arrival order: bit-reproducible. */
+int objnerf_mappoints_eval(const objnerf_net* net, int32_t K, int64_t N, int64_t M, const float* params, int64_t p_stride,
+                           const float* scale, const float* pts, const float* boxes, const int32_t* info,
+                           const int64_t* seg_off, const int32_t* pair_pt, float* pair_alpha, float* pair_color,
+                           float* pair_hfeat, uint64_t* best, void* stream);
+/* A wider object (the hidden-128 background, trainer.py:15): its segment of pair_pt is contiguous.  gather: out [n][3] =
+ * pts [pair_pt [i]] - obj_center for the n entries at pair_pt (the caller passes pair_pt + seg_off [k]), the input of
+ * objnerf_eval_points_ws; merge: the keys above for pairs pair0 .. pair0 + n - 1 from pair_alpha, into best. */
+int objnerf_mappoints_gather(int64_t n, const int32_t* pair_pt, const float* pts, float obj_center, float* out, void* stream);
+int objnerf_mappoints_merge(int64_t n, int64_t pair0, const int32_t* pair_pt, const float* pair_alpha, int32_t background,
+                            uint64_t* best, void* stream);
+/* best -> out_obj [N] int32 (position in the list; -1: no occupied candidate, trainer.py:71 occ > 0.5 <=> alpha > 0),
+ * out_alpha [N] (the winner's; without one the largest candidate alpha, -inf without a candidate), optional out_pair [N]
+ * int32 (the winning pair or -1) and out_color [N][3] (pair_color of the winner, 0 without one).  M = 0 (no pair at all:
+ * best is all zero) is valid, pair_color may then be NULL: every point gets -1, -inf and colour 0. */
+int objnerf_mappoints_resolve(int64_t N, int32_t K, int64_t M, const uint64_t* best, const int64_t* seg_off,
+                              const float* pair_color, int32_t* out_obj, float* out_alpha, int32_t* out_pair,
+                              float* out_color, void* stream);
+/* out_clip (model.py:101) for the winners only: the winning pairs are compacted (they stay object-major), then
+ * out_feat [point][C] = of_w . hfeat [pair] + of_b, once per winner; rows of points without a winner are NOT written (the
+ * caller zeroes out_feat).  heads [K] (device): per object the head's weights of_w [C][H], of_b [C], the hidden rows
+ * hfeat [..][H] with row (pair - row0), H a multiple of 32.  widths: the OBJNERF_MAPPOINTS_W* bits of the widths that
+ * occur among the objects (one launch per bit; 32, 64 and 128 keep an object's weights in registers); an object whose
+ * width's bit is missing gets no feature.  win_pair: 3 x min(N, M) int32 of scratch (winning pair, point, object). */
+#define OBJNERF_MAPPOINTS_W32 1
+#define OBJNERF_MAPPOINTS_W64 2
+#define OBJNERF_MAPPOINTS_W128 4
+#define OBJNERF_MAPPOINTS_WOTHER 8
+typedef struct objnerf_mappoints_head_obj {
+  const float* of_w; const float* of_b; const float* hfeat;
+  int64_t row0;
+  int32_t H, reserved;
+} objnerf_mappoints_head_obj;
+size_t objnerf_mappoints_head_workspace_bytes(int64_t M);
+int objnerf_mappoints_head(int32_t K, int32_t C, int64_t N, int64_t M, const uint64_t* best, const int64_t* seg_off,
+                           const int32_t* pair_pt, const objnerf_mappoints_head_obj* heads, int32_t widths, void* ws,
+                           size_t ws_bytes, int32_t* win_pair, float* out_feat, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OBJNERF_LIB") or os.path.join(_HERE, "csrc", "libobjnerf_hip.so")   # OBJNERF_LIB: diagnostic builds
 
 OBJNERF_N_TENSORS = 19
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class ObjnerfError(RuntimeError):
@@ -156,6 +156,11 @@ class MaskPointsArgs(C.Structure):
                 ("pix", C.c_void_p), ("depth", C.c_void_p), ("pose", C.c_void_p), ("out", C.c_void_p)]
 
 
+class MapPointsHead(C.Structure):      # ABI 14: objnerf_mappoints_head_obj
+    _fields_ = [("of_w", C.c_void_p), ("of_b", C.c_void_p), ("hfeat", C.c_void_p), ("row0", C.c_int64),
+                ("H", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AffinityArgs(C.Structure):
     _fields_ = [("N", C.c_int32), ("F", C.c_int32), ("d_cap", C.c_int32), ("d_clip", C.c_int32),
                 ("w_geo", C.c_double), ("w_cap", C.c_double), ("w_clip", C.c_double), ("w_color", C.c_double),
@@ -288,6 +293,22 @@ SIGNATURES = {
     "objnerf_ingest_frame_crops": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "objnerf_sample_rays_crops": (C.c_int, [C.POINTER(SampleArgs), C.c_int32, C.c_void_p, C.c_void_p]),
+    # ABI 14: labelling points against the whole map (objnerf_mappoints.hip)
+    "objnerf_mappoints_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "objnerf_mappoints_count": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_void_p]),
+    "objnerf_mappoints_emit": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64,
+                                         C.c_void_p, C.c_void_p]),
+    "objnerf_mappoints_eval": (C.c_int, [C.POINTER(Net), C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_mappoints_gather": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "objnerf_mappoints_merge": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "objnerf_mappoints_resolve": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_mappoints_head_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "objnerf_mappoints_head": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1476,3 +1476,128 @@ def mask_affinity(boxes: torch.Tensor, cap: torch.Tensor, clip: torch.Tensor, co
     if E:
         check(lib().objnerf_mask_edges(N, _ptr(W), _ptr(row_off), E, _ptr(ij), _ptr(ew), _stream()), "objnerf_mask_edges")
     return W, ij, ew, terms
+
+
+# ---------------------------------------------------------------------------------------------------
+# ABI 14: labelling arbitrary points against the whole map (objnerf_mappoints.hip; map_points.MapPoints drives these)
+MAPPOINTS_MAX_PAIRS = 2 ** 31 - 1
+
+
+def mappoints_check_pairs(M: int) -> int:
+    """The keys hold a pair in 31 bits (objnerf_mappoints_emit returns EINVAL past that): raise before allocating."""
+    if M > MAPPOINTS_MAX_PAIRS:
+        raise _lib.ObjnerfError(f"map points: {M} (point, object) pairs do not fit 31 bits; label the cloud in chunks")
+    return int(M)
+
+
+def mappoints_count(pts: torch.Tensor, boxes: torch.Tensor):
+    """pts [N, 3], boxes [K, 16] (centre | R row-major | extent / 2 | obj_center) -> (seg_off int64 [K + 1] on the device,
+    the same as a list, the workspace mappoints_emit needs).  Synchronises once: seg_off is read back, so that the caller
+    can decide on M = seg[-1] (allocate, or split the cloud) before anything of that size exists."""
+    pts, boxes = _req(pts, torch.float32, "pts"), _req(boxes, torch.float32, "boxes")
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] < 1 or boxes.dim() != 2 or boxes.shape[1] != 16 or boxes.shape[0] < 1:
+        raise _lib.ObjnerfError("mappoints_count: pts [N >= 1, 3], boxes [K >= 1, 16]")
+    N, K, dev = int(pts.shape[0]), int(boxes.shape[0]), pts.device
+    nbytes = int(lib().objnerf_mappoints_workspace_bytes(N, K))
+    if nbytes == 0:
+        raise _lib.ObjnerfError(f"mappoints_count: N = {N}, K = {K} outside the supported range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    seg_off = torch.empty(K + 1, dtype=torch.int64, device=dev)
+    check(lib().objnerf_mappoints_count(N, K, _ptr(pts), _ptr(boxes), _ptr(ws), nbytes, _ptr(seg_off), _stream()),
+          "objnerf_mappoints_count")
+    return seg_off, [int(x) for x in seg_off.tolist()], ws                  # the one host sync
+
+
+def mappoints_emit(pts: torch.Tensor, boxes: torch.Tensor, ws: torch.Tensor, M: int) -> torch.Tensor:
+    """After mappoints_count on the same pts and boxes -> pair_pt int32 [M]: object-major, ascending in the point index
+    inside an object."""
+    pts, boxes = _req(pts, torch.float32, "pts"), _req(boxes, torch.float32, "boxes")
+    M = mappoints_check_pairs(M)
+    pair_pt = torch.empty(M, dtype=torch.int32, device=pts.device)
+    check(lib().objnerf_mappoints_emit(int(pts.shape[0]), int(boxes.shape[0]), _ptr(pts), _ptr(boxes), _ptr(ws),
+                                       int(ws.numel()), M, _ptr(pair_pt) if M else None, _stream()), "objnerf_mappoints_emit")
+    return pair_pt
+
+
+def mappoints_candidates(pts: torch.Tensor, boxes: torch.Tensor):
+    """mappoints_count + mappoints_emit -> (seg_off on the device, the same as a list, pair_pt int32 [M])."""
+    seg_off, seg, ws = mappoints_count(pts, boxes)
+    return seg_off, seg, mappoints_emit(pts, boxes, ws, seg[-1])
+
+
+def mappoints_eval(arena: ParamArena, pts, boxes, info, seg_off, pair_pt, pair_alpha, pair_color, pair_hfeat, best) -> None:
+    """The ragged fused evaluation of the hidden-32 objects (info [K, 2] int32: arena row or -1, background flag); one
+    atomicMax per pair into best [N] (int64 storage of the unsigned keys, zeroed by the caller)."""
+    net = arena.net.c()
+    check(lib().objnerf_mappoints_eval(C.byref(net), int(boxes.shape[0]), int(pts.shape[0]), int(pair_pt.shape[0]),
+                                       _ptr(arena.params), arena.p_stride, _ptr(arena.scale), _ptr(pts), _ptr(boxes),
+                                       _ptr(info), _ptr(seg_off), _ptr(pair_pt), _ptr(pair_alpha), _ptr(pair_color),
+                                       _ptr(pair_hfeat), _ptr(best), _stream()), "objnerf_mappoints_eval")
+
+
+def mappoints_wide_bytes(arena: ParamArena, n: int, want_feat: bool) -> int:
+    """Device bytes mappoints_wide takes for a segment of n pairs of a wide object, beside the pair buffers."""
+    if n <= 0:
+        return 0
+    net = arena.net.c()
+    return int(lib().objnerf_eval_workspace_bytes(C.byref(net), 1, n)) + n * (24 + (arena.net.hidden * 4 if want_feat else 0))
+
+
+def mappoints_wide(arena: ParamArena, pts, pair_pt, pair0: int, n: int, obj_center: float, background: bool, pair_alpha,
+                   pair_color, want_feat: bool, best):
+    """A wider network (the hidden-128 background) over its contiguous segment [pair0, pair0 + n): gather,
+    objnerf_eval_points_ws, merge -- three launch groups whatever n is.  -> its hidden rows [n, H] or None."""
+    if n <= 0:
+        return None
+    dev = pts.device
+    gpts = torch.empty(n, 3, device=dev)
+    seg_pt = pair_pt[pair0:pair0 + n]
+    check(lib().objnerf_mappoints_gather(n, _ptr(seg_pt), _ptr(pts), float(obj_center), _ptr(gpts), _stream()),
+          "objnerf_mappoints_gather")
+    color = pair_color[pair0:pair0 + n] if pair_color is not None else torch.empty(n, 3, device=dev)
+    hfeat = torch.empty(n, arena.net.hidden, device=dev) if want_feat else None
+    net = arena.net.c()
+    nbytes = int(lib().objnerf_eval_workspace_bytes(C.byref(net), 1, n))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    check(lib().objnerf_eval_points_ws(C.byref(net), 1, n, _ptr(arena.params), arena.p_stride, _ptr(arena.scale), _ptr(gpts),
+                                       _ptr(pair_alpha[pair0:pair0 + n]), _ptr(color), _ptr(hfeat), None, _ptr(ws), nbytes,
+                                       _stream()), "objnerf_eval_points_ws")
+    check(lib().objnerf_mappoints_merge(n, pair0, _ptr(pair_pt), _ptr(pair_alpha), 1 if background else 0, _ptr(best),
+                                        _stream()), "objnerf_mappoints_merge")
+    return hfeat
+
+
+def mappoints_resolve(best, seg_off, pair_color, M: int, want_pair: bool = False):
+    """best [N] -> (obj int32 [N] (-1: unlabelled), alpha [N], winning pair int32 [N] | None, colour [N, 3] | None).
+    pair_color [M, 3] or None (no colour wanted); M = 0 -- no pair, an empty pair_color -- gives -1, -inf and colour 0."""
+    N, K, dev = int(best.shape[0]), int(seg_off.shape[0]) - 1, best.device
+    obj = torch.empty(N, dtype=torch.int32, device=dev)
+    alpha = torch.empty(N, device=dev)
+    pair = torch.empty(N, dtype=torch.int32, device=dev) if want_pair else None
+    color = torch.empty(N, 3, device=dev) if pair_color is not None else None
+    check(lib().objnerf_mappoints_resolve(N, K, int(M), _ptr(best), _ptr(seg_off), _ptr(pair_color), _ptr(obj), _ptr(alpha),
+                                          _ptr(pair), _ptr(color), _stream()), "objnerf_mappoints_resolve")
+    return obj, alpha, pair, color
+
+
+def mappoints_head(best, seg_off, pair_pt, heads, feat_dim: int, out_feat) -> None:
+    """out_clip for the winners only, rows written straight to out_feat [N, C] (zeroed by the caller).  heads: per object
+    (of_w [C, H], of_b [C], hfeat rows or None, row0, H) -- hfeat None for an object with an empty segment."""
+    N, K, M, dev = int(best.shape[0]), int(seg_off.shape[0]) - 1, int(pair_pt.shape[0]), best.device
+    if M == 0:
+        return
+    arr = (_lib.MapPointsHead * K)()
+    widths = 0
+    for h in heads:
+        widths |= {32: 1, 64: 2, 128: 4}.get(int(h[4]), 8)        # OBJNERF_MAPPOINTS_W*
+    for k, (of_w, of_b, hfeat, row0, H) in enumerate(heads):
+        if H % 32 != 0:
+            raise _lib.ObjnerfError(f"mappoints_head: hidden width {H} is not a multiple of 32")
+        arr[k] = _lib.MapPointsHead(_ptr(of_w), _ptr(of_b), _ptr(hfeat), int(row0), int(H), 0)
+    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    nbytes = int(lib().objnerf_mappoints_head_workspace_bytes(M))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    win_pair = torch.empty(3 * min(N, M), dtype=torch.int32, device=dev)
+    check(lib().objnerf_mappoints_head(K, int(feat_dim), N, M, _ptr(best), _ptr(seg_off), _ptr(pair_pt), _ptr(table),
+                                       widths, _ptr(ws), nbytes, _ptr(win_pair), _ptr(out_feat), _stream()),
+          "objnerf_mappoints_head")
