@@ -115,3 +115,16 @@ def allreduce_max_(t: torch.Tensor, group=None) -> torch.Tensor:
     if _active(group):
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
     return t
+
+
+def allreduce_or_status_(status: torch.Tensor, group=None) -> torch.Tensor:
+    """In-place bitwise-OR all-reduce of a status word (int32[1]; bit 0 = a loss term above 1e5, bit 1 = a term that is
+    not finite).  The word is a bit field: a MAX over ranks holding 1 and 2 would lose bit 0.  The backends have no OR
+    for every device, so the two bits travel as a two-element tensor under ONE MAX all-reduce and the word is rebuilt."""
+    import torch.distributed as dist
+    if _active(group):
+        s = status.reshape(-1)[:1]
+        bits = torch.cat([s & 1, (s >> 1) & 1])
+        dist.all_reduce(bits, op=dist.ReduceOp.MAX, group=group)
+        status.reshape(-1)[:1].copy_(bits[0:1] | (bits[1:2] << 1))
+    return status

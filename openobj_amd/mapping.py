@@ -355,15 +355,17 @@ class IncrementalMapper:
             out["bg"] = list(stats["bt"].unbind(0))
         if side is not None:
             torch.cuda.current_stream(cfg.training_device).wait_stream(side)
-        # render_rays.py:109-111 ("loss explode" -> exit): every rank must leave together, so the status is MAX-reduced
-        # before anyone raises (a rank-local raise would leave the others hanging in their next collective)
-        status = torch.zeros(1, dtype=torch.int32, device=cfg.training_device)
-        if self.loop is not None and self.loop.ws is not None:
-            status = torch.maximum(status, self.loop.ws.status)
-        if self.bg_loop is not None and self.bg_loop.ws is not None:
-            status = torch.maximum(status, self.bg_loop.ws.status)
+        # The status contract: bit 0 = a loss term above 1e5 (render_rays.py:109-111, "loss explode" -> exit),
+        # bit 1 = a term that is not finite; a word belongs to ONE step (every step overwrites it), words are merged with a
+        # bitwise OR, and a frame reports the OR over ALL its iterations -- the reference would have exited in the iteration
+        # that exploded, not only in the last one.  The frame's word is derived once, here, from the loss terms the frame
+        # holds on the device anyway (nothing is added to the iteration loop).  Every rank must leave together, so the
+        # word is OR-reduced before anyone raises (a rank-local raise would leave the others hanging in their next collective)
+        words = [ops.status_of_terms(torch.stack(t) if isinstance(t, (list, tuple)) else t)
+                 for t in (stats.get("ot", out["obj"]), stats.get("bt", out["bg"])) if len(t)]
+        status = ops.merge_status(*words) if words else torch.zeros(1, dtype=torch.int32, device=cfg.training_device)
         if sharded:
-            odist.allreduce_max_(status, self.group)
+            odist.allreduce_or_status_(status, self.group)
         from .render_rays import check_status
         check_status(status)                     # bit 0 raises LossExplode; a non-finite term only warns (as the reference)
         if self.loop is not None:

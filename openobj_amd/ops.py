@@ -372,6 +372,35 @@ def step_batch_loss(alpha, color, gt_depth, gt_rgb, labels, z, color_scaling=5.0
                 counts=counts)
 
 
+STATUS_BITS = (1, 2)     # bit 0: a loss term above 1e5; bit 1: a term that is not finite (include/objnerf_hip.h)
+
+
+def merge_status(*words: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The ONE way to merge status words: bitwise OR (they are bit fields -- a numeric maximum of 1 and 2 loses bit 0).
+    words: int32 tensors of any length, every element a word (a workspace's per-chunk slots, the words of several loops).
+    Returns int32[1] (`out` when given); stays on the words' device, no host synchronisation."""
+    flat = words[0].reshape(-1) if len(words) == 1 else torch.cat([w.reshape(-1) for w in words])
+    merged = None
+    for bit in STATUS_BITS:          # (torch has no OR reduction: per bit, "any element has it")
+        has = (flat & bit).amax(dim=0, keepdim=True)
+        merged = has if merged is None else merged | has
+    if out is None:
+        return merged
+    out.copy_(merged)
+    return out
+
+
+def status_of_terms(terms: torch.Tensor) -> torch.Tensor:
+    """The status word of a set of loss terms by its definition: any term above 1e5 sets bit 0 (render_rays.py:109-111),
+    any term that is not finite sets bit 1.  int32[1] on the terms' device, no host synchronisation."""
+    t = terms.reshape(-1)
+    if t.numel() == 0:
+        return torch.zeros(1, dtype=torch.int32, device=t.device)
+    explode = (t > 100000.0).any().to(torch.int32)
+    nonfinite = (~torch.isfinite(t)).any().to(torch.int32)
+    return (explode | (nonfinite << 1)).reshape(1)
+
+
 # bytes; the layer-wise / hidden-256 paths materialise activations per object chunk (OBJNERF_WORKSPACE_BUDGET_GIB: override)
 LAYERWISE_WORKSPACE_BUDGET = int(float(os.environ.get("OBJNERF_WORKSPACE_BUDGET_GIB", "64")) * (1 << 30))
 
@@ -585,8 +614,8 @@ def train_step(arena: ParamArena, ws: TrainWorkspace, batch: Dict[str, torch.Ten
         for sd, ev in zip(ws.sides, ws.ev_out):
             ev.record(sd)
             main.wait_event(ev)
-    torch.amax(ws.status_chunks, dim=0, keepdim=True, out=ws.status)
-    if optim is not None:               # (chunked: one optimiser launch over the whole arena after the last chunk)
+    merge_status(ws.status_chunks, out=ws.status)
+    if optim is not None:              # (chunked: one optimiser launch over the whole arena after the last chunk)
         optim.step(ws.grads, arena.has_grad_mask(with_feat), flags=flags)
 
 

@@ -56,7 +56,7 @@ class LossExplode(RuntimeError):
 
 
 STATUS_EXPLODE = 1       # a loss term above 1e5: the reference's test (render_rays.py:109-111) -> LossExplode
-STATUS_NONFINITE = 2     # a NaN / Inf loss term: `nan > 100000` is False, the reference carries on -> a warning, once
+STATUS_NONFINITE = 2     # a NaN / Inf loss term: `nan > 100000` is False, the reference carries on -> a warning, on every check
 
 
 def check_status(status) -> int:

@@ -291,14 +291,13 @@ class HipTrainLoop:
         counts, flags = ops.label_counts(batch["labels"])           # over the WHOLE stacked batch
         if global_flags is not None:
             flags = global_flags
-        self.status.zero_()
         for k, t in enumerate(self.trainers):
             bk = {key: v[k:k + 1] for key, v in batch.items()}
             ops.train_step(t.arena, self.wss[k], bk, with_feat=self.with_feat, global_flags=flags,
                            global_counts=counts[k:k + 1], bf16=self.bf16)
             self.opts[k].step(self.wss[k].grads, self.mask, flags=flags)
             self.loss_terms[k] = self.wss[k].loss_terms[0]
-            torch.maximum(self.status, self.wss[k].status, out=self.status)
+        ops.merge_status(*[w.status for w in self.wss], out=self.status)     # (bit fields: OR, never a maximum)
         return self.loss_terms
 
     def step(self, batch: Dict[str, torch.Tensor], global_flags: Optional[torch.Tensor] = None,
@@ -332,7 +331,9 @@ class HipTrainLoop:
             batch = {k: v[:, sl].contiguous() for k, v in pool.items()}
             out.append(self.step(batch).clone())
         if check_status:
-            _check_status(self.ws.status)
+            # the frame's word: the OR over ALL its iterations (each step overwrites ws.status; the reference would have
+            # exited in the iteration that exploded), derived once from the terms the frame holds anyway
+            _check_status(ops.status_of_terms(torch.stack(out)))
         return out
 
     def copy_back(self):
