@@ -835,6 +835,50 @@ int objnerf_mappoints_head(int32_t K, int32_t C, int64_t N, int64_t M, const uin
                            const int32_t* pair_pt, const objnerf_mappoints_head_obj* heads, int32_t widths, void* ws,
                            size_t ws_bytes, int32_t* win_pair, float* out_feat, void* stream);
 
+/* Geometry evaluation of a map (objnerf_mapeval.hip; openobj_amd/map_eval.py): vMAP's accuracy / completion between
+ * points sampled on two sets of meshes; the reference has no counterpart.  Added under ABI 14: the five entries below are
+ * purely additive (no existing struct or signature changes), so OBJNERF_ABI_VERSION stays 14.
+ *
+ * objnerf_mesh_sample: N area-weighted points on the surfaces of S meshes stored back to back.  verts [V][3] fp64, faces
+ * [F][3] int32 (global vertex rows), face_off / samp_off [S + 1] device int64 (segment s owns faces face_off[s] ..
+ * face_off[s+1] and samples samp_off[s] .. samp_off[s+1]; samp_off[S] = N).  Per face area = 0.5 sqrt((cx cx + cy cy) +
+ * cz cz) of c = (B - A) x (C - A) in fp64, amax the segment's exact maximum, q = (uint64) floor(area / amax * 2^32), the
+ * exclusive integer prefix of q per segment, W its total (< 2^63).  Sample i of segment s: the Philox4x32-10 block of
+ * counter (s, i, 0) on stream 8 under `seed` -> (x, y, z, w); t = mulhi64(x << 32 | y, W); the face k with prefix[k] <= t
+ * < prefix[k+1] (a zero-area face is never drawn); u1 = u01(z), u2 = u01(w) widened to fp64, s = sqrt(u1),
+ * p = ((1 - s) A + (s (1 - u2)) B) + (s u2) C per coordinate, every operation rounded on its own.  A draw depends on
+ * (seed, s, i) only.  out_pts [N][3] fp64, out_tri [N] int32 = the global face row.  status (one int32, cleared here):
+ * bit 0 a face names a vertex outside [0, V) (it counts as area 0), bit 1 a non-finite area (likewise), bit 2 a segment
+ * asks for samples but has W == 0 (its samples are NaN, face -1).  ws: objnerf_mesh_sample_workspace_bytes(F, S).
+ *
+ * objnerf_nearest: for every query point of segment s (qry [nq][3] fp64 under q_off [S + 1]) the nearest point of
+ * reference segment s (ref [nr][3] under r_off [S + 1]).  sorted_keys / perm: the reference's keys from objnerf_cell_keys
+ * with seg_off = r_off, shift = 0 and side `cell`, sorted per segment (stable), perm[t] = the row at sorted position t;
+ * mins [S][3] = that call's out_min.  out_d2 [nq] fp64 = the minimum over the segment of (dx dx + dy dy) + dz dz, every
+ * operation rounded on its own; out_idx [nq] int64 = the SMALLEST row of ref that attains it; +inf and -1 for an empty
+ * reference segment.  The result is exact for any cell > 0: cell only decides the speed.  Rings of cells around the
+ * query's cell are searched until the best d^2 is strictly below (r cell)^2 (1 - 2^-20) or the rings cover the grid; a
+ * query still open after ring max_rings is finished by brute force over its segment.  max_rings <= 0 selects the
+ * built-in default, a compile-time constant taken from a measured sweep: pass 0.  Other values (at most 64) exist for
+ * that sweep and for tests only -- the result never depends on it, and a large value makes a thread walk (2 r + 1)^2
+ * columns per ring before it gives up.  status bit 0: a query is not finite (its outputs are +inf, -1).  ws: objnerf_nearest_workspace_bytes(nq, S).
+ *
+ * objnerf_seg_stats: out [S][5 + T] fp64 per segment of d [n] under off [S + 1]: the number of finite entries, of
+ * non-finite ones, the sum, the sum of squares and the maximum (-inf without one) of the finite ones, and for each of
+ * the T <= 4 thresholds (a HOST array) the number of finite d < threshold.  Thread-strided partial sums, then a fixed
+ * tree: two calls write the same bytes. */
+size_t objnerf_mesh_sample_workspace_bytes(int64_t F, int32_t S);
+int objnerf_mesh_sample(int64_t V, int64_t F, int32_t S, int64_t N, const double* verts, const int32_t* faces,
+                        const int64_t* face_off, const int64_t* samp_off, uint64_t seed, void* ws, size_t ws_bytes,
+                        double* out_pts, int32_t* out_tri, int32_t* status, void* stream);
+size_t objnerf_nearest_workspace_bytes(int64_t nq, int32_t S);
+int objnerf_nearest(int64_t nr, int64_t nq, int32_t S, const double* ref, const int64_t* r_off, const int64_t* sorted_keys,
+                    const int64_t* perm, const double* mins, double cell, const double* qry, const int64_t* q_off,
+                    int32_t max_rings, void* ws, size_t ws_bytes, double* out_d2, int64_t* out_idx, int32_t* status,
+                    void* stream);
+int objnerf_seg_stats(int64_t n, int32_t S, const double* d, const int64_t* off, int32_t T, const double* thresholds,
+                      double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -309,6 +309,17 @@ SIGNATURES = {
     "objnerf_mappoints_head_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "objnerf_mappoints_head": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # geometry evaluation (objnerf_mapeval.hip): additive, still ABI 14
+    "objnerf_mesh_sample_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "objnerf_mesh_sample": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "objnerf_nearest_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "objnerf_nearest": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_seg_stats": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double),
+                                    C.c_void_p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

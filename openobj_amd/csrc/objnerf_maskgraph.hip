@@ -32,13 +32,12 @@
 #include <stdint.h>
 #include <math.h>
 #include "objnerf_wg.h"
+#include "objnerf_cells.h"
 
 namespace {
 
 constexpr int MG_WG = 256;
 constexpr int MG_SCAN_WG = 1024;
-constexpr int CELL_BITS = 21;
-constexpr int64_t CELL_MAX = (1ll << CELL_BITS) - 1;
 constexpr int RAY_STEP = 10;          // get_rays: torch.arange(0, w, 10)
 
 struct DbLayout { size_t parent, root, rank, core, blk, total; int64_t nb; };
@@ -54,33 +53,6 @@ inline DbLayout db_layout(int64_t n) {
   L.blk = o;    o += align256(sizeof(int32_t) * (size_t)(L.nb + 1));
   L.total = o;
   return L;
-}
-
-__device__ __forceinline__ int64_t cell_key(const int64_t x, const int64_t y, const int64_t z) {
-  return (x << (2 * CELL_BITS)) | (y << CELL_BITS) | z;
-}
-
-// the segment of row i: the largest s with off[s] <= i (off[0] = 0 <= i < off[S]; empty segments are stepped over)
-__device__ __forceinline__ int seg_of(const int64_t* __restrict__ off, const int S, const int64_t i) {
-  int lo = 0, hi = S;
-  while (hi - lo > 1) {
-    const int m = (lo + hi) >> 1;
-    if (off[m] <= i) lo = m; else hi = m;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ int64_t lower_bound(const int64_t* __restrict__ keys, int64_t lo, int64_t hi, const int64_t k) {
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (keys[m] < k) lo = m + 1; else hi = m;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ double dist2(const double* __restrict__ q, const double p[3]) {
-  const double dx = __dsub_rn(q[0], p[0]), dy = __dsub_rn(q[1], p[1]), dz = __dsub_rn(q[2], p[2]);
-  return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
 }
 
 // f(q, d2) for every point q of the sorted rows [lo, hi) in the 27 cells around `key`; f returns true to stop

@@ -1349,10 +1349,14 @@ def cell_keys(pts: torch.Tensor, seg_off, cell: float, shift: float = 0.0, name:
 def _sorted_cells(pts: torch.Tensor, key_off: torch.Tensor, sort_off: torch.Tensor, radius: float, name: str):
     """Cell keys on one grid per segment of key_off, sorted (stable) inside every segment of sort_off
     -> (sorted keys, permutation), both int64 [n]."""
-    dev = pts.device
     keys, _ = cell_keys(pts, key_off, float(radius) * _CELL_SLACK, 0.0, name)
+    return _sort_in_segments(keys, sort_off, pts.device)
+
+
+def _sort_in_segments(keys: torch.Tensor, off: torch.Tensor, dev):
+    """keys sorted (stable) inside every segment of off -> (sorted keys, permutation), both int64 [n]."""
     sk, perm = torch.sort(keys, stable=True)
-    seg = torch.repeat_interleave(torch.arange(sort_off.numel() - 1, device=dev), (sort_off[1:] - sort_off[:-1]).to(dev))
+    seg = torch.repeat_interleave(torch.arange(off.numel() - 1, device=dev), (off[1:] - off[:-1]).to(dev))
     _, order = torch.sort(seg[perm], stable=True)
     return sk[order].contiguous(), perm[order].contiguous()
 
@@ -1630,3 +1634,152 @@ def mappoints_head(best, seg_off, pair_pt, heads, feat_dim: int, out_feat) -> No
     check(lib().objnerf_mappoints_head(K, int(feat_dim), N, M, _ptr(best), _ptr(seg_off), _ptr(pair_pt), _ptr(table),
                                        widths, _ptr(ws), nbytes, _ptr(win_pair), _ptr(out_feat), _stream()),
           "objnerf_mappoints_head")
+
+
+# ------------------------------------------------------------------------- geometry evaluation (objnerf_mapeval.hip)
+NEAREST_CELL_FACTOR = 1.0       # cell side = this x the typical sample spacing (profiles/mapeval_bench.txt)
+_MESH_STATUS = ((1, "a face names a vertex outside [0, V)"), (2, "a face has a non-finite area"),
+                (4, "a segment asks for samples but has no area"))
+
+
+def _offsets(off, total: int, name: str) -> torch.Tensor:
+    off = torch.as_tensor(off, dtype=torch.int64).cpu()
+    if off.dim() != 1 or off.numel() < 2 or int(off[0]) != 0 or int(off[-1]) != total or bool((off[1:] < off[:-1]).any()):
+        raise _lib.ObjnerfError(f"{name}: offsets must rise from 0 to {total}")
+    return off
+
+
+def mesh_sample(verts: torch.Tensor, faces: torch.Tensor, face_off, samp_off, seed: int = 0, out=None):
+    """objnerf_mesh_sample: area-weighted points on S meshes stored back to back -> (pts fp64 [N, 3], tri int32 [N] = the
+    global face row).  verts fp64 [V, 3], faces int32 [F, 3] (global vertex rows), face_off / samp_off [S + 1].  Sample i
+    of mesh s depends on (seed, s, i) only.  out: (pts, tri) to write into."""
+    verts = _req(verts, torch.float64, "mesh_sample: verts")
+    faces = _req(faces, torch.int32, "mesh_sample: faces")
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.ObjnerfError("mesh_sample: expected verts [V, 3] and faces [F, 3]")
+    V, F, dev = int(verts.shape[0]), int(faces.shape[0]), verts.device
+    if faces.device != dev:
+        raise _lib.ObjnerfError("mesh_sample: verts and faces on different devices")
+    foff = _offsets(face_off, F, "mesh_sample: face_off")
+    S = foff.numel() - 1
+    soff = torch.as_tensor(samp_off, dtype=torch.int64).cpu()
+    if soff.numel() != S + 1:
+        raise _lib.ObjnerfError("mesh_sample: face_off and samp_off must have one entry per mesh, plus one")
+    N = int(soff[-1]) if soff.numel() else 0
+    soff = _offsets(soff, N, "mesh_sample: samp_off")
+    if max(V, F, N) >= 2 ** 31:
+        raise _lib.ObjnerfError("mesh_sample: at most 2^31 - 1 vertices, faces and samples")
+    if out is None:
+        pts = torch.empty(N, 3, dtype=torch.float64, device=dev)
+        tri = torch.empty(N, dtype=torch.int32, device=dev)
+    else:
+        pts, tri = _req(out[0], torch.float64, "mesh_sample: out pts"), _req(out[1], torch.int32, "mesh_sample: out tri")
+        if tuple(pts.shape) != (N, 3) or tuple(tri.shape) != (N,) or pts is not out[0] or tri is not out[1]:
+            raise _lib.ObjnerfError("mesh_sample: out must be contiguous (pts [N, 3], tri [N])")
+    nbytes = int(lib().objnerf_mesh_sample_workspace_bytes(F, S))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    foff_dev, soff_dev = foff.to(dev), soff.to(dev)          # (held in names: a temporary's block is reused by the next)
+    check(lib().objnerf_mesh_sample(V, F, S, N, _ptr(verts) if V else None, _ptr(faces) if F else None, _ptr(foff_dev),
+                                    _ptr(soff_dev), int(seed) & (2 ** 64 - 1), _ptr(ws), nbytes,
+                                    _ptr(pts) if N else None, _ptr(tri) if N else None, _ptr(status), _stream()),
+          "objnerf_mesh_sample")
+    st = int(status.item())
+    if st:
+        raise _lib.ObjnerfError("mesh_sample: " + "; ".join(msg for bit, msg in _MESH_STATUS if st & bit))
+    return pts, tri
+
+
+class NearestPlan:
+    """The sorted cell keys of S reference point sets: query() then finds exact nearest points for any number of query
+    sets.  cell: the grid's cell side (any value > 0 gives the same result; it decides the speed only); None: taken
+    from the sets' extents and counts as NEAREST_CELL_FACTOR x the spacing of that many points spread over the surface
+    of each set's box (the median over the sets)."""
+
+    def __init__(self, ref: torch.Tensor, r_off, cell: Optional[float] = None):
+        self.ref, self.off, self.n = _point_sets(ref, r_off, "nearest: ref")
+        self.S = self.off.numel() - 1
+        self.dev = self.ref.device
+        self.off_dev = self.off.to(self.dev)
+        self.keys = self.perm = None
+        self.mins = torch.zeros(self.S, 3, dtype=torch.float64, device=self.dev)
+        self.cell = float(cell) if cell is not None else (self._auto_cell() if self.n else 1.0)
+        if not (self.cell > 0.0 and np.isfinite(self.cell)):
+            raise _lib.ObjnerfError("nearest: cell must be positive")
+        if self.n:
+            keys, self.mins = cell_keys(self.ref, self.off, self.cell, 0.0, "nearest: ref")
+            self.keys, self.perm = _sort_in_segments(keys, self.off, self.dev)
+
+    def _auto_cell(self) -> float:
+        b = point_bounds(self.ref, self.off).cpu().numpy()
+        cnt = (self.off[1:] - self.off[:-1]).numpy().astype(np.float64)
+        ok = cnt > 0
+        if not np.isfinite(b[ok]).all():
+            raise _lib.ObjnerfError("nearest: ref: a point is not finite")
+        e = b[ok, 3:] - b[ok, :3]
+        area = 2.0 * (e[:, 0] * e[:, 1] + e[:, 1] * e[:, 2] + e[:, 2] * e[:, 0])
+        spacing = np.sqrt(area / cnt[ok])
+        spacing = spacing[spacing > 0]
+        cell = NEAREST_CELL_FACTOR * float(np.median(spacing)) if spacing.size else 1.0
+        return max(cell, float(e.max()) / 2.0 ** 20, float(np.finfo(np.float64).tiny))
+
+    def query(self, qry: torch.Tensor, q_off, max_rings: int = 0, out=None):
+        """objnerf_nearest -> (d2 fp64 [nq] = the smallest squared distance to a reference point of the same segment,
+        idx int64 [nq] = the smallest row of ref that attains it; +inf and -1 for an empty reference segment).
+        max_rings: the last ring of cells the per-query search visits before brute force takes over (0 = the library's
+        default; the result does not depend on it); out: (d2, idx) to write into."""
+        qry, qoff, nq = _point_sets(qry, q_off, "nearest: qry")
+        if qoff.numel() != self.S + 1:
+            raise _lib.ObjnerfError("nearest: ref and qry must have the same number of segments")
+        if qry.device != self.dev:
+            raise _lib.ObjnerfError("nearest: ref and qry on different devices")
+        if out is None:
+            d2 = torch.empty(nq, dtype=torch.float64, device=self.dev)
+            idx = torch.empty(nq, dtype=torch.int64, device=self.dev)
+        else:
+            d2, idx = _req(out[0], torch.float64, "nearest: out d2"), _req(out[1], torch.int64, "nearest: out idx")
+            if tuple(d2.shape) != (nq,) or tuple(idx.shape) != (nq,) or d2 is not out[0] or idx is not out[1]:
+                raise _lib.ObjnerfError("nearest: out must be contiguous (d2 [nq], idx [nq])")
+        if nq == 0:
+            return d2, idx
+        qoff_dev = qoff.to(self.dev)
+        nbytes = int(lib().objnerf_nearest_workspace_bytes(nq, self.S))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        status = torch.empty(1, dtype=torch.int32, device=self.dev)
+        check(lib().objnerf_nearest(self.n, nq, self.S, _ptr(self.ref) if self.n else None, _ptr(self.off_dev),
+                                    _ptr(self.keys), _ptr(self.perm), _ptr(self.mins), self.cell, _ptr(qry), _ptr(qoff_dev),
+                                    int(max_rings), _ptr(ws), nbytes, _ptr(d2), _ptr(idx), _ptr(status), _stream()),
+              "objnerf_nearest")
+        if int(status.item()) != 0:
+            raise _lib.ObjnerfError("nearest: a query point is not finite")
+        return d2, idx
+
+
+def nearest(qry: torch.Tensor, q_off, ref: torch.Tensor, r_off, cell: Optional[float] = None):
+    """For every query point of segment s the nearest point of reference segment s -> (d2, idx); see NearestPlan."""
+    _req(qry, torch.float64, "nearest: qry")
+    return NearestPlan(ref, r_off, cell).query(qry, q_off)
+
+
+def seg_stats(d: torch.Tensor, off, thresholds=(), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """objnerf_seg_stats -> fp64 [S, 5 + T]: per segment of d (fp64 [n]) the number of finite entries, of non-finite
+    ones, the sum, the sum of squares and the maximum of the finite ones, then the number of finite d < thr per threshold
+    (at most 4).  Summed in a fixed order: two calls give the same bits.  out: the tensor to write into."""
+    d = _req(d, torch.float64, "seg_stats: d")
+    if d.dim() != 1:
+        raise _lib.ObjnerfError("seg_stats: expected d [n]")
+    n, dev = int(d.shape[0]), d.device
+    o = _offsets(off, n, "seg_stats: off")
+    thr = [float(t) for t in thresholds]
+    if len(thr) > 4:
+        raise _lib.ObjnerfError("seg_stats: at most 4 thresholds")
+    S = o.numel() - 1
+    if out is None:
+        out = torch.empty(S, 5 + len(thr), dtype=torch.float64, device=dev)
+    elif _req(out, torch.float64, "seg_stats: out") is not out or tuple(out.shape) != (S, 5 + len(thr)):
+        raise _lib.ObjnerfError("seg_stats: out must be contiguous [S, 5 + T]")
+    arr = (C.c_double * max(len(thr), 1))(*thr)
+    off_dev = o.to(dev)
+    check(lib().objnerf_seg_stats(n, S, _ptr(d) if n else None, _ptr(off_dev), len(thr), arr, _ptr(out), _stream()),
+          "objnerf_seg_stats")
+    return out
