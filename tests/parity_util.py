@@ -116,9 +116,11 @@ def oracle_step(fc, B, scale, b, feat, dtype=None, device="cpu", k_chunk=None, d
 
 
 def oracle_step_16(fc, B, scale, b, feat, operand_dtype, act16, grad_scale=1.0, round_head_weights=False,
-                   device="cpu", round_head_grads=False):
+                   device="cpu", round_head_grads=False, dtype=None, round_feat_head=False):
     """One iteration through the SPECIFICATION of the opt-in 16-bit modes (oracle.mlp_forward_stacked_16: operands of
-    every hidden nn.Linear rounded to the operand type, fp32 accumulation).  Same result dict as oracle_step."""
+    every hidden nn.Linear rounded to the operand type, fp32 accumulation).  Same result dict as oracle_step.
+    dtype=torch.float64: the same roundings with every accumulation (and the compositing and the loss) in fp64 -- what
+    is left between the two is the specification's own ambiguity, the order and width of its sums (spec_spread)."""
     K = B.shape[0]
     dev = torch.device(device)
     fcr = [_t(p, dev).clone().requires_grad_(True) for p in fc]
@@ -129,7 +131,8 @@ def oracle_step_16(fc, B, scale, b, feat, operand_dtype, act16, grad_scale=1.0, 
     loss, t = O.train_forward_loss(fcr, Br, sc, tb["pts"], tb["gt_depth"], tb["gt_rgb"], tb["labels"], tb["z"],
                                    gt_feat=tb["gt_feat"] if feat else None, return_terms=True, do_clip=bool(feat),
                                    operand_dtype=operand_dtype, act16=act16, grad_scale=grad_scale,
-                                   round_head_weights=round_head_weights, round_head_grads=round_head_grads)
+                                   round_head_weights=round_head_weights, round_head_grads=round_head_grads,
+                                   mlp_dtype=dtype, round_feat_head=round_feat_head)
     loss.backward()
     terms = torch.zeros(K, 4, dtype=torch.float64)
     for j, name in enumerate(["depth", "color", "opacity", "feat"]):
@@ -137,6 +140,58 @@ def oracle_step_16(fc, B, scale, b, feat, operand_dtype, act16, grad_scale=1.0, 
             terms[:, j] = t[name].detach().double().cpu()
     grads = [(p.grad if p.grad is not None else torch.zeros_like(p)).detach().cpu() for p in fcr + [Br]]
     return dict(loss=float(loss.item()), terms=terms, grads=grads, none_grad=[p.grad is None for p in fcr + [Br]])
+
+
+def spec_spread(o32, o64):
+    """Per gradient tensor, the relative distance between the 16-bit specification accumulated in fp32 and in fp64
+    (two oracle_step_16 results): how far two CORRECT implementations of it may lie apart."""
+    return [rel_norm(a, b) for a, b in zip(o32["grads"], o64["grads"])]
+
+
+# ---- the hidden-128 small-batch dispatch of objnerf_generic.hip, restated (tests assert which kernel a shape reaches)
+def sf_rays_per_wg(S, feat):
+    """objnerf_small_body.h:62-66."""
+    rpw = 80 // S
+    if feat and rpw > 5:
+        rpw = 64 // S
+    return rpw
+
+
+def small128_route(K, R, S, feat, mode="bf16", H=128, C=512, layerwise=False):
+    """Which kernels objgen::train_step runs for a hidden-H step of K objects x R rays x S samples.  Returns
+    ("A", RT, rpw, nwg): the one-launch iteration train_small_kernel<RT, mode == bf16, feat> (objnerf_generic.hip:2622-2634,
+    RT from train_step_small, :2502-2508); ("B", RT, 0, workgroups per object): mlp_fwd_small_kernel / mlp_bwd_small_kernel<RT>
+    (small_batch_rt, :1598-1611; launch grid :1565 / :1578); ("gemm", 0, 0, 0): the layer-wise GEMM chain.  In bf16 mode the
+    kernels are the BF = true instantiations on both routes (:2633 E.operands == 1; :2692 small_bf); in fp16 mode the
+    fp32 ones."""
+    n = R * S
+    half_acts = mode in ("bf16", "fp16") and H == 256 and n >= 4096          # acts16_shape, :2075 / :2615
+    if H == 128 and 4 <= S <= 64:
+        rpw = sf_rays_per_wg(S, feat)
+        nwg = (R + rpw - 1) // rpw
+        if (K * nwg <= 1536 and not half_acts and K <= 65535 and nwg * 63 <= n * 4 and nwg * (4 * H + 4) <= n * 129
+                and not (layerwise and K > 8) and (not feat or (C % 4 == 0 and R >= 1))):
+            return ("A", 4 if rpw * S <= 64 else 5, rpw, nwg)
+    if H != 128:
+        return ("gemm", 0, 0, 0)
+    for rt in range(1, 6):
+        if K * ((n + 16 * rt - 1) // (16 * rt)) <= 256:
+            return ("B", rt, 0, (n + 16 * rt - 1) // (16 * rt))
+    if mode != "fp16" and K * ((n + 79) // 80) <= 1024:
+        return ("B", 5, 0, (n + 79) // 80)
+    return ("gemm", 0, 0, 0)
+
+
+def guarded(t, guard_rows, fill, row_dims=2):
+    """A contiguous view of `t`'s values at the start of a LARGER storage whose tail -- guard_rows rows, a row being
+    everything behind the first `row_dims` dimensions -- holds `fill`: a kernel that reads past the end of its input
+    reads the guard."""
+    row = 1
+    for d in t.shape[row_dims:]:
+        row *= d
+    store = torch.full((t.numel() + guard_rows * row,), fill, dtype=t.dtype, device=t.device)
+    store[:t.numel()] = t.reshape(-1)
+    return store[:t.numel()].view(t.shape)
 
 
 def rel_norm(a, b):

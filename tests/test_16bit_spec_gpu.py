@@ -56,7 +56,8 @@ def test_layerwise_16bit_step_matches_its_specification(dev, mode, shape):
     K, R, n1, n2, H = shape
     if mode == "fp16" and H == 128 and R * (n1 + n2) < 20000:
         pytest.skip("small hidden-128 batches run the one-launch fp32 kernels in fp16 mode (objnerf_generic.hip "
-                    "small_batch_rt): nothing is rounded, test_hip_parity.py covers that path")
+                    "small_batch_rt): nothing is rounded, test_hip_parity.py covers that path and "
+                    "test_bf16_small_gpu.py::test_fp16_mode_runs_the_fp32_small_batch_kernels asserts this note")
     arena, st, b, ws, _ = _run(dev, K, R, n1, n2, H, False, mode)
     # hidden 256 with S a power of two in 32..256: the fused objnerf_train256.hip path -- activations ARE the next MFMA's
     # 16-bit operands, the heads and their gradients run on the matrix core too
@@ -86,7 +87,8 @@ def test_layerwise_16bit_feature_step_matches_its_specification(dev, mode, shape
     specification rounds W_of only (round_head_weights), hence the wider bound on the feature branch's tensors."""
     K, R, n1, n2, H = shape
     if mode == "fp16" and H == 128:
-        pytest.skip("small hidden-128 batches: fp32 kernels in fp16 mode")
+        pytest.skip("small hidden-128 batches: fp32 kernels in fp16 mode "
+                    "(asserted by test_bf16_small_gpu.py::test_fp16_mode_runs_the_fp32_small_batch_kernels)")
     arena, st, b, ws, _ = _run(dev, K, R, n1, n2, H, True, mode)
     act16 = H == 256 and R * (n1 + n2) >= 4096
     gs = 2.0 ** (math.floor(math.log2(R)) + 3) if mode == "fp16" else 1.0

@@ -80,7 +80,9 @@ def test_bf16_feature_step_close_to_fp32(golden, dev, shape):
 def test_bf16_background_step_close_to_fp32(dev, feat, net):
     """The layer-wise path with bf16 GEMM operands against its fp32 self: hidden 128 (the background network) and
     hidden 256 with >= 4096 samples per object (configs[4]: resident-panel GEMMs, the concatenated layers as one
-    contraction, activations stored in bf16 -- sized with the 16-bit bit of objnerf_train_workspace_bytes)."""
+    contraction, activations stored in bf16 -- sized with the 16-bit bit of objnerf_train_workspace_bytes).
+    (Its 15 % bar is no longer the only statement about the hidden-128 small-batch kernels this shape runs:
+    tests/test_bf16_small_gpu.py holds every bf16 instantiation of them to the operand-rounded specification at 1 %.)"""
     from openobj_amd import init as obj_init
     K, R, H = net
     n1, n2 = 16, 48
