@@ -8,6 +8,7 @@
 #include "objnerf_device.h"
 #include "../../include/objnerf_hip.h"
 #include "objnerf_generic.h"
+#include "objnerf_step_tail.h"
 
 namespace objgen {
 
@@ -799,8 +800,8 @@ struct RedItem {
 // Optional tail of the step's reduction launch (the one-launch small-batch iteration, objnerf_small_body.h): the block
 // after the last item's sums the per-workgroup loss terms in workgroup order and WRITES the status word
 // (loss_total_kernel's job), and -- with params set -- every thread that has just summed a gradient element applies
-// torch.optim.AdamW to it (adamw_dyn_kernel's arithmetic, objnerf_misc.hip; the flag-dependent skipping and the
-// per-group step counters included), so the iteration has no optimiser launch and the gradient is not read back.
+// torch.optim.AdamW to it (objnerf_step_tail.h; the flag-dependent skipping and the per-group step counters
+// included), so the iteration has no optimiser launch and the gradient is not read back.
 struct RedTail {
   const float* loss_part = nullptr; int loss_blocks, K; float* loss_terms; int* status;      // loss_part == NULL: no tail
   float* params = nullptr; const float* grads; float* m; float* v; const int* flags; int* steps; int bank;   // params == NULL: no AdamW
@@ -826,16 +827,11 @@ __global__ __launch_bounds__(256) void reduce_parts_kernel(const RedGroup gr) {
   const bool tail_block = (int)blockIdx.x == gr.beg[gr.count];      // (only launched when the tail is set)
   if (tl.params && threadIdx.x < 3) {
     const int g = threadIdx.x;
-    const bool f0 = tl.flags[0] != 0, f1 = tl.flags[1] != 0;
-    s_active[g] = g == 0 ? !(f0 && f1) : !f0;
-    const int old = tl.steps[3 * tl.bank + g];
-    const double st = (double)(old + 1);
-    s_step_size[g] = (float)(tl.lr / (1.0 - pow(tl.b1, st)));
-    s_bc2_sqrt[g] = (float)sqrt(1.0 - pow(tl.b2, st));
-    if (tail_block) tl.steps[3 * (1 - tl.bank) + g] = old + (s_active[g] ? 1 : 0);
+    adamw_group_begin(g, tl.flags[0] != 0, tl.flags[1] != 0, tl.steps, tl.bank, tl.lr, tl.b1, tl.b2, tail_block,
+                      s_active[g], s_step_size[g], s_bc2_sqrt[g]);
   }
   if (tail_block) {
-    // the objects' loss terms from the workgroups' partial sums, in workgroup order; status as loss_total_kernel
+    // the objects' loss terms from the workgroups' partial sums, in workgroup order, and their status bits
     __shared__ int s_bad;
     if (threadIdx.x == 0) s_bad = 0;
     __syncthreads();
@@ -851,8 +847,7 @@ __global__ __launch_bounds__(256) void reduce_parts_kernel(const RedGroup gr) {
       for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
       if (lane == 0) {
         tl.loss_terms[e] = v;
-        if (v > 100000.f) bad |= 1;                 // render_rays.py:109-111
-        if (!(fabsf(v) <= 3.0e38f)) bad |= 2;       // NaN / Inf
+        bad |= loss_status_bits(v);
       }
     }
     if (bad) atomicOr(&s_bad, bad);
@@ -898,20 +893,11 @@ __global__ __launch_bounds__(256) void reduce_parts_kernel(const RedGroup gr) {
     *dst = sum;
     const long idx = dst - tl.grads;                         // position in the gradient arena = in params / moments
     if (tl.params && idx >= 0 && idx < tl.arena_floats) {    // (the 512-d head's moment sums go to the workspace)
-      const long pi = idx % tl.p_stride;
-      const int g = (pi >= tl.lo1 && pi < tl.lo2) ? 1 : ((pi >= tl.lo2 && pi < tl.hi2) ? 2 : 0);
+      const int g = adamw_group_of(idx % tl.p_stride, tl.lo1, tl.lo2, tl.hi2);
       if (s_active[g]) {
-        const float decay = (float)(1.0 - tl.lr * tl.wd), w1 = (float)(1.0 - tl.b1), w2 = (float)(1.0 - tl.b2);
-        const float beta2 = (float)tl.b2;
-        float p = tl.params[idx] * decay;
-        const float mo = tl.m[idx];
-        const float mn = mo + w1 * (sum - mo);
-        const float vn = tl.v[idx] * beta2 + (w2 * sum) * sum;
-        const float denom = sqrtf(vn) / s_bc2_sqrt[g] + tl.eps;
-        p = p + (-s_step_size[g]) * (mn / denom);
-        tl.params[idx] = p;
-        tl.m[idx] = mn;
-        tl.v[idx] = vn;
+        float decay, w1, beta2, w2;
+        adamw_coeffs(tl.lr, tl.b1, tl.b2, tl.wd, decay, w1, beta2, w2);
+        adamw_update(tl.params, tl.m, tl.v, idx, sum, decay, w1, beta2, w2, s_step_size[g], s_bc2_sqrt[g], tl.eps);
       }
     }
   }
@@ -1850,13 +1836,10 @@ __global__ void copy_cols_kernel(long rows, int cols, const float* src, long lds
 // ------------------------------------------------------------------------------------------------
 // Feature-distillation branch with the 512-d head hoisted past the compositing, any hidden width Hh
 // (the hidden-32 fused kernel has its own copies in objnerf_train.hip).
-// beta[r] = b_of . g[r], |g[r]| into rayin[r][Hh], [Hh + 1]  (u = W_of^T g is a GEMM): 16 lanes per ray
-__global__ __launch_bounds__(256) void featg_rowstats_kernel(const float* params, long p_stride, int off_b, int C, int R,
-                                                             int rin_ld, const float* gt_feat, float* rayin) {
-  const int k = blockIdx.y;
-  const int l16 = threadIdx.x & 15;
-  const long r = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
-  const float* B = params + (long)k * p_stride + off_b;
+// beta = b_of . g, |g| of ray r of object k (gt_feat [K][R][C]) into the last two columns of its rayin record  (u =
+// W_of^T g is a GEMM): the 16 lanes of a DPP row share the ray
+__device__ __forceinline__ void featg_ray_stats(const float* B, const int C, const int R, const float* gt_feat,
+                                                float* rayin, const int rin_ld, const int k, const long r, const int l16) {
   float bs = 0.f, gs = 0.f;
   if (r < R) {
     const float* gp = gt_feat + ((long)k * R + r) * C;
@@ -1874,15 +1857,27 @@ __global__ __launch_bounds__(256) void featg_rowstats_kernel(const float* params
     o[rin_ld - 1] = sqrtf(gs);
   }
 }
-// wb = W_of^T b_of, bb = b_of . b_of appended to the Gram matrix: gram[k][Hh * Hh + h], [Hh * Hh + Hh]
+__global__ __launch_bounds__(256) void featg_rowstats_kernel(const float* params, long p_stride, int off_b, int C, int R,
+                                                             int rin_ld, const float* gt_feat, float* rayin) {
+  const int k = blockIdx.y;
+  const int l16 = threadIdx.x & 15;
+  const long r = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  featg_ray_stats(params + (long)k * p_stride + off_b, C, R, gt_feat, rayin, rin_ld, k, r, l16);
+}
+// Entry h of [wb | bb], wb = W_of^T b_of (h < Hh), bb = b_of . b_of (h == Hh): one wave per entry
+__device__ __forceinline__ float featg_wb_entry(const float* W, const float* B, const int C, const int Hh, const int h,
+                                                const int lane) {
+  float acc = 0.f;
+  for (int cc = lane; cc < C; cc += 64) acc = fmaf(h < Hh ? W[(long)cc * Hh + h] : B[cc], B[cc], acc);
+  return wave_sum64(acc);
+}
+// [wb | bb] appended to the Gram matrix: gram[k][Hh * Hh + h], [Hh * Hh + Hh]
 __global__ __launch_bounds__(64) void featg_wb_kernel(const float* params, long p_stride, int off_w, int off_b, int C,
                                                       int Hh, float* gram, long gstride) {
-  const int k = blockIdx.y, h = blockIdx.x;            // one wave per entry h (h == Hh: bb)
+  const int k = blockIdx.y, h = blockIdx.x;
   const float* W = params + (long)k * p_stride + off_w;
   const float* B = params + (long)k * p_stride + off_b;
-  float acc = 0.f;
-  for (int cc = threadIdx.x; cc < C; cc += 64) acc = fmaf(h < Hh ? W[(long)cc * Hh + h] : B[cc], B[cc], acc);
-  acc = wave_sum64(acc);
+  const float acc = featg_wb_entry(W, B, C, Hh, h, threadIdx.x);
   if (threadIdx.x == 0) gram[(long)k * gstride + (long)Hh * Hh + h] = acc;
 }
 // X1 = [a fh | a O], X2 = [c fh | c O] from rayfeat rows (fh[Hh], O, a, c)
@@ -1897,18 +1892,10 @@ __global__ void featg_scale_kernel(long n, int Hh, const float* rayfeat, float* 
   X1[i] = rf[Hh + 1] * v;
   X2[i] = rf[Hh + 2] * v;
 }
-// d W_of[c][h] = T[c][h] + sum_j W_of[c][j] M[j][h] + b_of[c] M[Hh][h];  d b_of[c] = T[c][Hh] + W_of[c] . M[Hh][:] + b_of[c] M[Hh][Hh]
-__global__ __launch_bounds__(256) void featg_finish_kernel(const float* params, long p_stride, int off_w, int off_b, int C,
-                                                           int Hh, const float* Tm, const float* mom, float* grads) {
-  const int XC = Hh + 1;
-  const int k = blockIdx.y;
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long)C * XC) return;
-  const int cc = (int)(i / XC), hh = (int)(i - (long)cc * XC);
-  const float* W = params + (long)k * p_stride + off_w + (long)cc * Hh;
-  const float bc = params[(long)k * p_stride + off_b + cc];
-  const float* M = mom + (long)k * XC * XC;
-  float v = Tm[(long)k * C * XC + i];
+// Entry (c, hh) of the head's gradient from row c of W_of, b_c = b_of[c], the rays' moments M [XC][XC] and t = T[c][hh]:
+// d W_of[c][h] = T[c][h] + sum_j W_of[c][j] M[j][h] + b_of[c] M[Hh][h];  d b_of[c] (hh == Hh) = T[c][Hh] + W_of[c] . M[Hh][:] + b_of[c] M[Hh][Hh]
+__device__ __forceinline__ float featg_head_grad(const float* W, const float bc, const float* M, float v, const int hh,
+                                                 const int Hh, const int XC) {
   // four partial sums: the loads of four steps are in flight together (Hh is a multiple of 32)
   float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
   if (hh < Hh) {
@@ -1918,8 +1905,6 @@ __global__ __launch_bounds__(256) void featg_finish_kernel(const float* params, 
       v2 = fmaf(W[j + 2], M[(long)(j + 2) * XC + hh], v2);
       v3 = fmaf(W[j + 3], M[(long)(j + 3) * XC + hh], v3);
     }
-    v += (v0 + v1) + (v2 + v3);
-    grads[(long)k * p_stride + off_w + (long)cc * Hh + hh] = fmaf(bc, M[(long)Hh * XC + hh], v);
   } else {
     for (int j = 0; j < Hh; j += 4) {
       v0 = fmaf(W[j], M[(long)Hh * XC + j], v0);
@@ -1927,12 +1912,25 @@ __global__ __launch_bounds__(256) void featg_finish_kernel(const float* params, 
       v2 = fmaf(W[j + 2], M[(long)Hh * XC + j + 2], v2);
       v3 = fmaf(W[j + 3], M[(long)Hh * XC + j + 3], v3);
     }
-    v += (v0 + v1) + (v2 + v3);
-    grads[(long)k * p_stride + off_b + cc] = fmaf(bc, M[(long)Hh * XC + Hh], v);
   }
+  v += (v0 + v1) + (v2 + v3);
+  return fmaf(bc, M[(long)Hh * XC + hh], v);
+}
+// The head's gradient, one thread per entry of [d W_of (C x Hh) | d b_of (C)] in the order (c, hh)
+__global__ __launch_bounds__(256) void featg_finish_kernel(const float* params, long p_stride, int off_w, int off_b, int C,
+                                                           int Hh, const float* Tm, const float* mom, float* grads) {
+  const int XC = Hh + 1;
+  const int k = blockIdx.y;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)C * XC) return;
+  const int cc = (int)(i / XC), hh = (int)(i - (long)cc * XC);
+  const float* W = params + (long)k * p_stride + off_w + (long)cc * Hh;
+  const float bc = params[(long)k * p_stride + off_b + cc];
+  const float gr = featg_head_grad(W, bc, mom + (long)k * XC * XC, Tm[(long)k * C * XC + i], hh, Hh, XC);
+  grads[(long)k * p_stride + (hh < Hh ? off_w + (long)cc * Hh + hh : off_b + cc)] = gr;
 }
 
-// FeatPrepTask (512 threads per workgroup): featg_wb_kernel's, featg_rowstats_kernel's arithmetic and the [W_of | b_of] copy.
+// FeatPrepTask (512 threads per workgroup): featg_wb_kernel's, featg_rowstats_kernel's work and the [W_of | b_of] copy.
 // b = (object, pass-local index)
 __device__ void feat_prep_task(const FeatPrepTask& t, int b) {
   const int per = t.nb_wb + t.nb_rs + t.nb_snap;
@@ -1944,9 +1942,7 @@ __device__ void feat_prep_task(const FeatPrepTask& t, int b) {
   if (b < t.nb_wb) {                                       // wb[h] = W_of[:, h] . b_of (h < Hh), bb = b_of . b_of: a wave per entry
     const int h = 8 * b + wv;
     if (h <= t.Hh) {
-      float acc = 0.f;
-      for (int cc = lane; cc < t.C; cc += 64) acc = fmaf(h < t.Hh ? W[(long)cc * t.Hh + h] : B[cc], B[cc], acc);
-      acc = wave_sum64(acc);
+      const float acc = featg_wb_entry(W, B, t.C, t.Hh, h, lane);
       if (lane == 0) t.gram[(long)k * t.gstride + (long)t.Hh * t.Hh + h] = acc;
     }
     return;
@@ -1955,22 +1951,7 @@ __device__ void feat_prep_task(const FeatPrepTask& t, int b) {
   if (b < t.nb_rs) {                                       // beta, |g| of 32 rays: 16 lanes per ray
     const int l16 = tid & 15;
     const long r = (long)b * 32 + (tid >> 4);
-    float bs = 0.f, gs = 0.f;
-    if (r < t.R) {
-      const float* gp = t.gt_feat + ((long)k * t.R + r) * t.C;
-      for (int cc = l16; cc < t.C; cc += 16) {
-        const float gv = gp[cc];
-        bs = fmaf(B[cc], gv, bs);
-        gs = fmaf(gv, gv, gs);
-      }
-    }
-    bs = dpp_rowsum16(bs);
-    gs = dpp_rowsum16(gs);
-    if (r < t.R && l16 == 0) {
-      float* o = t.rayin + ((long)k * t.R + r) * t.rin_ld;
-      o[t.rin_ld - 2] = bs;
-      o[t.rin_ld - 1] = sqrtf(gs);
-    }
+    featg_ray_stats(B, t.C, t.R, t.gt_feat, t.rayin, t.rin_ld, k, r, l16);
     return;
   }
   b -= t.nb_rs;
@@ -1983,10 +1964,10 @@ __device__ void feat_prep_task(const FeatPrepTask& t, int b) {
 }
 // featg_finish_kernel + the head's AdamW in one launch (the one-launch background iteration with an optimiser attached):
 // the entry's gradient is formed from the COPY of [W_of | b_of] (FeatPrepTask; a gradient needs a whole row of W_of that
-// other threads of this launch are stepping) and stepped at once -- adamw_dyn_kernel's arithmetic for the feature group
-// [lo2, hi2), whose counter the reduction launch has already advanced in the other bank.
+// other threads of this launch are stepping) and stepped at once as the feature group [lo2, hi2) (objnerf_step_tail.h),
+// whose counter the reduction launch has already advanced in the other bank.
 struct FeatFinishOpt {
-  float* params; float* m; float* v; const int* flags; const int* steps; int bank;
+  float* params; float* m; float* v; const int* flags; int* steps; int bank;      // (steps: read only)
   double lr, b1, b2, wd; float eps;
 };
 __global__ __launch_bounds__(256) void featg_finish_adamw_kernel(const float* snap, long p_stride, int off_w, int off_b, int C,
@@ -1996,57 +1977,21 @@ __global__ __launch_bounds__(256) void featg_finish_adamw_kernel(const float* sn
   const int k = blockIdx.y;
   __shared__ float s_step, s_bc2;
   __shared__ int s_act;
-  if (threadIdx.x == 0) {
-    const bool f0 = o.flags[0] != 0;
-    s_act = !f0;                                           // (group 2 of adamw_dyn_kernel: skipped when no ray has label 1)
-    const double st = (double)(o.steps[3 * o.bank + 2] + 1);
-    s_step = (float)(o.lr / (1.0 - pow(o.b1, st)));
-    s_bc2 = (float)sqrt(1.0 - pow(o.b2, st));
-  }
+  if (threadIdx.x == 0)      // (group 2: skipped when no ray has label 1)
+    adamw_group_begin(2, o.flags[0] != 0, o.flags[1] != 0, o.steps, o.bank, o.lr, o.b1, o.b2, false, s_act, s_step, s_bc2);
   __syncthreads();
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long)C * XC) return;
   const int cc = (int)(i / XC), hh = (int)(i - (long)cc * XC);
   const float* hs = snap + (long)k * ((long)C * XC);
-  const float* W = hs + (long)cc * Hh;
-  const float bc = hs[(long)C * Hh + cc];
-  const float* M = mom + (long)k * XC * XC;
-  float v = Tm[(long)k * C * XC + i];
-  float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f, gr;
-  long idx;
-  if (hh < Hh) {
-    for (int j = 0; j < Hh; j += 4) {
-      v0 = fmaf(W[j], M[(long)j * XC + hh], v0);
-      v1 = fmaf(W[j + 1], M[(long)(j + 1) * XC + hh], v1);
-      v2 = fmaf(W[j + 2], M[(long)(j + 2) * XC + hh], v2);
-      v3 = fmaf(W[j + 3], M[(long)(j + 3) * XC + hh], v3);
-    }
-    v += (v0 + v1) + (v2 + v3);
-    gr = fmaf(bc, M[(long)Hh * XC + hh], v);
-    idx = (long)k * p_stride + off_w + (long)cc * Hh + hh;
-  } else {
-    for (int j = 0; j < Hh; j += 4) {
-      v0 = fmaf(W[j], M[(long)Hh * XC + j], v0);
-      v1 = fmaf(W[j + 1], M[(long)Hh * XC + j + 1], v1);
-      v2 = fmaf(W[j + 2], M[(long)Hh * XC + j + 2], v2);
-      v3 = fmaf(W[j + 3], M[(long)Hh * XC + j + 3], v3);
-    }
-    v += (v0 + v1) + (v2 + v3);
-    gr = fmaf(bc, M[(long)Hh * XC + Hh], v);
-    idx = (long)k * p_stride + off_b + cc;
-  }
+  const float gr = featg_head_grad(hs + (long)cc * Hh, hs[(long)C * Hh + cc], mom + (long)k * XC * XC,
+                                   Tm[(long)k * C * XC + i], hh, Hh, XC);
+  const long idx = (long)k * p_stride + (hh < Hh ? off_w + (long)cc * Hh + hh : off_b + cc);
   grads[idx] = gr;
   if (s_act) {
-    const float decay = (float)(1.0 - o.lr * o.wd), w1 = (float)(1.0 - o.b1), w2 = (float)(1.0 - o.b2), beta2 = (float)o.b2;
-    float p = o.params[idx] * decay;
-    const float mo = o.m[idx];
-    const float mn = mo + w1 * (gr - mo);
-    const float vn = o.v[idx] * beta2 + (w2 * gr) * gr;
-    const float denom = sqrtf(vn) / s_bc2 + o.eps;
-    p = p + (-s_step) * (mn / denom);
-    o.params[idx] = p;
-    o.m[idx] = mn;
-    o.v[idx] = vn;
+    float decay, w1, beta2, w2;
+    adamw_coeffs(o.lr, o.b1, o.b2, o.wd, decay, w1, beta2, w2);
+    adamw_update(o.params, o.m, o.v, idx, gr, decay, w1, beta2, w2, s_step, s_bc2, o.eps);
   }
 }
 

@@ -8,6 +8,7 @@
 #include "objnerf_device.h"
 #include "objnerf_philox.h"
 #include "objnerf_wg.h"
+#include "objnerf_step_tail.h"
 
 namespace {
 
@@ -64,8 +65,9 @@ __global__ __launch_bounds__(256) void reduce_loss_kernel(int R, const float* lo
   if (threadIdx.x == 0) {
     const float m = zero ? 0.0f : red[0] / ((float)counts[k] + 1e-10f);
     out[k] = m;
-    if (m > 100000.0f) atomicOr(status, 1);
-    if (!(fabsf(m) <= 3.0e38f)) atomicOr(status, 2);   // NaN / Inf: reported, not fatal
+    const int bad = loss_status_bits(m);
+    if (bad & 1) atomicOr(status, 1);
+    if (bad & 2) atomicOr(status, 2);
   }
 }
 

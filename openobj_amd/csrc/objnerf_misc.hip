@@ -6,6 +6,7 @@
 #include "objnerf_philox.h"
 #include "objnerf_wg.h"
 #include "objnerf_generic.h"
+#include "objnerf_step_tail.h"
 
 namespace {
 
@@ -382,9 +383,7 @@ __global__ void loss_total_kernel(int K, float* terms, float cs, float os, float
     int bad = 0;
     for (int k = 0; k < K; ++k) {
       const float d = terms[4 * k], c = terms[4 * k + 1], o = terms[4 * k + 2], f = terms[4 * k + 3];
-      if (d > 100000.f || c > 100000.f || o > 100000.f || f > 100000.f) bad |= 1;        // render_rays.py:109-111
-      if (!(fabsf(d) <= 3.0e38f && fabsf(c) <= 3.0e38f && fabsf(o) <= 3.0e38f && fabsf(f) <= 3.0e38f))
-        bad |= 2;   // NaN / Inf: reported, NOT fatal (the reference's `> 100000` is false for NaN and it carries on)
+      bad |= loss_status_bits(d) | loss_status_bits(c) | loss_status_bits(o) | loss_status_bits(f);
       t += d + c * cs + o * os + f * fs;
     }
     if (total) *total = t;
@@ -401,58 +400,31 @@ __global__ void adamw_kernel(long P, long p_stride, float* params, const float* 
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P || (has_grad && !has_grad[i])) return;
   const long idx = (long)blockIdx.y * p_stride + i;
-  const float g = grads[idx];
-  float p = params[idx] * decay;
-  const float mo = m[idx];
-  const float mn = mo + w1 * (g - mo);
-  const float vn = v[idx] * beta2 + (w2 * g) * g;
-  const float denom = sqrtf(vn) / bc2_sqrt + eps;
-  p = p + (-step_size) * (mn / denom);
-  params[idx] = p;
-  m[idx] = mn;
-  v[idx] = vn;
+  adamw_update(params, m, v, idx, grads[idx], decay, w1, beta2, w2, step_size, bc2_sqrt, eps);
 }
 
 // The same with the "did this tensor receive a gradient?" decision made ON THE DEVICE from the iteration's early-return
-// flags (render_rays.py:89-94).  When the label-1 masks trigger the early return, the depth / colour / feature terms are
-// constants: the colour and feature branches get .grad = None and torch.optim.AdamW skips them entirely (no decay, no
-// moment update, and their per-parameter step count does not advance); with both flags set nothing has a gradient.
-// Three groups with their own step counters (device int32[3]): 0 = trunk + density head + B, 1 = colour branch
-// [lo1, lo2), 2 = feature branch [lo2, hi2).
+// flags (render_rays.py:89-94): when the label-1 masks trigger the early return, the depth / colour / feature terms are
+// constants.  Three groups with their own step counters (adamw_group_of, adamw_group_begin; objnerf_step_tail.h).
 __global__ void adamw_dyn_kernel(long P, long p_stride, float* params, const float* grads, float* m, float* v,
                                  const uint8_t* has_grad, const int* flags, int* steps, int bank, long lo1, long lo2,
                                  long hi2, double lr, double b1, double b2, float eps, double wd, long ng_lo, long ng_hi) {
-  // step counters: two banks of three; this call READS bank `bank` and its first block WRITES the advanced counters to
-  // the other one -- no second launch, and no block can see a counter of its own call already advanced
   __shared__ float s_step_size[3], s_bc2_sqrt[3];
   __shared__ int s_active[3];
   if (threadIdx.x < 3) {
     const int g = threadIdx.x;
-    const bool f0 = flags[0] != 0, f1 = flags[1] != 0;
-    s_active[g] = g == 0 ? !(f0 && f1) : !f0;
-    const int old = steps[3 * bank + g];
-    const double st = (double)(old + 1);
-    s_step_size[g] = (float)(lr / (1.0 - pow(b1, st)));
-    s_bc2_sqrt[g] = (float)sqrt(1.0 - pow(b2, st));
-    if (blockIdx.x == 0 && blockIdx.y == 0) steps[3 * (1 - bank) + g] = old + (s_active[g] ? 1 : 0);
+    adamw_group_begin(g, flags[0] != 0, flags[1] != 0, steps, bank, lr, b1, b2, blockIdx.x == 0 && blockIdx.y == 0,
+                      s_active[g], s_step_size[g], s_bc2_sqrt[g]);
   }
   __syncthreads();
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P || (has_grad && !has_grad[i]) || (i >= ng_lo && i < ng_hi)) return;
-  const int g = (i >= lo1 && i < lo2) ? 1 : ((i >= lo2 && i < hi2) ? 2 : 0);
+  const int g = adamw_group_of(i, lo1, lo2, hi2);
   if (!s_active[g]) return;
-  const float decay = (float)(1.0 - lr * wd), w1 = (float)(1.0 - b1), w2 = (float)(1.0 - b2), beta2 = (float)b2;
+  float decay, w1, beta2, w2;
+  adamw_coeffs(lr, b1, b2, wd, decay, w1, beta2, w2);
   const long idx = (long)blockIdx.y * p_stride + i;
-  const float gr = grads[idx];
-  float p = params[idx] * decay;
-  const float mo = m[idx];
-  const float mn = mo + w1 * (gr - mo);
-  const float vn = v[idx] * beta2 + (w2 * gr) * gr;
-  const float denom = sqrtf(vn) / s_bc2_sqrt[g] + eps;
-  p = p + (-s_step_size[g]) * (mn / denom);
-  params[idx] = p;
-  m[idx] = mn;
-  v[idx] = vn;
+  adamw_update(params, m, v, idx, grads[idx], decay, w1, beta2, w2, s_step_size[g], s_bc2_sqrt[g], eps);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #include "objnerf_train_common.h"
 #include "objnerf_generic.h"
 #include "objnerf_wg.h"
+#include "objnerf_step_tail.h"
 
 using namespace obj32;
 using namespace objtrain;
@@ -34,7 +35,7 @@ struct EvalDev {
 // ------------------------------------------------------------------------------------------------
 // The step's last launch: grads[k][i] = sum_g slab[k][g][i] for every entry this configuration differentiates,
 // loss_terms[k][:] = sum_g loss_part, the status word -- and, with an optimiser attached (objnerf_train_args.optim),
-// torch.optim.AdamW on the element just summed (adamw_dyn_kernel's arithmetic; objnerf_misc.hip).
+// torch.optim.AdamW on the element just summed (adamw_update; objnerf_step_tail.h).
 // No byte mask and no zero fill: [ng_lo, ng_hi) are the entries WITHOUT a gradient (the feature branch when gt_feat is
 // NULL: .grad stays None, train.py:435-438), [ext_lo, ext_hi) the entries whose gradient another kernel has already
 // written to `grads` (the 512-d head: feat_finish_kernel).  Block (0, 0) also sums the loss terms of ALL objects and
@@ -73,26 +74,17 @@ __global__ __launch_bounds__(256) void finalize_kernel(const FinalizeArgs a) {
   __shared__ float s_M[XCOLS * XCOLS];
   const bool first = blockIdx.x == 0 && blockIdx.y == 0;
   if (a.counts_in && first && threadIdx.x == 64) {     // derived flags: published for the host / later launches
-    int e0 = 0, e1 = 0;
-    for (int kk = 0; kk < a.K; ++kk) { e0 |= a.counts_in[2 * kk] == 0; e1 |= a.counts_in[2 * kk + 1] == 0; }
+    int e0, e1;
+    early_flags_of_counts(a.counts_in, a.K, e0, e1);
     a.flags_out[0] = e0; a.flags_out[1] = e1;
   }
-  if (a.params && threadIdx.x < 3) {          // (as adamw_dyn_kernel: read bank `bank`, the first block writes the other)
+  if (a.params && threadIdx.x < 3) {
     const int g = threadIdx.x;
-    bool f0, f1;
-    if (a.counts_in) {
-      int e0 = 0, e1 = 0;
-      for (int kk = 0; kk < a.K; ++kk) { e0 |= a.counts_in[2 * kk] == 0; e1 |= a.counts_in[2 * kk + 1] == 0; }
-      f0 = e0 != 0; f1 = e1 != 0;
-    } else {
-      f0 = a.flags[0] != 0; f1 = a.flags[1] != 0;
-    }
-    s_active[g] = g == 0 ? !(f0 && f1) : !f0;
-    const int old = a.steps[3 * a.bank + g];
-    const double st = (double)(old + 1);
-    s_step_size[g] = (float)(a.lr / (1.0 - pow(a.b1, st)));
-    s_bc2_sqrt[g] = (float)sqrt(1.0 - pow(a.b2, st));
-    if (first) a.steps[3 * (1 - a.bank) + g] = old + (s_active[g] ? 1 : 0);
+    int e0, e1;
+    if (a.counts_in) early_flags_of_counts(a.counts_in, a.K, e0, e1);
+    else { e0 = a.flags[0]; e1 = a.flags[1]; }
+    adamw_group_begin(g, e0 != 0, e1 != 0, a.steps, a.bank, a.lr, a.b1, a.b2, first, s_active[g], s_step_size[g],
+                      s_bc2_sqrt[g]);
   }
   if (first && threadIdx.x == 0) s_bad = 0;
   // the head's moments (workgroups that hold entries of [ext_lo, ext_hi) only): M = sum of the chunks' partials, in chunk order
@@ -165,18 +157,11 @@ __global__ __launch_bounds__(256) void finalize_kernel(const FinalizeArgs a) {
     const float sv_ = s[e];
     if (slabbed[e] || a.Tpart) a.grads[idx] = sv_;
     if (a.params) {
-      const int g = (i >= a.lo1 && i < a.lo2) ? 1 : ((i >= a.lo2 && i < a.hi2) ? 2 : 0);
+      const int g = adamw_group_of(i, a.lo1, a.lo2, a.hi2);
       if (s_active[g]) {
-        const float decay = (float)(1.0 - a.lr * a.wd), w1 = (float)(1.0 - a.b1), w2 = (float)(1.0 - a.b2), beta2 = (float)a.b2;
-        float p = a.params[idx] * decay;
-        const float mo = a.m[idx];
-        const float mn = mo + w1 * (sv_ - mo);
-        const float vn = a.v[idx] * beta2 + (w2 * sv_) * sv_;
-        const float denom = sqrtf(vn) / s_bc2_sqrt[g] + a.eps;
-        p = p + (-s_step_size[g]) * (mn / denom);
-        a.params[idx] = p;
-        a.m[idx] = mn;
-        a.v[idx] = vn;
+        float decay, w1, beta2, w2;
+        adamw_coeffs(a.lr, a.b1, a.b2, a.wd, decay, w1, beta2, w2);
+        adamw_update(a.params, a.m, a.v, idx, sv_, decay, w1, beta2, w2, s_step_size[g], s_bc2_sqrt[g], a.eps);
       }
     }
   }
@@ -192,8 +177,7 @@ __global__ __launch_bounds__(256) void finalize_kernel(const FinalizeArgs a) {
       float sl = 0.f;
       for (int g = 0; g < Gk; ++g) sl += a.loss_part[((long)kk * stride + g) * 4 + (e & 3)];
       a.loss_terms[e] = sl;
-      if (sl > 100000.0f) bad |= 1;          // render_rays.py:109-111
-      if (!(fabsf(sl) <= 3.0e38f)) bad |= 2;   // NaN / Inf (the reference carries on with NaN parameters)
+      bad |= loss_status_bits(sl);
     }
     if (bad) atomicOr(&s_bad, bad);
     __syncthreads();

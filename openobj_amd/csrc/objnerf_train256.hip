@@ -34,6 +34,7 @@
 #include <type_traits>
 #include "objnerf_device.h"
 #include "objnerf_generic.h"
+#include "objnerf_step_tail.h"
 
 namespace obj256 {
 
@@ -2076,8 +2077,9 @@ __global__ __launch_bounds__(256) void finalize256_kernel(const FinArgs a) {
     if (threadIdx.x < (a.feat ? 4 : 3))
       for (int g = 0; g < NWG_A; ++g) sl += a.part[((long)k * NWG_A + g) * PART_FLOATS + 64 + threadIdx.x];
     a.loss_terms[k * 4 + threadIdx.x] = sl;
-    if (sl > 100000.0f) atomicOr(a.status, 1);           // render_rays.py:109-111
-    if (!(fabsf(sl) <= 3.0e38f)) atomicOr(a.status, 2);  // NaN / Inf: reported, not fatal (same word as finalize_kernel)
+    const int bad = loss_status_bits(sl);                // (same word as finalize_kernel)
+    if (bad & 1) atomicOr(a.status, 1);
+    if (bad & 2) atomicOr(a.status, 2);
   }
 }
 
