@@ -879,6 +879,44 @@ int objnerf_nearest(int64_t nr, int64_t nq, int32_t S, const double* ref, const 
 int objnerf_seg_stats(int64_t n, int32_t S, const double* d, const int64_t* off, int32_t T, const double* thresholds,
                       double* out, void* stream);
 
+/* Culling meshes to what the frames of a sequence observed (objnerf_meshcull.hip; openobj_amd/map_cull.py, DESIGN.md
+ * 4.22): the step before accuracy / completion in vMAP's, iMAP's and NICE-SLAM's evaluations; the reference has no
+ * counterpart.  Added under ABI 14: the four entries below are purely additive, so OBJNERF_ABI_VERSION stays 14.
+ *
+ * objnerf_vertex_views: views[v] += the number of frames of the batch that see vertex v (views [V] int32, in / out: the
+ * caller zeroes it once and streams a sequence through in batches).  verts [V][3] fp64 world coordinates, t_cw [B][3][4]
+ * fp64 = the upper 3 x 4 of inverse(T_WC) per frame (inverted by the caller), depth [B][W][H] fp32 metres, 0 = invalid.
+ * Per vertex p and frame, in fp64, every operation rounded once and in this order, M = t_cw[f]:
+ *   xc = ((M[0] px + M[1] py) + M[2] pz) + M[3]      (yc: M[4..7], zc: M[8..11])
+ *   front  = zc > z_min
+ *   u = (fx xc) / zc + cx,  v = (fy yc) / zc + cy,  iu = floor(u + 0.5),  iv = floor(v + 0.5)
+ *   inside = front and margin <= iu <= W - 1 - margin and margin <= iv <= H - 1 - margin       (compared as doubles)
+ *   seen   = inside and d > 0 and zc <= d + eps,  d = (double) depth[f][iu][iv]
+ * A NaN or infinite coordinate makes every comparison false: the vertex is never seen and nothing is converted to an
+ * integer or dereferenced before `inside` holds.  margin >= 0.  No atomics: a thread owns a vertex.
+ *
+ * objnerf_mesh_cull_count / _emit: the sub-mesh a vertex mask keeps.  keep_v [V] uint8 (non-zero = kept), faces [F][3]
+ * int32.  A face stays iff all three (OBJNERF_CULL_ALL) or at least one (OBJNERF_CULL_ANY) of its corners are kept; the
+ * output holds the kept faces in their original order and exactly the vertices those faces use, in ascending original
+ * order (under ANY that includes corners that are not kept; a vertex no kept face uses is dropped under either rule).
+ * A face that names a vertex outside [0, V) is never dereferenced: it is dropped and sets status bit 0.  Degenerate and
+ * repeated faces pass through.  count: counts [2] int64 = (Vn, Fn) and status (one int32, cleared here), both on the
+ * device; ws: objnerf_mesh_cull_workspace_bytes(V, F), handed on to emit unchanged.  emit (same V, F, rule, keep_v,
+ * faces; Vn, Fn as counted): new_of_old [V] int32 (-1 = dropped), old_of_new [Vn] int32, faces_out [Fn][3] int32
+ * re-indexed, face_old [Fn] int32 = the original row of each kept face.  Integers only, no atomics: two calls write the
+ * same bytes. */
+#define OBJNERF_CULL_ALL 0
+#define OBJNERF_CULL_ANY 1
+int objnerf_vertex_views(int64_t V, int32_t B, int32_t W, int32_t H, const double* verts, const double* t_cw,
+                         const float* depth, double fx, double fy, double cx, double cy, double z_min, double eps,
+                         int32_t margin, int32_t* views, void* stream);
+size_t objnerf_mesh_cull_workspace_bytes(int64_t V, int64_t F);
+int objnerf_mesh_cull_count(int64_t V, int64_t F, int32_t rule, const uint8_t* keep_v, const int32_t* faces, void* ws,
+                            size_t ws_bytes, int64_t* counts, int32_t* status, void* stream);
+int objnerf_mesh_cull_emit(int64_t V, int64_t F, int32_t rule, const uint8_t* keep_v, const int32_t* faces, const void* ws,
+                           size_t ws_bytes, int64_t Vn, int64_t Fn, int32_t* new_of_old, int32_t* old_of_new,
+                           int32_t* faces_out, int32_t* face_old, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -320,6 +320,15 @@ SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "objnerf_seg_stats": (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double),
                                     C.c_void_p, C.c_void_p]),
+    # culling meshes to what the frames observed (objnerf_meshcull.hip): additive, still ABI 14
+    "objnerf_vertex_views": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                       C.c_void_p, C.c_void_p]),
+    "objnerf_mesh_cull_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "objnerf_mesh_cull_count": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_mesh_cull_emit": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

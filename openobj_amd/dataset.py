@@ -198,11 +198,17 @@ class Replica(_FrameSet):
     def __len__(self):
         return int((len(os.listdir(os.path.join(self.root_dir, "depth"))) - self.start) / self.stride)
 
+    def depth_and_pose(self, i):
+        """(depth f32 [W, H], T_WC f64 [4, 4]) of sample i, as __getitem__ gives them; reads the depth image only."""
+        idx = int(self.start + i * self.stride)
+        depth = self._depth(_read_image(os.path.join(self.root_dir, "depth", "depth_%d.png" % idx)).transpose(1, 0))
+        return depth, self.Twc[idx]
+
     def __getitem__(self, i):
         idx = int(self.start + i * self.stride)
         idx_no = int(idx / 10)
         r = self.root_dir
-        depth = self._depth(_read_image(os.path.join(r, "depth", "depth_%d.png" % idx)).transpose(1, 0))
+        depth, _ = self.depth_and_pose(i)
         image = _read_image(os.path.join(r, "rgb", "rgb_%d.png" % idx)).astype(np.uint8).transpose(1, 0, 2)
         sem = _read_image(os.path.join(r, "class_our", "semantic_class_%d.png" % idx_no)).astype(np.int32).transpose(1, 0)
         inst = _read_image(os.path.join(r, "instance_our", "semantic_instance_%d.png" % idx_no)).astype(np.int32).transpose(1, 0)
@@ -238,11 +244,19 @@ class ScanNet(_FrameSet):
             pf = pf.squeeze(0).permute(1, 2, 0)
         return pf
 
+    def _raw_depth(self, idx):
+        return np.nan_to_num(_read_image(self.depth_paths[idx]).astype(np.float32).transpose(1, 0), nan=0.0)
+
+    def depth_and_pose(self, i):
+        """(depth f32 [W, H], T_WC f64 [4, 4]) of sample i, as __getitem__ gives them; reads the depth image only."""
+        idx = int(self.start + i * self.stride)
+        return self._depth(self._raw_depth(idx)), self.Twc[idx]
+
     def __getitem__(self, i):
         idx = int(self.start + i * self.stride)
         idx_no = int(idx / 10)
         color = _read_image(self.color_paths[idx]).astype(np.uint8).transpose(1, 0, 2)      # [W, H, 3]
-        raw = np.nan_to_num(_read_image(self.depth_paths[idx]).astype(np.float32).transpose(1, 0), nan=0.0)
+        raw = self._raw_depth(idx)
         # the reference calls cv2.resize(color [W,H,3], (W_d, H_d)) with (H_d, W_d) = raw.shape, i.e. dsize = raw.shape
         # reversed: the result has raw's shape (dataset.py:312-313)
         color = resize_linear(color, raw.shape[1], raw.shape[0])

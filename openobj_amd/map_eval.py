@@ -2,6 +2,8 @@
 
     python -m openobj_amd.map_eval --logdir OUT (--gt-dir DIR | --ref-logdir OTHER) [--gt-scene mesh.ply]
         [--samples N] [--scene-samples N] [--thresholds 0.05 0.01] [--seed S] [--out FILE] [--device cuda:0]
+        [--cull-config scene.json [--cull-stride N] [--cull-eps E] [--cull-min-views M] [--cull-margin PX]
+         [--cull-face-rule all|any]]
 
 This is vMAP's measure (points sampled on the reconstructed and on the ground-truth meshes, nearest neighbours both
 ways); the reference dropped that step, so nothing here has a counterpart in it.  It reads OUT/map_vis/obj_<id>.ply
@@ -22,6 +24,11 @@ scene level with every object of a side as one surface.  The sample counts (10 0
 ASSUMED sizes: vMAP's evaluation script is not part of the reference and was not available; they set the resolution of
 the measure (a sample-to-sample distance cannot fall below the spacing of the samples), so compare only runs made with
 the same counts.
+
+With --cull-config every side (the run, the other side, --gt-scene) is first culled to the surface the frames of that
+scene's sequence observed, in one pass over the frames (openobj_amd/map_cull.py): without it a real ground truth charges
+the run for geometry the sensor never saw.  The file then gains a "cull" entry (parameters, frames, sizes per side);
+an object left empty on a side counts as absent.  Without the option the file is what it was before.
 """
 from __future__ import annotations
 
@@ -36,7 +43,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import mesh, ops
+from . import map_cull, mesh, ops
 
 N_SAMPLES = 10000           # per object and side: an assumed size (see the module docstring)
 N_SCENE_SAMPLES = 200000    # per side at scene level: likewise
@@ -155,14 +162,22 @@ def compare(pred, gt, n_samples: int = N_SAMPLES, thresholds: Sequence[float] = 
 
 
 # ---------------------------------------------------------------------------------------------------------------- CLI
-def read_mesh_dir(path: str) -> Dict[int, tuple]:
-    """{id: (vertices, faces)} of the obj_<id>.ply files in a directory."""
+def mesh_files(path: str) -> Dict[int, str]:
+    """{id: file} of the obj_<id>.ply files in a directory."""
     out = {}
     for f in sorted(glob.glob(os.path.join(path, "obj_*.ply"))):
         m = re.fullmatch(r"obj_(-?\d+)\.ply", os.path.basename(f))
         if m:
-            v, _, _, faces = mesh.read_ply(f)
-            out[int(m.group(1))] = (v.astype(np.float64), faces)
+            out[int(m.group(1))] = f
+    return out
+
+
+def read_mesh_dir(path: str) -> Dict[int, tuple]:
+    """{id: (vertices, faces)} of the obj_<id>.ply files in a directory."""
+    out = {}
+    for k, f in mesh_files(path).items():
+        v, _, _, faces = mesh.read_ply(f)
+        out[k] = (v.astype(np.float64), faces)
     return out
 
 
@@ -179,6 +194,9 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="default: LOGDIR/eval_geometry.json")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--cull-config", default=None, help="a scene config: cull every side to what its frames observed "
+                    "(openobj_amd.map_cull) before comparing")
+    map_cull.add_arguments(ap, "cull-")
     return ap
 
 
@@ -192,16 +210,35 @@ def main(argv=None):
         raise FileNotFoundError(f"no obj_<id>.ply under {os.path.join(a.logdir, 'map_vis')}: run openobj_amd.map_vis first")
     kw = dict(n_samples=a.samples, thresholds=a.thresholds, seed=a.seed, n_scene_samples=a.scene_samples, device=a.device)
     res = {}
+    other = scene = None
     if a.gt_dir or a.ref_logdir:
         other = read_mesh_dir(a.gt_dir if a.gt_dir else os.path.join(a.ref_logdir, "map_vis"))
-        res = compare(pred, other, **kw)
     if a.gt_scene:
         v, _, _, faces = mesh.read_ply(a.gt_scene)
-        whole = compare(pred, {0: (v.astype(np.float64), faces)}, per_object=False, **kw)
+        scene = {0: (v.astype(np.float64), faces)}
+    culled = None
+    if a.cull_config:
+        # every side in ONE pass over the frames
+        given = {"pred": pred, "other": other, "gt_scene": scene}
+        names = [n for n, s in given.items() if s is not None]
+        params = map_cull.parameters(a.cull_stride, a.cull_eps, a.cull_min_views, a.cull_margin, a.cull_face_rule)
+        sides, _, rep = map_cull.cull_sides([given[n] for n in names], a.cull_config, params, a.device)
+        by_name = dict(zip(names, sides))
+        pred, other, scene = by_name["pred"], by_name.get("other"), by_name.get("gt_scene")
+        culled = {"parameters": rep["parameters"], "frames": rep["frames"]}
+        for n, sizes in zip(names, rep["sides"]):
+            culled[n] = {"vertices": [sum(o["vertices"][j] for o in sizes.values()) for j in (0, 1)],
+                         "faces": [sum(o["faces"][j] for o in sizes.values()) for j in (0, 1)], "objects": sizes}
+    if other is not None:
+        res = compare(pred, other, **kw)
+    if scene is not None:
+        whole = compare(pred, scene, per_object=False, **kw)
         if res:
             res["scene_vs_gt_scene"] = whole["scene"]
         else:
             res = whole
+    if culled is not None:
+        res["cull"] = culled
     res["objects"] = {str(k): v for k, v in res["objects"].items()}
     out = a.out or os.path.join(a.logdir, "eval_geometry.json")
     with open(out, "w") as fh:

@@ -1783,3 +1783,88 @@ def seg_stats(d: torch.Tensor, off, thresholds=(), out: Optional[torch.Tensor] =
     check(lib().objnerf_seg_stats(n, S, _ptr(d) if n else None, _ptr(off_dev), len(thr), arr, _ptr(out), _stream()),
           "objnerf_seg_stats")
     return out
+
+
+# ------------------------------------------------------------------------- culling meshes to what the frames observed
+VIEWS_MAX_BATCH = 256           # frames per objnerf_vertex_views call; longer batches are chunked
+_CULL_RULES = {"all": 0, "any": 1}      # OBJNERF_CULL_ALL / OBJNERF_CULL_ANY
+
+
+def vertex_views(verts: torch.Tensor, T_CW: torch.Tensor, depth: torch.Tensor, intrinsics, z_min: float = 0.0,
+                 eps: float = 0.05, margin: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """objnerf_vertex_views: the number of frames that see each vertex -> int32 [V].  verts fp64 [V, 3]
+    (world), T_CW fp64 [B, 3, 4] = the upper rows of inverse(T_WC) per frame, depth fp32 [B, W, H] (metres, 0 = invalid),
+    intrinsics (fx, fy, cx, cy).  out: an int32 [V] tensor the counts are ADDED to (the caller zeroes it once and streams
+    a sequence through in batches); None: a fresh zeroed one."""
+    verts = _req(verts, torch.float64, "vertex_views: verts")
+    T_CW = _req(T_CW, torch.float64, "vertex_views: T_CW")
+    depth = _req(depth, torch.float32, "vertex_views: depth")
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise _lib.ObjnerfError("vertex_views: expected verts [V, 3]")
+    if T_CW.dim() != 3 or tuple(T_CW.shape[1:]) != (3, 4):
+        raise _lib.ObjnerfError("vertex_views: expected T_CW [B, 3, 4]")
+    if depth.dim() != 3 or depth.shape[0] != T_CW.shape[0] or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise _lib.ObjnerfError("vertex_views: expected depth [B, W, H] with one image per pose")
+    V, B, W, H, dev = int(verts.shape[0]), int(T_CW.shape[0]), int(depth.shape[1]), int(depth.shape[2]), verts.device
+    if T_CW.device != dev or depth.device != dev:
+        raise _lib.ObjnerfError("vertex_views: verts, T_CW and depth on different devices")
+    if V >= 2 ** 31 or W >= 2 ** 31 or H >= 2 ** 31:
+        raise _lib.ObjnerfError("vertex_views: at most 2^31 - 1 vertices, columns and rows")
+    fx, fy, cx, cy = (float(x) for x in intrinsics)
+    margin = int(margin)
+    if margin < 0:
+        raise _lib.ObjnerfError("vertex_views: margin must not be negative")
+    if out is None:
+        out = torch.zeros(V, dtype=torch.int32, device=dev)
+    elif _req(out, torch.int32, "vertex_views: out") is not out or tuple(out.shape) != (V,) or out.device != dev:
+        raise _lib.ObjnerfError("vertex_views: out must be contiguous int32 [V] on the vertices' device")
+    for b0 in range(0, B, VIEWS_MAX_BATCH):
+        b1 = min(B, b0 + VIEWS_MAX_BATCH)
+        check(lib().objnerf_vertex_views(V, b1 - b0, W, H, _ptr(verts) if V else None, _ptr(T_CW[b0:b1]),
+                                         _ptr(depth[b0:b1]), fx, fy, cx, cy, float(z_min), float(eps), margin,
+                                         _ptr(out) if V else None, _stream()), "objnerf_vertex_views")
+    return out
+
+
+def mesh_compact(keep_v: torch.Tensor, faces: torch.Tensor, rule: str = "all", out=None) -> Dict[str, torch.Tensor]:
+    """objnerf_mesh_cull_count / _emit: the sub-mesh a vertex mask keeps.  keep_v uint8 or bool [V], faces int32 [F, 3];
+    rule "all": a face stays iff its three corners are kept, "any": iff at least one is.  -> {"new_of_old" int32 [V]
+    (-1 = dropped), "old_of_new" int32 [Vn], "faces" int32 [Fn, 3] re-indexed, "face_old" int32 [Fn]}: the kept faces
+    in their original order and exactly the vertices they use, in ascending original order.  Raises if a face names a
+    vertex outside [0, V).  Synchronises the stream once (the two totals are read back to size the outputs).
+    out: a dict of the four tensors to write into (their sizes must be the counted ones)."""
+    if rule not in _CULL_RULES:
+        raise ValueError(f"mesh_compact: rule {rule!r}: 'all' or 'any' expected")
+    if keep_v.dtype == torch.bool and keep_v.is_cuda:
+        keep_v = keep_v.contiguous().view(torch.uint8)
+    keep_v = _req(keep_v, torch.uint8, "mesh_compact: keep_v")
+    faces = _req(faces, torch.int32, "mesh_compact: faces")
+    if keep_v.dim() != 1 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.ObjnerfError("mesh_compact: expected keep_v [V] and faces [F, 3]")
+    V, F, dev, r = int(keep_v.shape[0]), int(faces.shape[0]), keep_v.device, _CULL_RULES[rule]
+    if faces.device != dev:
+        raise _lib.ObjnerfError("mesh_compact: keep_v and faces on different devices")
+    if max(V, F) >= 2 ** 31:
+        raise _lib.ObjnerfError("mesh_compact: at most 2^31 - 1 vertices and faces")
+    nbytes = int(lib().objnerf_mesh_cull_workspace_bytes(V, F))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    kp, fp = _ptr(keep_v) if V else None, _ptr(faces) if F else None
+    check(lib().objnerf_mesh_cull_count(V, F, r, kp, fp, _ptr(ws), nbytes, _ptr(counts), _ptr(status), _stream()),
+          "objnerf_mesh_cull_count")
+    Vn, Fn = (int(x) for x in counts.tolist())                # the one host sync
+    if int(status.item()):
+        raise _lib.ObjnerfError("mesh_compact: a face names a vertex outside [0, V)")
+    shapes = {"new_of_old": (V,), "old_of_new": (Vn,), "faces": (Fn, 3), "face_old": (Fn,)}
+    if out is None:
+        res = {k: torch.empty(s, dtype=torch.int32, device=dev) for k, s in shapes.items()}
+    else:
+        res = {k: out[k] for k in shapes}
+        for k, s in shapes.items():
+            if _req(res[k], torch.int32, f"mesh_compact: out {k}") is not res[k] or tuple(res[k].shape) != s or res[k].device != dev:
+                raise _lib.ObjnerfError(f"mesh_compact: out[{k!r}] must be contiguous int32 {list(s)}")
+    p = {k: (_ptr(t) if t.numel() else None) for k, t in res.items()}
+    check(lib().objnerf_mesh_cull_emit(V, F, r, kp, fp, _ptr(ws), nbytes, Vn, Fn, p["new_of_old"], p["old_of_new"],
+                                       p["faces"], p["face_old"], _stream()), "objnerf_mesh_cull_emit")
+    return res
