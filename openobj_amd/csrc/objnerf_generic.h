@@ -25,20 +25,25 @@ size_t train_workspace_bytes(const objnerf_net* net, int K, int R, int S, int fe
 // done (optional): bit 0 = the call derived counts / flags itself (OBJNERF_TRAIN_SELF_COUNTS), bit 1 = the call applied
 // a->optim; what is not reported is left to the caller (objnerf_train_step)
 int train_step(const objnerf_net* net, const objnerf_train_args* a, void* stream, int* done = nullptr);
-// the batched fp32 MFMA GEMM of this path, for the feature-head kernels of objnerf_train.hip:
-//   C[z][m][n] (+)= sum_k A(z; m,k) B(z; k,n), element strides (sam, sak), (sbk, sbn), (scm, scn), batch strides bs*
-void feat_gram(void* stream, int K, const float* params, long p_stride, int off_w, int off_b, int C, int Hh, float* gram,
-               long gstride);
-void feature_head(void* stream, int K, long n, int Hh, int C, const float* params, long p_stride, long off_w, long off_b,
-                  const float* hfeat, const float* weight, float* out);
-void gemm_f32(void* stream, int batch, int M, int N, int Kd, const float* A, long sam, long sak, long bsa, const float* B,
-              long sbk, long sbn, long bsb, float* C, long scm, long scn, long bsc, bool accumulate);
-//   long contraction over n, few output tiles: split-K with float atomics into a PRE-ZEROED C (scn = 1)
-// split-K weight gradient over n samples (C pre-zeroed only for the atomics fallback).  parts: scratch of
-// wgrad_parts_floats(batch, M, N, n) floats for the deterministic slab-and-reduce form; NULL = float atomics
+// One operand of a batched GEMM  C[z][m][n] (+)= sum_k A(z; m,k) B(z; k,n):  element (i, j) of batch entry z is
+// p[z bs + i s0 + j s1], with (i, j) = (m, k) for A, (k, n) for B and (m, n) for C and the mask.  h16: the buffer holds
+// the step's 16-bit operand type (element strides as for floats); set where the buffer is known, never inferred.
+struct Operand { const float* p; long s0, s1, bs; bool h16; };
+inline Operand op_rows(const float* p, long ld, long bs, bool h16 = false) { return {p, ld, 1, bs, h16}; }   // [z][i][ld]
+inline Operand op_cols(const float* p, long ld, long bs, bool h16 = false) { return {p, 1, ld, bs, h16}; }   // [z][j][ld]
+// the 512-d feature head of K stacked networks: W_of [C][Hh] at P + off_w, b_of [C] at P + off_b; gt_feat [K][R][C]
+struct FeatHeadArgs { int K, R, Hh, C; const float* P; long ps; int off_w, off_b; const float* gt_feat; };
+// the batched fp32 MFMA GEMM of this path, for the feature-head kernels of objnerf_train.hip
+void feat_gram(void* stream, const FeatHeadArgs& h, float* gram, long gstride);
+// out[k][m][:] = W_of[k] hfeat[k][m] + b_of[k] * weight[k][m] over n rows per object (weight NULL = 1)
+void feature_head(void* stream, const FeatHeadArgs& h, long n, const float* hfeat, const float* weight, float* out);
+void gemm_f32(void* stream, int batch, int M, int N, int Kd, const Operand& A, const Operand& B, const Operand& C,
+              bool accumulate);
+// split-K weight gradient over n samples, C(m, n) with s1 == 1 (C pre-zeroed only for the atomics fallback).  parts: scratch
+// of wgrad_parts_floats(batch, M, N, n) floats for the deterministic slab-and-reduce form; NULL = float atomics
 size_t wgrad_parts_floats(int batch, int M, int N, long n);
-void wgrad_f32(void* stream, int batch, int M, int N, long n, const float* A, long sam, long sak, long bsa, const float* B,
-               long sbk, long sbn, long bsb, float* C, long scm, long bsc, float* parts, size_t parts_floats);
+void wgrad_f32(void* stream, int batch, int M, int N, long n, const Operand& A, const Operand& B, const Operand& C,
+               float* parts, size_t parts_floats);
 // The hoisted 512-d feature head around a fused kernel of ANOTHER width (the hidden-256 path, objnerf_train256.hip):
 // buffers, the preparation ahead of the kernel (G = W_of^T W_of, wb, bb per object; u = W_of^T g, beta, |g| per ray) and
 // the head's gradient behind it (the rays' moment GEMMs + featg_finish_kernel).  operands: 0 fp32, 1 bf16, 2 fp16 GEMMs.
@@ -47,10 +52,8 @@ struct FeatHead {
 };
 size_t feat_head_workspace_bytes(int K, int R, int Hh, int C);
 FeatHead feat_head_carve(char* base, int K, int R, int Hh, int C);
-int feat_head_prep(void* stream, int K, int R, int Hh, int C, const float* params, long p_stride, long off_w, long off_b,
-                   const float* gt_feat, const FeatHead& f, int operands);
-int feat_head_grads(void* stream, int K, int R, int Hh, int C, const float* params, long p_stride, long off_w, long off_b,
-                    const float* gt_feat, const FeatHead& f, float* grads, int operands);
+int feat_head_prep(void* stream, const FeatHeadArgs& h, const FeatHead& f, int operands);
+int feat_head_grads(void* stream, const FeatHeadArgs& h, const FeatHead& f, float* grads, int operands);
 size_t eval_workspace_bytes(const objnerf_net* net, int K, long N);
 // pts == NULL: emb_in [K][N][129] is the embedding (OccupancyMap.forward on a caller-supplied tensor)
 int eval_points(const objnerf_net* net, int K, long N, const float* params, long p_stride, const float* scale,

@@ -2,1057 +2,16 @@
 // (hidden 128, train.py:447-463) and the hidden-256 stress configuration.  The hidden-32 object networks
 // use the fused kernel in objnerf_train32.hip; wider networks do not fit one CU's LDS / registers, so this
 // path materialises activations in the caller's workspace and runs the contraction as batched fp32 MFMA
-// GEMMs (v_mfma_f32_16x16x4_f32, 64x64x16 tiles), with the reference's op order:
+// GEMMs (objnerf_gemm.hip), with the reference's op order:
 //   embedding.py:46-55 -> model.py:61-103 -> loss.py:5-103 (objnerf_step_batch_loss) -> reverse.
 #include <algorithm>
 #include "objnerf_device.h"
 #include "../../include/objnerf_hip.h"
 #include "objnerf_generic.h"
+#include "objnerf_gemm.h"
 #include "objnerf_step_tail.h"
 
 namespace objgen {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// ------------------------------------------------------------------------------------------------
-// C[m][n] (+)= sum_k A(m,k) B(k,n), generic strides, batched over blockIdx.z.  Epilogue (in order):
-// + bias[n], * scale, relu, mask (C = mask(m,n) > 0 ? C : 0).
-struct Gemm {
-  int M, N, Kd;
-  const float* A; long sam, sak, bsa;
-  const float* B; long sbk, sbn, bsb;
-  float* C; long scm, scn, bsc;
-  const float* bias; long bsbias;
-  const float* mask; long smm, smn, bsm;
-  int accumulate, relu;
-  int splitk;      // > 1: blockIdx.z = batch * splitk + slice; each slice atomically adds its partial into C
-  float* rowsum; long bsrs;   // optional: rowsum[m] += sum_k A(m,k)  (bias gradient riding on the weight-gradient GEMM)
-  const float* biasrow; long bsbr;   // optional per-row factor of the bias: + bias[n] * biasrow[m sbr]
-  int sbr;
-  float* part; float* rs_part;   // split-K with these set: slice s of batch z STORES its partial tile at part[((z sk + s) M + m)
-                                 // N + n] (row sums: rs_part[(z sk + s) M + m]) and reduce_parts_kernel adds the slices in
-                                 // order -- bit-reproducible; NULL: float atomics into C / rowsum
-  int vec4;        // A is read with dwordx4 loads: AFULL panel rows / k-major A rows are 16-byte aligned
-  const void* Bp;  // AFULL: B packed as 16-bit MFMA operands, [z][k / 32][n / 16][lane][8] (pack_b_kernel)
-  int a16, b16, m16, c16;   // 16-bit kernels: A / B / mask / C are arrays of the kernel's operand type (the layer-wise
-                            // path keeps h1 .. hc in 16 bit in the 16-bit modes); element strides as for floats
-  const float* A2; long sam2, bsa2; int k2;   // AFULL: columns k >= k2 of A come from A2[m sam2 + (k - k2)] (the
-                                              // concatenated layers [h | x] as ONE contraction); k2 >= Kd: none
-  float a_scale;   // 16-bit operand kernels: A is multiplied by this power of two before it is rounded and the result
-                   // divided by it (keeps back-propagated gradients out of fp16's subnormal range); 1 elsewhere
-};
-
-#ifndef OBJ_GEMM_BK
-#define OBJ_GEMM_BK 16
-#endif
-constexpr int BK = OBJ_GEMM_BK;
-#ifndef OBJ_WGRAD_MINPER
-#define OBJ_WGRAD_MINPER 256
-#endif
-
-// Workgroup tile (32*TM*2) x (32*TN*2): 4 waves as 2 x 2, each wave TM x TN MFMA tiles of 16 x 16.
-// <1,1> = 64 x 64 (small problems), <2,2> = 128 x 128 (the n x H x H layer GEMMs: 2 MFMAs per LDS read).
-template <int TM, int TN, int BKT = BK, int WM = 2, int WN = 2>
-__device__ __forceinline__ void gemm_tile(const Gemm& g, const int bx, const int by, const int bz) {
-  constexpr int BK = BKT;      // k depth of one LDS stage (shadows the default)
-  constexpr int BM = 16 * TM * WM, BN = 16 * TN * WN;      // (per wave 16*TM x 16*TN, workgroup WM x WN waves)
-  constexpr int NTH = 64 * WM * WN;
-  __shared__ float As[BK][BM + 4];
-  __shared__ float Bs[BK][BN + 4];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int c = lane & 15, gg = lane >> 4;
-  const int wm = w / WN, wn = w % WN;
-  const int m0 = by * BM, n0 = bx * BN;
-  const int sk = g.splitk > 1 ? g.splitk : 1;
-  const long z = bz / sk;
-  const int slice = bz % sk;
-  const float* A = g.A + z * g.bsa;
-  const float* B = g.B + z * g.bsb;
-  float* C = g.C + z * g.bsc;
-  const int kper = ((g.Kd + sk - 1) / sk + BK - 1) / BK * BK;
-  const int kbeg = slice * kper, kend = min(g.Kd, kbeg + kper);
-  f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int NA = BM * BK / NTH, NB = BN * BK / NTH;
-  float ra[NA], rb[NB];
-  // a thread's elements of the two tiles: fixed (row, k-slot) per element, so each keeps a pointer that advances by one
-  // k stage per load (the per-element stride products of every stage were ~12 VALU instructions per load -- 40 % on top
-  // of the MFMA time of the 8-deep wide kernel, and VALU time adds to fp32 MFMA time here)
-  const float* pa[NA]; const float* pb[NB];
-  int ka[NA], kb[NB];          // the element's current k; < 0: row out of range
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-    const int e = tid + NTH * i;
-    int am, ak;
-    if (g.sak == 1) { ak = e % BK; am = e / BK; } else { am = e % BM; ak = e / BM; }
-    const int gm = m0 + am;
-    pa[i] = A + (long)gm * g.sam + (long)(kbeg + ak) * g.sak;
-    ka[i] = gm < g.M ? kbeg + ak : INT_MAX / 2;
-  }
-#pragma unroll
-  for (int i = 0; i < NB; ++i) {
-    const int e = tid + NTH * i;
-    int bn, bk;
-    if (g.sbk == 1) { bk = e % BK; bn = e / BK; } else { bn = e % BN; bk = e / BN; }
-    const int gn = n0 + bn;
-    pb[i] = B + (long)(kbeg + bk) * g.sbk + (long)gn * g.sbn;
-    kb[i] = gn < g.N ? kbeg + bk : INT_MAX / 2;
-  }
-  const long stepa = (long)BK * g.sak, stepb = (long)BK * g.sbk;
-  auto load_tiles = [&](int) {                 // (stages are requested in order: the argument is implied)
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      ra[i] = ka[i] < kend ? *pa[i] : 0.f;
-      pa[i] += stepa; ka[i] += BK;
-    }
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      rb[i] = kb[i] < kend ? *pb[i] : 0.f;
-      pb[i] += stepb; kb[i] += BK;
-    }
-  };
-  auto store_tiles = [&]() {
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int e = tid + NTH * i;
-      int am, ak;
-      if (g.sak == 1) { ak = e % BK; am = e / BK; } else { am = e % BM; ak = e / BM; }
-      As[ak][am] = ra[i];
-    }
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const int e = tid + NTH * i;
-      int bn, bk;
-      if (g.sbk == 1) { bk = e % BK; bn = e / BK; } else { bn = e % BN; bk = e / BN; }
-      Bs[bk][bn] = rb[i];
-    }
-  };
-  float rs = 0.f;
-  const bool do_rs = g.rowsum != nullptr && bx == 0 && tid < BM;
-  if (kbeg < kend) load_tiles(kbeg);
-  for (int k0 = kbeg; k0 < kend; k0 += BK) {
-    store_tiles();
-    __syncthreads();
-    if (k0 + BK < kend) load_tiles(k0 + BK);       // next tile's global loads fly under the MFMAs
-    if (do_rs) {
-#pragma unroll
-      for (int kk = 0; kk < BK; ++kk) rs += As[kk][tid];
-    }
-#pragma unroll
-    for (int ks = 0; ks < BK / 4; ++ks) {
-      float a[TM], b[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) a[i] = As[4 * ks + gg][16 * TM * wm + 16 * i + c];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) b[j] = Bs[4 * ks + gg][16 * TN * wn + 16 * j + c];
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  if (do_rs && m0 + tid < g.M) {
-    if (g.rs_part) g.rs_part[(z * sk + slice) * g.M + m0 + tid] = rs;
-    else atomicAdd(g.rowsum + z * g.bsrs + m0 + tid, rs);
-  }
-  // epilogue: D layout: col n = lane & 15, row m = 4 * (lane >> 4) + r.  Offsets are advanced incrementally (the 64-bit
-  // stride products per element were ~15 VALU instructions each, and VALU time adds to fp32 MFMA time on this part).
-  const int mb = m0 + 16 * TM * wm + 4 * gg, nb = n0 + 16 * TN * wn + c;
-  long ci = (long)mb * g.scm + (long)nb * g.scn;                        // into C (this batch entry)
-  long mi = z * g.bsm + (long)mb * g.smm + (long)nb * g.smn;            // into g.mask
-  long ri = z * g.bsbr + (long)mb * g.sbr;                              // into g.biasrow
-  const long c16m = 16 * g.scm, c16n = 16 * g.scn, m16m = 16 * g.smm, m16n = 16 * g.smn, r16 = 16 * (long)g.sbr;
-#pragma unroll
-  for (int i = 0; i < TM; ++i, ci += c16m, mi += m16m, ri += r16) {
-    long cj = ci, mj = mi;
-#pragma unroll
-    for (int j = 0; j < TN; ++j, cj += c16n, mj += m16n) {
-      const int n = nb + 16 * j;
-      const float bn_ = (g.bias && n < g.N && sk <= 1) ? g.bias[z * g.bsbias + n] : 0.f;
-      long co = cj, mo = mj, ro = ri;
-#pragma unroll
-      for (int r = 0; r < 4; ++r, co += g.scm, mo += g.smm, ro += g.sbr) {
-        const int m = mb + 16 * i + r;
-        if (m < g.M && n < g.N) {
-          float v = acc[i][j][r];
-          if (sk > 1) {
-            if (g.part) g.part[((z * sk + slice) * g.M + m) * g.N + n] = v;
-            else atomicAdd(C + co, v);
-            continue;
-          }
-          if (g.accumulate) v += C[co];
-          if (g.bias) v += bn_ * (g.biasrow ? g.biasrow[ro] : 1.0f);
-          if (g.relu) v = fmaxf(v, 0.f);
-          if (g.mask) v = g.mask[mo] > 0.f ? v : 0.f;
-          C[co] = v;
-        }
-      }
-    }
-  }
-}
-
-
-template <int TM, int TN, int BKT = BK>
-__global__ __launch_bounds__(256) void gemm_kernel(const Gemm g) {
-  gemm_tile<TM, TN, BKT>(g, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-// 128 x 128 tile on 8 waves (4 x 2 waves of 32 x 64)
-#ifndef OBJ_GEMM_BK_WIDE
-#define OBJ_GEMM_BK_WIDE 8      // measured on the hidden-256 layer GEMMs (configs[4] share): 8 -> 422 ms, 16 -> 452, 32 -> 457
-#endif
-#ifndef OBJ_GEMM_WIDE_TM
-#define OBJ_GEMM_WIDE_TM 2      // row tiles per wave of the wide kernel: workgroup tile (64 TM) x 128
-#endif
-__global__ __launch_bounds__(512, 8) void gemm_kernel8(const Gemm g) {
-  gemm_tile<OBJ_GEMM_WIDE_TM, 4, OBJ_GEMM_BK_WIDE, 4, 2>(g, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
-// Several independent GEMMs in ONE launch (the weight-gradient GEMMs of a small-batch step: each alone is ~260
-// workgroups of latency-bound work): blockIdx.z runs over the concatenated (batch x split-K) slices of all of them.
-// Optional extra workgroups of a grouped launch (blockIdx.z >= zbeg[count], x = y = 0): the feature branch's small
-// preparation passes of the one-launch background iteration -- wb = W_of^T b_of, bb; beta = b_of . g, |g| per ray; a copy of
-// [W_of | b_of] for the head's finish -- ride on the launch of its two preparation GEMMs (round 6: three launches fewer).
-struct FeatPrepTask {
-  int blocks = 0;                         // 0: no task
-  const float* params; long ps; int off_w, off_b, C, Hh, R, rin_ld, K;
-  const float* gt_feat; float* rayin; float* gram; long gstride; float* snap;
-  int nb_wb, nb_rs, nb_snap;              // workgroups per object of the three passes
-};
-struct GemmGroup {
-  static constexpr int MAXG = 11;
-  int count;
-  int zbeg[MAXG + 1];
-  Gemm g[MAXG];
-  FeatPrepTask task;
-};
-__device__ void feat_prep_task(const FeatPrepTask& t, int b);
-// 8 waves per workgroup on a 128 x 128 output tile (4 x 2 waves of 32 x 64): every operand slice is read once
-// (64 x 64 tiles of 4 waves read it once per tile: 0.297 -> 0.287 ms for the background step)
-__global__ __launch_bounds__(512) void gemm_group_kernel(const GemmGroup gr) {
-  if ((int)blockIdx.z >= gr.zbeg[gr.count]) {            // (extra workgroups: FeatPrepTask)
-    if (blockIdx.x == 0 && blockIdx.y == 0) feat_prep_task(gr.task, (int)blockIdx.z - gr.zbeg[gr.count]);
-    return;
-  }
-  int i = 0;
-  while (i + 1 < gr.count && (int)blockIdx.z >= gr.zbeg[i + 1]) ++i;
-  const Gemm& g = gr.g[i];
-  if ((int)blockIdx.x * 128 >= g.N || (int)blockIdx.y * 128 >= g.M) return;
-  gemm_tile<2, 4, BK, 4, 2>(g, blockIdx.x, blockIdx.y, blockIdx.z - gr.zbeg[i]);
-}
-
-// ------------------------------------------------------------------------------------------------
-// bf16-operand variant (OBJNERF_TRAIN_BF16 on the layer-wise path): same interface and epilogue, operands are
-// rounded to bf16 when they are staged in LDS ([row][k], k contiguous: one ds_read_b128 per MFMA operand),
-// v_mfma_f32_16x16x32_bf16, fp32 accumulation.  64 x 64 (or, for wide layers, 128 x 128) tiles, 32-deep k steps:
-// 4 (16) MFMAs per wave and step, so the kernel is bound by the operand traffic, not by the matrix core.
-//
-// OT = _Float16 is the OBJNERF_TRAIN_FP16 mode (v_mfma_f32_16x16x32_f16): 11 significant bits instead of 8, but a
-// narrow exponent -- operands are clamped to +-65504 when rounded, and the backward GEMMs scale their gradient
-// operand (Gemm::a_scale).
-#ifndef OBJ_G16_BK
-#define OBJ_G16_BK 32
-#endif
-#ifndef OBJ_G16_AFULL
-#define OBJ_G16_AFULL 1
-#endif
-#ifndef OBJ_G16_WIDE_NARROW
-#define OBJ_G16_WIDE_NARROW 1
-#endif
-#ifndef OBJ_ACT16
-#define OBJ_ACT16 1
-#endif
-#ifndef OBJ_G16_AFULL_NARROW
-#define OBJ_G16_AFULL_NARROW 1
-#endif
-#ifndef OBJ_G16_XCD
-#define OBJ_G16_XCD 1
-#endif
-#ifndef OBJ_G16_BK_WIDE
-#define OBJ_G16_BK_WIDE 32
-#endif
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-template <typename OT> struct Op16;
-template <> struct Op16<__bf16> {
-  typedef bf16x8 V;
-  static __device__ __forceinline__ __bf16 cvt(float x) { return (__bf16)x; }
-  static __device__ __forceinline__ f32x4 mfma(V a, V b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Op16<_Float16> {
-  typedef f16x8 V;
-  static __device__ __forceinline__ _Float16 cvt(float x) { return (_Float16)fminf(fmaxf(x, -65504.0f), 65504.0f); }
-  static __device__ __forceinline__ f32x4 mfma(V a, V b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-// BKB: k-stage depth (OBJ_G16_BK / OBJ_G16_BK_WIDE).  Measured on MI355X (tools/gemm16_ab.sh): deeper stages LOSE --
-// background step in bf16 mode 0.92 ms at 32, 1.19 ms at 64, 2.2 ms at 128; configs[4] share in fp16 2.18 / 2.37 /
-// 2.60 s -- the prefetch registers and the larger LDS tiles cost more occupancy than the saved barriers return.  (Again
-// with both weight-gradient operands 16-bit pass-through, 8 registers per stage: share per 8 objects 83 ms at 32,
-// 104 at 64, 85 at 128.)
-// WM x WN waves per workgroup, TM x TN MFMA tiles per wave.  The 128 x 128 tile runs on 8 waves (4 x 2, 32 x 64 per wave:
-// 32 accumulator and 16 staging registers): as 4 waves of 64 x 64 it needed 197 registers, ONE wave per SIMD, and ran
-// the hidden-256 layer GEMMs at 28 TFLOP/s -- slower than the fp32 kernel.
-//
-// AKM / BKM: the operand's ROWS (m / n) are the contiguous dimension in memory (weight gradients: A = d_out^T, B =
-// activations; input gradients: B = W as stored).  Such a tile is staged K-MAJOR -- four consecutive rows per thread,
-// one 8-byte LDS store, coalesced -- and the MFMA operand (8 consecutive k of one row) is gathered by two
-// ds_read_b64_tr_b16 (gfx950's transposing LDS read: a 16-lane group reads a 4 k x 16 rows block column-wise;
-// tools/ubench_tr.hip checks the lane map).  Before, those tiles went to the [row][k] image as 2-byte stores with a
-// 4-way bank conflict and the hidden-256 weight gradients ran at 18 TFLOP/s.
-// The read is the compiler's builtin (__builtin_amdgcn_ds_read_tr16_b64_*): it knows the instruction returns through
-// LGKM, so it places the s_waitcnt itself and a batch of reads stays in flight together.  (Rounds 2-3 issued it as bare
-// inline asm with a hand-written wait tied to the destination registers: correct only as long as the register
-// allocator never copied a destination before that wait.)
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint2 lds_tr16(const void* p) {
-  const s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(p));
-  return __builtin_bit_cast(uint2, v);
-}
-// (the 8-wave tile is held to 128 registers -- two workgroups per CU: at 130 the fp16 forward variant lost one)
-//
-// AFULL (layer GEMMs over the sample axis: M = 10^6 rows, contraction <= 256, A rows k-contiguous): the workgroup's A
-// panel -- BM rows x the WHOLE contraction -- is fetched with one burst of loads before the k-loop (64 KB in flight
-// per workgroup) and stays in LDS.  B -- the layer's weights -- is NOT staged by the workgroup at all: pack_b_kernel
-// rounds it ONCE per GEMM into a 16-bit image laid out as MFMA operands ([k / 32][n / 16][lane][8], 128 KB for 256 x
-// 256, L2-resident) and every lane fetches its operand with one 16-byte load.  No barrier and no conversion in the
-// k-loop.  (The plain kernel re-read and re-rounded the fp32 weights in every workgroup: rocprof counted 36 VALU
-// instructions per MFMA on the hidden-256 layer GEMMs, which ran at ~2 TB/s of HBM traffic with the matrix core 90 %
-// idle.)  With BN = 256 the panel is read exactly once.  The epilogue's LDS patch aliases the panel.
-// (the body takes its block coordinates as arguments: gemm_group16_kernel below runs it for several GEMMs per launch)
-template <int TM, int TN, typename OT, int BKB, int WM = 2, int WN = 2, bool AKM = false, bool BKM = false,
-          bool AFULL = false, int KMAX = 256>
-__device__ __forceinline__ void gemm_bf16_body(const Gemm& g, const int bx, const int by, const int bz) {
-  constexpr int BM = 16 * TM * WM, BN = 16 * TN * WN, LDK = BKB + 8, NTH = 64 * WM * WN;
-  constexpr int PA = BM + 8, PB = BN + 8;                 // k-major row pitches (elements; 8-byte aligned rows)
-  constexpr int LDA = AFULL ? KMAX + 8 : LDK;   // AFULL: panel row pitch (conflict-free b128 reads: 132 / 180 dwords)
-  static_assert(!(AFULL && AKM), "the resident panel is row-major");
-  typedef typename Op16<OT>::V OV;
-  constexpr int EC_ = 16 * TN, EP_ = EC_ + 4;
-  constexpr size_t a_bytes = sizeof(OT) * (AFULL ? BM * LDA : (AKM ? BKB * PA : BM * LDK));
-  constexpr size_t ep_bytes = sizeof(float) * WM * WN * 16 * EP_;
-  __shared__ __attribute__((aligned(16))) char a_raw[AFULL ? (a_bytes > ep_bytes ? a_bytes : ep_bytes) : a_bytes];
-  OT* const Asm = reinterpret_cast<OT*>(a_raw);
-  __shared__ __attribute__((aligned(16))) OT Bsm[AFULL ? 8 : (BKM ? BKB * PB : BN * LDK)];
-  const float a_scale = g.a_scale, inv_scale = 1.0f / g.a_scale;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int c = lane & 15, gg = lane >> 4;
-  const int wm = w / WN, wn = w % WN;
-  const int m0 = by * BM, n0 = bx * BN;
-  const int sk = g.splitk > 1 ? g.splitk : 1;
-  const long z = bz / sk;
-  const int slice = bz % sk;
-  const float* A = g.A + z * g.bsa;
-  const float* B = g.B + z * g.bsb;
-  const int kper = ((g.Kd + sk - 1) / sk + BKB - 1) / BKB * BKB;
-  const int kbeg = slice * kper, kend = min(g.Kd, kbeg + kper);
-  f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int NA = AFULL ? 0 : BM * BKB / NTH, NB = AFULL ? 0 : BN * BKB / NTH;
-  float ra[NA ? NA : 1], rb[NB ? NB : 1];
-  if constexpr (AFULL) {
-    // the panel: columns [0, ka) from A (lanes along k; 16-byte loads when g.vec4: rows 16-byte aligned, ka a multiple
-    // of 8), then, for the 352-deep variant, columns [256, 352) from the second source (x1 / x2 inside the 129-float
-    // embedding rows: scalars).  Everything else of the panel is zero.
-    constexpr int KA = 256;
-    const int ka = min(g.k2, g.Kd);                     // columns [0, ka) from A, [ka, Kd) from A2 (then ka == KA)
-    if (g.a16) {
-      constexpr int N8 = BM * KA / 8 / NTH;
-      const OT* A16 = reinterpret_cast<const OT*>(g.A) + z * g.bsa;
-      uint4 pv[N8];
-#pragma unroll
-      for (int i = 0; i < N8; ++i) {
-        const int q = tid + NTH * i, am = q / (KA / 8), ak = 8 * (q % (KA / 8));
-        const int gm = m0 + am;
-        pv[i] = (gm < g.M && ak < ka) ? *reinterpret_cast<const uint4*>(A16 + gm * g.sam + ak) : uint4{0u, 0u, 0u, 0u};
-      }
-#pragma unroll
-      for (int i = 0; i < N8; ++i) {
-        const int q = tid + NTH * i, am = q / (KA / 8), ak = 8 * (q % (KA / 8));
-        *reinterpret_cast<uint4*>(&Asm[am * LDA + ak]) = pv[i];
-      }
-    } else if (g.vec4) {
-      constexpr int NV = BM * KA / 4 / NTH;
-      f32x4 pv[NV];
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int q = tid + NTH * i, am = q / (KA / 4), ak = 4 * (q % (KA / 4));
-        const int gm = m0 + am;
-        pv[i] = (gm < g.M && ak < ka) ? *reinterpret_cast<const f32x4*>(A + gm * g.sam + ak) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int q = tid + NTH * i, am = q / (KA / 4), ak = 4 * (q % (KA / 4));
-        typedef OT ot4 __attribute__((ext_vector_type(4)));
-        ot4 v;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = Op16<OT>::cvt(a_scale != 1.0f ? pv[i][j] * a_scale : pv[i][j]);
-        *reinterpret_cast<ot4*>(&Asm[am * LDA + ak]) = v;
-      }
-    } else {
-      constexpr int NS = BM * KA / NTH / 2;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {          // two bursts of scalar loads
-        float ps[NS];
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-          const int e = tid + NTH * (NS * h + i), am = e / KA, ak = e % KA;
-          const int gm = m0 + am;
-          ps[i] = (gm < g.M && ak < ka) ? A[gm * g.sam + ak] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-          const int e = tid + NTH * (NS * h + i), am = e / KA, ak = e % KA;
-          Asm[am * LDA + ak] = Op16<OT>::cvt(ps[i] * a_scale);
-        }
-      }
-    }
-    if constexpr (KMAX > KA) {
-      constexpr int K2 = KMAX - KA, N2 = BM * K2 / NTH;
-      static_assert(BM * K2 % NTH == 0, "second-source share");
-      const float* A2 = g.A2 + z * g.bsa2;
-      float ps[N2];
-#pragma unroll
-      for (int i = 0; i < N2; ++i) {
-        const int e = tid + NTH * i, am = e / K2, ak = KA + e % K2;
-        const int gm = m0 + am;
-        ps[i] = (gm < g.M && ak >= ka && ak < g.Kd) ? A2[gm * g.sam2 + (ak - ka)] : 0.f;
-      }
-#pragma unroll
-      for (int i = 0; i < N2; ++i) {
-        const int e = tid + NTH * i, am = e / K2, ak = KA + e % K2;
-        Asm[am * LDA + ak] = Op16<OT>::cvt(ps[i] * a_scale);
-      }
-    }
-  }
-  // element e of a thread's share -> (row, k): lanes along the operand's contiguous dimension
-  auto load_tiles = [&](int k0) {
-    if (AKM && g.a16) {
-      // A is a 16-bit gradient array (stored already scaled by a_scale): four consecutive m per lane, one 8-byte load,
-      // passed through to the k-major image (host-checked alignment)
-      const OT* A16 = reinterpret_cast<const OT*>(g.A) + z * g.bsa;
-#pragma unroll
-      for (int i = 0; i < NA / 4; ++i) {
-        const int q = tid + NTH * i, am = 4 * (q % (BM / 4)), ak = q / (BM / 4);
-        const int gm = m0 + am, gk = k0 + ak;
-        const uint2 u = (gm < g.M && gk < kend) ? *reinterpret_cast<const uint2*>(A16 + gk * g.sak + gm) : uint2{0u, 0u};
-        ra[2 * i] = __builtin_bit_cast(float, u.x); ra[2 * i + 1] = __builtin_bit_cast(float, u.y);
-      }
-    } else if (AKM && g.vec4) {
-      // rows contiguous and 16-byte aligned (weight gradients: A = d_out^T): four consecutive m per lane, one dwordx4
-#pragma unroll
-      for (int i = 0; i < NA / 4; ++i) {
-        const int q = tid + NTH * i, am = 4 * (q % (BM / 4)), ak = q / (BM / 4);
-        const int gm = m0 + am, gk = k0 + ak;
-        const f32x4 v = (gm < g.M && gk < kend) ? *reinterpret_cast<const f32x4*>(A + gk * g.sak + gm) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ra[4 * i + j] = v[j];
-      }
-    } else
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      int am, ak;
-      if (AKM) { const int e = tid + NTH * i; am = e % BM; ak = e / BM; }
-      else { const int e = tid + NTH * i; ak = e % BKB; am = e / BKB; }
-      const int gm = m0 + am, gk = k0 + ak;
-      ra[i] = (gm < g.M && gk < kend) ? A[gm * g.sam + gk * g.sak] : 0.f;
-    }
-    if (BKM && g.b16) {
-      // B is a 16-bit activation array (weight gradients in the 16-bit modes): four consecutive n per lane, one 8-byte
-      // load, passed through to the k-major image unchanged (host-checked: sbn == 1, sbk and N multiples of 4)
-      const OT* B16 = reinterpret_cast<const OT*>(g.B) + z * g.bsb;
-#pragma unroll
-      for (int i = 0; i < NB / 4; ++i) {
-        const int q = tid + NTH * i, bn = 4 * (q % (BN / 4)), bk = q / (BN / 4);
-        const int gn = n0 + bn, gk2 = k0 + bk;
-        const uint2 u = (gn < g.N && gk2 < kend) ? *reinterpret_cast<const uint2*>(B16 + gk2 * g.sbk + gn) : uint2{0u, 0u};
-        rb[2 * i] = __builtin_bit_cast(float, u.x); rb[2 * i + 1] = __builtin_bit_cast(float, u.y);
-      }
-      return;
-    }
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      int bn, bk;
-      if (BKM) { const int e = tid + NTH * i; bn = e % BN; bk = e / BN; }
-      else { const int e = tid + NTH * i; bk = e % BKB; bn = e / BKB; }
-      const int gn = n0 + bn, gk2 = k0 + bk;
-      rb[i] = (gn < g.N && gk2 < kend) ? B[gk2 * g.sbk + gn * g.sbn] : 0.f;
-    }
-  };
-  auto store_tiles = [&]() {
-    if (AFULL) {
-    } else if (AKM && g.a16) {
-#pragma unroll
-      for (int i = 0; i < NA / 4; ++i) {
-        const int q = tid + NTH * i;
-        *reinterpret_cast<uint2*>(&Asm[(q / (BM / 4)) * PA + 4 * (q % (BM / 4))]) =
-            uint2{__builtin_bit_cast(uint32_t, ra[2 * i]), __builtin_bit_cast(uint32_t, ra[2 * i + 1])};
-      }
-    } else if (AKM && g.vec4) {
-#pragma unroll
-      for (int i = 0; i < NA / 4; ++i) {
-        const int q = tid + NTH * i;
-        typedef OT ot4 __attribute__((ext_vector_type(4)));
-        ot4 v;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = Op16<OT>::cvt(ra[4 * i + j] * a_scale);
-        *reinterpret_cast<ot4*>(&Asm[(q / (BM / 4)) * PA + 4 * (q % (BM / 4))]) = v;
-      }
-    } else if (AKM) {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int e = tid + NTH * i;
-        Asm[(e / BM) * PA + e % BM] = Op16<OT>::cvt(ra[i] * a_scale);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const int e = tid + NTH * i;
-        Asm[(e / BKB) * LDK + e % BKB] = Op16<OT>::cvt(ra[i] * a_scale);
-      }
-    }
-    if (BKM && g.b16) {
-#pragma unroll
-      for (int i = 0; i < NB / 4; ++i) {
-        const int q = tid + NTH * i;
-        *reinterpret_cast<uint2*>(&Bsm[(q / (BN / 4)) * PB + 4 * (q % (BN / 4))]) =
-            uint2{__builtin_bit_cast(uint32_t, rb[2 * i]), __builtin_bit_cast(uint32_t, rb[2 * i + 1])};
-      }
-    } else if (BKM) {
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int e = tid + NTH * i;
-        Bsm[(e / BN) * PB + e % BN] = Op16<OT>::cvt(rb[i]);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int e = tid + NTH * i;
-        Bsm[(e / BKB) * LDK + e % BKB] = Op16<OT>::cvt(rb[i]);
-      }
-    }
-  };
-  // MFMA operands of the wave's T row tiles (first tile-local row row0), k-slots ks + 8 gg .. + 7
-  auto operands_km = [&](auto& out, const OT* img, const int pitch, const int row0, const int ks) {
-    constexpr int T = sizeof(out) / sizeof(out[0]);
-    uint2 lo[T], hi[T];
-#pragma unroll
-    for (int i = 0; i < T; ++i) {
-      const OT* p = img + (ks + 8 * gg + (c >> 2)) * pitch + row0 + 16 * i + 4 * (c & 3);
-      lo[i] = lds_tr16(p);
-      hi[i] = lds_tr16(p + 4 * pitch);
-    }
-#pragma unroll
-    for (int i = 0; i < T; ++i) out[i] = __builtin_bit_cast(OV, uint4{lo[i].x, lo[i].y, hi[i].x, hi[i].y});
-  };
-  auto operands_rm = [&](auto& out, const OT* img, const int pitch, const int row0, const int ks) {
-    constexpr int T = sizeof(out) / sizeof(out[0]);
-#pragma unroll
-    for (int i = 0; i < T; ++i) out[i] = *reinterpret_cast<const OV*>(img + (row0 + 16 * i + c) * pitch + ks + 8 * gg);
-  };
-  float rs = 0.f;
-  const bool do_rs = !AFULL && g.rowsum != nullptr && bx == 0 && tid < BM;
-  if constexpr (AFULL) {
-    __syncthreads();                     // the panel is complete
-    const int nks = (g.Kd + 31) / 32;
-    const uint4* bp = reinterpret_cast<const uint4*>(g.Bp) + ((z * (KMAX / 32)) * (BN / 16) + TN * wn) * 64 + lane;
-    for (int ks = 0; ks < nks; ++ks) {     // (no operand prefetch: 64 registers -> four workgroups per CU hide the round trip)
-      OV bcur[TN];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) bcur[j] = __builtin_bit_cast(OV, bp[(ks * (BN / 16) + j) * 64]);
-      OV a[TM];
-      operands_rm(a, Asm, LDA, 16 * TM * wm, 32 * ks);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = Op16<OT>::mfma(a[i], bcur[j], acc[i][j]);
-    }
-    __syncthreads();                     // every wave is done with the panel: the epilogue patch may overwrite it
-  }
-  if (!AFULL && kbeg < kend) load_tiles(kbeg);
-  for (int k0 = kbeg; !AFULL && k0 < kend; k0 += BKB) {
-    store_tiles();
-    __syncthreads();
-    if (k0 + BKB < kend) load_tiles(k0 + BKB);
-    if (do_rs) {
-#pragma unroll
-      for (int kk = 0; kk < BKB; ++kk) rs += (float)(AKM ? Asm[kk * PA + tid] : Asm[tid * LDK + kk]);
-    }
-#pragma unroll
-    for (int ks = 0; ks < BKB; ks += 32) {
-      OV a[TM], b[TN];
-      if (AKM) operands_km(a, Asm, PA, 16 * TM * wm, ks); else operands_rm(a, Asm, LDA, 16 * TM * wm, ks);
-      if (BKM) operands_km(b, Bsm, PB, 16 * TN * wn, ks); else operands_rm(b, Bsm, LDK, 16 * TN * wn, ks);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = Op16<OT>::mfma(a[i], b[j], acc[i][j]);
-    }
-    __syncthreads();
-  }
-  if (do_rs && m0 + tid < g.M) {
-    if (g.rs_part) g.rs_part[(z * sk + slice) * g.M + m0 + tid] = rs * inv_scale;
-    else atomicAdd(g.rowsum + z * g.bsrs + m0 + tid, rs * inv_scale);
-  }
-  // Epilogue through LDS: the accumulator layout gives a lane ONE column of four rows, i.e. 64-byte runs per output row
-  // (and the same for the mask / accumulate reads) -- each wave turns a 16-row strip of its tile around in its own LDS
-  // patch so that the lanes run ALONG a row: 256-byte (128-byte for the 64-wide tile) coalesced rows for every global
-  // access of the epilogue.
-  constexpr int EC = 16 * TN, EP = EC + 4, RPI = 64 / EC;            // strip columns, pitch, rows per pass
-  __shared__ float Ep_own[AFULL ? 1 : WM * WN][AFULL ? 1 : 16][AFULL ? 1 : EP];
-  float (*const Ep)[16][EP] = AFULL ? reinterpret_cast<float (*)[16][EP]>(a_raw) : reinterpret_cast<float (*)[16][EP]>(Ep_own);
-  const int ecol = lane % EC, erow0 = lane / EC;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) Ep[w][4 * gg + r][16 * j + c] = acc[i][j][r] * inv_scale;
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const int n = n0 + EC * wn + ecol;
-    // (element offsets of the strip's first row, advanced by one row pass each: the per-row 64-bit products of the
-    // generic strides were most of this kernel's VALU work -- 15 instructions per MFMA on the hidden-256 layer GEMMs)
-    const int mfirst = m0 + 16 * TM * wm + 16 * i + erow0;
-    long coff = z * g.bsc + (long)mfirst * g.scm + (long)n * g.scn;             // into g.C (float or 16-bit elements)
-    long moff = z * g.bsm + (long)mfirst * g.smm + (long)n * g.smn;             // into g.mask
-    long roff = z * g.bsbr + (long)mfirst * g.sbr;                              // into g.biasrow
-    const long cstep = (long)RPI * g.scm, mstep = (long)RPI * g.smm, rstep = (long)RPI * g.sbr;
-    const float bn_ = (g.bias && n < g.N) ? g.bias[z * g.bsbias + n] : 0.f;
-#pragma unroll
-    for (int rr = 0; rr < 16; rr += RPI, coff += cstep, moff += mstep, roff += rstep) {
-      const int m = mfirst + rr;
-      float v = Ep[w][rr + erow0][ecol];
-      if (m < g.M && n < g.N) {
-        if (sk > 1) {
-          if (g.part) g.part[((z * sk + slice) * g.M + m) * g.N + n] = v;
-          else atomicAdd(g.C + coff, v);
-          continue;
-        }
-        if (g.accumulate) v += g.c16 ? (float)reinterpret_cast<const OT*>(g.C)[coff] * inv_scale : g.C[coff];
-        if (g.bias) v += bn_ * (g.biasrow ? g.biasrow[roff] : 1.0f);
-        if (g.relu) v = fmaxf(v, 0.f);
-        if (g.mask) {
-          const bool on = g.m16 ? (float)reinterpret_cast<const OT*>(g.mask)[moff] > 0.f : g.mask[moff] > 0.f;
-          v = on ? v : 0.f;
-        }
-        // (16-bit outputs are stored as the NEXT GEMM's operand: gradients already scaled by a_scale -- 1 in the forward)
-        if (g.c16) reinterpret_cast<OT*>(g.C)[coff] = Op16<OT>::cvt(v * a_scale);
-        else g.C[coff] = v;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-  }
-}
-
-template <int TM, int TN, typename OT, int BKB, int WM = 2, int WN = 2, bool AKM = false, bool BKM = false,
-          bool AFULL = false, int KMAX = 256>
-__global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 8) ? ((AFULL && KMAX == 256) ? 8 : 4) : 1) void gemm_bf16_kernel(const Gemm g) {
-  // Workgroups are handed to the 8 XCDs round-robin in launch order (x fastest), so the column tiles of one row
-  // block -- which read the same A rows -- would land on different L2s.  Re-map: consecutive workgroups OF ONE XCD
-  // take the column tiles of one row block (rows beyond the last multiple of 8 row blocks keep the plain order).
-  // Split-K weight gradients (few output tiles, hundreds of slices): the tiles of ONE slice read the same operand slabs,
-  // so they go to one XCD the same way.
-  int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  if (OBJ_G16_XCD && gridDim.x > 1 && gridDim.y >= 8) {
-    const unsigned gx = gridDim.x, L = blockIdx.x + gx * blockIdx.y, full = (gridDim.y / 8) * 8 * gx;
-    if (L < full) {
-      const unsigned xcd = L % 8, s = L / 8;
-      bx = (int)(s % gx);
-      by = (int)((s / gx) * 8 + xcd);
-    }
-  } else if (OBJ_G16_XCD && gridDim.x * gridDim.y > 1 && gridDim.z >= 8) {
-    const unsigned gx = gridDim.x, T = gx * gridDim.y, L = blockIdx.x + gx * blockIdx.y + T * blockIdx.z;
-    const unsigned full = (gridDim.z / 8) * 8 * T;
-    if (L < full) {
-      const unsigned xcd = L % 8, s = L / 8, tile = s % T;
-      bx = (int)(tile % gx);
-      by = (int)(tile / gx);
-      bz = (int)((s / T) * 8 + xcd);
-    }
-  }
-  gemm_bf16_body<TM, TN, OT, BKB, WM, WN, AKM, BKM, AFULL, KMAX>(g, bx, by, bz);
-}
-
-// The weight-gradient GEMMs of a small-batch step in bf16 mode, in ONE launch (the fp32 twin: gemm_group_kernel): 64 x 64
-// tiles on 4 waves, both operands k-major (d_out^T and the activations as they lie in memory), split-K partial tiles.
-// OBJ_GROUP16_WIDE: 128 x 128 tiles on 8 waves (every operand slice read once, as the fp32 twin) instead of 64 x 64 on 4
-#ifndef OBJ_GROUP16_WIDE
-#define OBJ_GROUP16_WIDE 1
-#endif
-#if OBJ_GROUP16_WIDE
-__global__ __launch_bounds__(512) void gemm_group16_kernel(const GemmGroup gr) {
-  if ((int)blockIdx.z >= gr.zbeg[gr.count]) return;      // (tasks ride on the fp32 grouped launch only)
-  int i = 0;
-  while (i + 1 < gr.count && (int)blockIdx.z >= gr.zbeg[i + 1]) ++i;
-  const Gemm& g = gr.g[i];
-  if ((int)blockIdx.x * 128 >= g.N || (int)blockIdx.y * 128 >= g.M) return;
-  gemm_bf16_body<2, 4, __bf16, OBJ_G16_BK_WIDE, 4, 2, true, true>(g, blockIdx.x, blockIdx.y, blockIdx.z - gr.zbeg[i]);
-}
-#else
-__global__ __launch_bounds__(256) void gemm_group16_kernel(const GemmGroup gr) {
-  if ((int)blockIdx.z >= gr.zbeg[gr.count]) return;      // (tasks ride on the fp32 grouped launch only)
-  int i = 0;
-  while (i + 1 < gr.count && (int)blockIdx.z >= gr.zbeg[i + 1]) ++i;
-  const Gemm& g = gr.g[i];
-  if ((int)blockIdx.x * 64 >= g.N || (int)blockIdx.y * 64 >= g.M) return;
-  gemm_bf16_body<2, 2, __bf16, OBJ_G16_BK, 2, 2, true, true>(g, blockIdx.x, blockIdx.y, blockIdx.z - gr.zbeg[i]);
-}
-#endif
-
-// B (generic strides, fp32) -> the AFULL kernel's operand image: thread (ks, jt, lane) writes the 8 values
-// B[32 ks + 8 (lane >> 4) + e][16 jt + (lane & 15)], e = 0..7, rounded to OT; zero beyond Kd / N.
-template <typename OT, int KS>
-__global__ __launch_bounds__(256) void pack_b_kernel(const Gemm g, OT* __restrict__ out) {
-  typedef typename Op16<OT>::V OV;
-  const int t = blockIdx.x * 256 + threadIdx.x;              // (ks, jt, lane), KS * 16 * 64 per batch entry
-  const int lane = t & 63, jt = (t >> 6) & 15, ks = t >> 10;
-  const long z = blockIdx.y;
-  const float* B = g.B + z * g.bsb;
-  const int n = 16 * jt + (lane & 15);
-  OV v;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int k = 32 * ks + 8 * (lane >> 4) + e;
-    v[e] = Op16<OT>::cvt((k < g.Kd && n < g.N) ? B[k * g.sbk + n * g.sbn] : 0.f);
-  }
-  reinterpret_cast<OV*>(out)[z * (KS * 1024) + t] = v;
-}
-
-// selected for the duration of one train_step call (single host thread per device)
-struct A2Src { const float* A2; long sam2, bsa2; int k2; };
-struct RedGroup;
-// What a GEMM call needs beyond its operands: the operand precision of the step, the step's scratch regions and the
-// one-shot modifiers of the NEXT call.  One instance per C-ABI call, on that call's stack, passed explicitly -- the
-// library keeps no state between (or beside) calls.
-struct GemmEnv {
-  int operands = 0;                 // 0: fp32 GEMMs, 1: bf16 operands, 2: fp16 operands
-  float a_scale = 1.0f;             // Gemm::a_scale of the next gemm(E, ) calls (fp16 backward)
-  GemmGroup* group = nullptr;       // non-null: gemm(E, ) collects descriptors instead of launching
-  bool group16 = false;             // the collected GEMMs run with bf16 operands (gemm_group16_kernel: small-batch step in bf16 mode)
-  const float* biasrow = nullptr;   // Gemm::biasrow / bsbr / sbr of the next calls
-  long bsbr = 0;
-  int sbr = 1;
-  void* packb = nullptr;            // scratch of the AFULL GEMMs' packed B images (176 KB per batch entry)
-  long packb_entries = 0;
-  // [lo, hi): the step's 16-bit activation buffers (h1 .. hc stored in the operand type) and the same for d_hc,
-  // d_h4 .. d_h1 (stored scaled by a_scale); gemm(E, ) marks every operand that lies inside (Gemm::a16 / b16 / m16 / c16)
-  const char *act16_lo = nullptr, *act16_hi = nullptr, *grad16_lo = nullptr, *grad16_hi = nullptr;
-  A2Src a2 = {nullptr, 0, 0, 0};    // second A source of the NEXT gemm(E, ) call (Gemm::A2), panel path only
-  // bump allocator over the caller's workspace region for the partial slabs of ONE step (the weight-gradient GEMMs of
-  // a step run side by side, so each has its own slab); exhausted or absent -> atomics
-  float* parts = nullptr;
-  size_t parts_cap = 0, parts_off = 0;
-  float* next_part = nullptr;       // Gemm::part / rs_part of the next gemm(E, ) call
-  float* next_rs_part = nullptr;
-  RedGroup* red_group = nullptr;    // non-null: reductions are collected (grouped launch)
-  int max_slices = 0;               // > 0: wgrad(E, ) cuts the sample axis into at most this many split-K slices
-  bool error = false;               // a GEMM of the step was handed operands its kernel does not take: train_step returns
-                                    // OBJNERF_EINVAL (a library call never ends the host process)
-  bool need_parts = false;          // wgrad(E, ): the slab form is required (the gradient arena is not zero-filled)
-  bool parts_failed = false;        // ... and the scratch did not hold it
-  bool in_act16(const void* p) const {
-    return (act16_lo && (const char*)p >= act16_lo && (const char*)p < act16_hi) ||
-           (grad16_lo && (const char*)p >= grad16_lo && (const char*)p < grad16_hi);
-  }
-  float* parts_alloc(size_t floats) {
-    floats = (floats + 63) / 64 * 64;
-    if (!parts || parts_off + floats > parts_cap) return nullptr;
-    float* p = parts + parts_off;
-    parts_off += floats;
-    return p;
-  }
-};
-
-// ---- deterministic split-K: partial-tile slabs + an ordered reduction (instead of float atomics)
-#ifndef OBJ_WGRAD_TARGET
-#define OBJ_WGRAD_TARGET 512         // 64 x 64 output tiles x slices a weight-gradient GEMM should at least have
-#endif
-#ifndef OBJ_WGRAD_MAXSLICES
-#define OBJ_WGRAD_MAXSLICES 128      // (32 was measured: the background step in bf16 mode 0.92 -> 1.4 ms, too few workgroups)
-#endif
-// split-K slices of a weight-gradient GEMM over n samples: 512 samples per slice; 256 when that would leave most of the
-// chip idle (the background network at the reference's native batch of 16 800 samples: step 0.55 -> 0.46 ms)
-static int wgrad_slices(int batch, int M, int N, long n) {
-  const long tiles = (long)batch * ((M + 63) / 64) * ((N + 63) / 64);
-  long per = 512;
-  while (per > OBJ_WGRAD_MINPER && tiles * ((n + per - 1) / per) < OBJ_WGRAD_TARGET) per >>= 1;
-  int sk = (int)((n + per - 1) / per);
-  if (sk < 2) sk = 2;
-  if (sk > 256) sk = 256;
-#ifndef OBJ_WGRAD_ATOMICS
-  if (sk > OBJ_WGRAD_MAXSLICES) sk = OBJ_WGRAD_MAXSLICES;
-#endif
-  return sk;
-}
-struct RedItem {
-  const float* part; const float* rs_part; float* C; float* rowsum;
-  int M, N, sk, batch;
-  long scm, bsc, bsrs;
-};
-// Optional tail of the step's reduction launch (the one-launch small-batch iteration, objnerf_small_body.h): the block
-// after the last item's sums the per-workgroup loss terms in workgroup order and WRITES the status word
-// (loss_total_kernel's job), and -- with params set -- every thread that has just summed a gradient element applies
-// torch.optim.AdamW to it (objnerf_step_tail.h; the flag-dependent skipping and the per-group step counters
-// included), so the iteration has no optimiser launch and the gradient is not read back.
-struct RedTail {
-  const float* loss_part = nullptr; int loss_blocks, K; float* loss_terms; int* status;      // loss_part == NULL: no tail
-  float* params = nullptr; const float* grads; float* m; float* v; const int* flags; int* steps; int bank;   // params == NULL: no AdamW
-  long p_stride, lo1, lo2, hi2, arena_floats;      // (sums that land outside [grads, grads + arena_floats) are not parameters' gradients)
-  double lr, b1, b2, wd; float eps;
-};
-struct RedGroup {
-  static constexpr int MAXG = 16;        // (>= the GEMM group's capacity + head sums + d B: a step's reductions in ONE launch)
-  int count;
-  int beg[MAXG + 1];      // first block of each item
-  RedItem it[MAXG];
-  RedTail tail;
-};
-// one thread per output (m, n) of a batch entry (+ one per row sum): adds the sk slices in slice order
-__global__ __launch_bounds__(256) void reduce_parts_kernel(const RedGroup gr) {
-  // a block = 64 consecutive outputs x 4 waves; wave w adds slices [w sk / 4, (w + 1) sk / 4) of its outputs in order
-  // (coalesced: lanes along the outputs; 16 loads in flight), the four quarter sums meet in LDS and are added in wave
-  // order -- a fixed association, so the result is bit-reproducible
-  __shared__ float quarter[4][64];
-  __shared__ float s_step_size[3], s_bc2_sqrt[3];
-  __shared__ int s_active[3];
-  const RedTail& tl = gr.tail;
-  const bool tail_block = (int)blockIdx.x == gr.beg[gr.count];      // (only launched when the tail is set)
-  if (tl.params && threadIdx.x < 3) {
-    const int g = threadIdx.x;
-    adamw_group_begin(g, tl.flags[0] != 0, tl.flags[1] != 0, tl.steps, tl.bank, tl.lr, tl.b1, tl.b2, tail_block,
-                      s_active[g], s_step_size[g], s_bc2_sqrt[g]);
-  }
-  if (tail_block) {
-    // the objects' loss terms from the workgroups' partial sums, in workgroup order, and their status bits
-    __shared__ int s_bad;
-    if (threadIdx.x == 0) s_bad = 0;
-    __syncthreads();
-    int bad = 0;
-    // a wave per (object, term): lane l adds partials l, l + 64, .. in order, then the lanes meet in a fixed butterfly --
-    // one association for every run (bit-reproducible), 64 loads in flight instead of a chain of `loss_blocks` latencies
-    // (1200 workgroups at the benchmark shape: 120 us as one thread per term)
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int e = wv; e < 4 * tl.K; e += 4) {
-      const float* p = tl.loss_part + (long)(e >> 2) * tl.loss_blocks * 4 + (e & 3);
-      float v = 0.f;
-      for (int b = lane; b < tl.loss_blocks; b += 64) v += p[4 * b];
-      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-      if (lane == 0) {
-        tl.loss_terms[e] = v;
-        bad |= loss_status_bits(v);
-      }
-    }
-    if (bad) atomicOr(&s_bad, bad);
-    __syncthreads();
-    if (threadIdx.x == 0 && tl.status) *tl.status = s_bad;
-    return;
-  }
-  int i = 0;
-  while (i + 1 < gr.count && (int)blockIdx.x >= gr.beg[i + 1]) ++i;
-  const RedItem& r = gr.it[i];
-  const long per = (long)r.M * r.N, nrs = r.rs_part ? r.M : 0;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const long e = ((long)blockIdx.x - gr.beg[i]) * 64 + lane;
-  const bool live = e < (long)r.batch * (per + nrs);
-  const long z = live ? e / (per + nrs) : 0, q = live ? e - z * (per + nrs) : 0;
-  const bool is_c = q < per;
-  const float* p = is_c ? r.part + z * r.sk * per + q : r.rs_part + z * r.sk * r.M + (q - per);
-  const long stride = is_c ? per : r.M;
-  const int s0 = (int)((long)r.sk * w / 4), s1 = (int)((long)r.sk * (w + 1) / 4);
-  float v = 0.f;
-  if (live) {
-    int s = s0;
-    for (; s + 16 <= s1; s += 16) {
-      float t[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) t[j] = p[(s + j) * stride];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v += t[j];
-    }
-    for (; s < s1; ++s) v += p[s * stride];
-  }
-  quarter[w][lane] = v;
-  __syncthreads();
-  if (w == 0 && live) {
-    const float sum = ((quarter[0][lane] + quarter[1][lane]) + quarter[2][lane]) + quarter[3][lane];
-    float* dst;
-    if (is_c) {
-      const long m = q / r.N, n = q - m * r.N;
-      dst = r.C + z * r.bsc + m * r.scm + n;
-    } else {
-      dst = r.rowsum + z * r.bsrs + (q - per);
-    }
-    *dst = sum;
-    const long idx = dst - tl.grads;                         // position in the gradient arena = in params / moments
-    if (tl.params && idx >= 0 && idx < tl.arena_floats) {    // (the 512-d head's moment sums go to the workspace)
-      const int g = adamw_group_of(idx % tl.p_stride, tl.lo1, tl.lo2, tl.hi2);
-      if (s_active[g]) {
-        float decay, w1, beta2, w2;
-        adamw_coeffs(tl.lr, tl.b1, tl.b2, tl.wd, decay, w1, beta2, w2);
-        adamw_update(tl.params, tl.m, tl.v, idx, sum, decay, w1, beta2, w2, s_step_size[g], s_bc2_sqrt[g], tl.eps);
-      }
-    }
-  }
-}
-static int red_blocks(const RedItem& r) {
-  return (int)(((long)r.batch * ((long)r.M * r.N + (r.rs_part ? r.M : 0)) + 63) / 64);
-}
-static void red_append(RedGroup& rg, const RedItem& r) {
-  if (rg.count == 0) rg.beg[0] = 0;
-  rg.it[rg.count] = r;
-  rg.beg[rg.count + 1] = rg.beg[rg.count] + red_blocks(r);
-  ++rg.count;
-}
-static void launch_reductions(hipStream_t st, RedGroup& rg) {
-  const int tail = rg.tail.loss_part ? 1 : 0;
-  if (rg.count) hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)(rg.beg[rg.count] + tail)), dim3(256), 0, st, rg);
-  rg.count = 0;
-}
-// items collected into the step's reduction launch (collect != NULL), or launched now as a group of their own
-static void red_emit(hipStream_t st, RedGroup* collect, const RedItem* items, int count) {
-  RedGroup own;
-  own.count = 0;
-  RedGroup& rg = collect ? *collect : own;
-  for (int i = 0; i < count; ++i) red_append(rg, items[i]);
-  if (!collect) launch_reductions(st, own);
-}
-// the layer GEMMs the resident-panel kernel takes (16-bit modes, rows k-contiguous, contraction <= 352, N <= 256)
-static bool panel_ok(const GemmEnv& E, int M, int N, int Kd, long sak, int splitk, bool rowsum, int nz) {
-  return OBJ_G16_AFULL && E.operands && sak == 1 && Kd <= 352 && N <= 256 && splitk <= 1 && M >= 4096 && !rowsum &&
-         E.packb && nz <= E.packb_entries;
-}
-
-static void gemm(GemmEnv& E, hipStream_t st, int batch, int M, int N, int Kd, const float* A, long sam, long sak, long bsa,
-                 const float* B, long sbk, long sbn, long bsb, float* C, long scm, long scn, long bsc,
-                 bool accumulate = false, const float* bias = nullptr, long bsbias = 0, bool relu = false,
-                 const float* mask = nullptr, long smm = 0, long smn = 0, long bsm = 0, int splitk = 1,
-                 float* rowsum = nullptr, long bsrs = 0) {
-  Gemm g;
-  g.M = M; g.N = N; g.Kd = Kd;
-  g.A = A; g.sam = sam; g.sak = sak; g.bsa = bsa;
-  g.B = B; g.sbk = sbk; g.sbn = sbn; g.bsb = bsb;
-  g.C = C; g.scm = scm; g.scn = scn; g.bsc = bsc;
-  g.bias = bias; g.bsbias = bsbias; g.mask = mask; g.smm = smm; g.smn = smn; g.bsm = bsm;
-  g.accumulate = accumulate; g.relu = relu; g.splitk = splitk;
-  g.rowsum = rowsum; g.bsrs = bsrs;
-  g.biasrow = E.biasrow; g.bsbr = E.bsbr; g.sbr = E.sbr;
-  g.vec4 = 0; g.Bp = nullptr; g.A2 = nullptr; g.sam2 = g.bsa2 = 0; g.k2 = Kd;
-  g.a16 = E.in_act16(A); g.b16 = E.in_act16(B); g.m16 = mask && E.in_act16(mask); g.c16 = E.in_act16(C);
-  g.a_scale = E.operands == 2 ? E.a_scale : 1.0f;
-  g.part = E.next_part; g.rs_part = E.next_rs_part;
-  E.next_part = E.next_rs_part = nullptr;
-  const int nz = batch * (splitk > 1 ? splitk : 1);
-  if (E.group && !E.operands && !(M >= 256 && N >= 192) && E.group->count < GemmGroup::MAXG) {
-    GemmGroup& gr = *E.group;               // collected; launched by flush_group(E, )
-    if (E.group16) {
-      // gemm_group16_kernel stages both operands k-major: rows contiguous in memory (weight gradients are)
-      if (!(sak != 1 && sam == 1 && sbk != 1 && sbn == 1)) { E.error = true; return; }      // (needs k-major operands)
-      g.vec4 = (sak % 4 == 0 && bsa % 4 == 0 && M % 4 == 0 && ((uintptr_t)A & 15) == 0) ? 1 : 0;
-    }
-    if (gr.count == 0) gr.zbeg[0] = 0;
-    gr.g[gr.count] = g;
-    gr.zbeg[gr.count + 1] = gr.zbeg[gr.count] + nz;
-    ++gr.count;
-    return;
-  }
-  if (E.operands) {
-    // operands whose rows are the contiguous dimension are staged k-major (exec is full at the transposing reads:
-    // out-of-range elements are zero-filled, never masked)
-    const bool akm = sak != 1 && sam == 1, bkm = sbk != 1 && sbn == 1;
-    // (split-K weight gradients with a narrow output -- the x1 / x2 columns of the concatenated layers, N = 87 / 42 --
-    // take the 128-row tile too: the streamed d_out^T operand is then read once instead of once per 64-row tile)
-    const bool wide = M >= 256 && (N >= 192 || (OBJ_G16_WIDE_NARROW && akm && splitk > 1 && N >= 40)), f16 = E.operands == 2;
-    const dim3 grid(wide ? (N + 127) / 128 : (N + 63) / 64, wide ? (M + 127) / 128 : (M + 63) / 64, nz);
-    // layer GEMMs over the sample axis: resident A panel (64 rows x the whole contraction), 64 x 256 tiles
-    if (panel_ok(E, M, N, Kd, sak, splitk, rowsum != nullptr, nz) && (wide || (OBJ_G16_AFULL_NARROW && Kd >= 128))) {
-      const int ka = E.a2.A2 ? E.a2.k2 : Kd;
-      g.A2 = E.a2.A2 ? E.a2.A2 : A; g.sam2 = E.a2.sam2; g.bsa2 = E.a2.bsa2; g.k2 = ka;
-      E.a2.A2 = nullptr;
-      g.vec4 = (ka % 8 == 0 && sam % 8 == 0 && bsa % 8 == 0 && ((uintptr_t)A & 15) == 0) ? 1 : 0;
-      if ((g.a16 && !g.vec4) || (g.c16 && g.b16)) { E.error = true; return; }   // (16-bit panel: aligned rows, one 16-bit side)
-      g.Bp = E.packb;
-      const dim3 pgrid(1, (M + 63) / 64, nz);
-#define OBJ_G16_PANEL(OT_, KM_)                                                                                         \
-      do {                                                                                                              \
-        hipLaunchKernelGGL((pack_b_kernel<OT_, KM_ / 32>), dim3(KM_ / 8, nz), dim3(256), 0, st, g, (OT_*)E.packb);      \
-        hipLaunchKernelGGL((gemm_bf16_kernel<2, 4, OT_, 32, 2, 4, false, false, true, KM_>), pgrid, dim3(512), 0, st, g); \
-      } while (0)
-      if (Kd <= 256) { if (f16) OBJ_G16_PANEL(_Float16, 256); else OBJ_G16_PANEL(__bf16, 256); }
-      else { if (f16) OBJ_G16_PANEL(_Float16, 352); else OBJ_G16_PANEL(__bf16, 352); }
-#undef OBJ_G16_PANEL
-      return;
-    }
-    E.a2.A2 = nullptr;
-    g.vec4 = (akm && sak % 4 == 0 && bsa % 4 == 0 && M % 4 == 0 && ((uintptr_t)A & 15) == 0) ? 1 : 0;
-    if ((g.a16 && !(akm && g.vec4)) || g.c16 || (g.b16 && !(bkm && sbk % 4 == 0 && N % 4 == 0 && bsb % 4 == 0))) {
-      E.error = true;                 // (16-bit activations in a GEMM shape that does not take them)
-      return;
-    }
-#define OBJ_G16_LAUNCH(OT_, AK_, BK_)                                                                                   \
-    do {                                                                                                                \
-      if (wide) hipLaunchKernelGGL((gemm_bf16_kernel<2, 4, OT_, OBJ_G16_BK_WIDE, 4, 2, AK_, BK_>), grid, dim3(512), 0, st, g); \
-      else hipLaunchKernelGGL((gemm_bf16_kernel<2, 2, OT_, OBJ_G16_BK, 2, 2, AK_, BK_>), grid, dim3(256), 0, st, g);    \
-    } while (0)
-#define OBJ_G16_LAUNCH_T(OT_)                                                                                           \
-    do {                                                                                                                \
-      if (akm && bkm) OBJ_G16_LAUNCH(OT_, true, true);                                                                  \
-      else if (bkm) OBJ_G16_LAUNCH(OT_, false, true);                                                                   \
-      else if (akm) OBJ_G16_LAUNCH(OT_, true, false);                                                                   \
-      else OBJ_G16_LAUNCH(OT_, false, false);                                                                           \
-    } while (0)
-    if (f16) OBJ_G16_LAUNCH_T(_Float16); else OBJ_G16_LAUNCH_T(__bf16);
-#undef OBJ_G16_LAUNCH_T
-#undef OBJ_G16_LAUNCH
-    return;
-  }
-  if (M >= 256 && N >= 192) {         // wide layer GEMMs (hidden 256): 128 x 128 tiles on 8 waves (3.5 % faster than the
-                                      // same tile on 4 waves with 64 accumulator registers each).  Up to N = 128 the
-                                      // 64 x 64 tiles win (measured, hidden 128): 4x the workgroups, 16 instead
-                                      // of 64 accumulator registers -> occupancy hides the operand latency
-    dim3 grid((N + 127) / 128, (M + 64 * OBJ_GEMM_WIDE_TM - 1) / (64 * OBJ_GEMM_WIDE_TM), nz);
-    hipLaunchKernelGGL(gemm_kernel8, grid, dim3(512), 0, st, g);
-  } else {
-    dim3 grid((N + 63) / 64, (M + 63) / 64, nz);
-    // (64-deep k stages for small grids were measured: slower -- the transposed LDS store conflicts dominate)
-    hipLaunchKernelGGL((gemm_kernel<2, 2>), grid, dim3(256), 0, st, g);
-  }
-}
-
-// weight gradient: C[M][N] += sum over the n samples; few output tiles, long contraction -> split-K + atomics.
-// bias_grad (optional, pre-zeroed like C): [M] column sums of the output-gradient operand, same pass.
-static void wgrad(GemmEnv& E, hipStream_t st, int batch, int M, int N, long n, const float* A, long sam, long sak, long bsa,
-                  const float* B, long sbk, long sbn, long bsb, float* C, long scm, long bsc,
-                  float* bias_grad = nullptr) {
-  int sk = wgrad_slices(batch, M, N, n);
-  if (E.max_slices > 0 && sk > E.max_slices) sk = E.max_slices;
-#ifndef OBJ_WGRAD_ATOMICS
-  // deterministic form: every slice stores its partial tile; an ordered reduction follows
-  const int skd = sk;
-  float* part = E.parts_alloc((size_t)batch * skd * M * N);
-  float* rs_part = (part && bias_grad) ? E.parts_alloc((size_t)batch * skd * M) : nullptr;
-  if (part && (!bias_grad || rs_part)) {
-    E.next_part = part; E.next_rs_part = rs_part;
-    gemm(E, st, batch, M, N, (int)n, A, sam, sak, bsa, B, sbk, sbn, bsb, C, scm, 1, bsc, false, nullptr, 0, false, nullptr, 0,
-         0, 0, skd, bias_grad, bsc);
-    RedItem r;
-    r.part = part; r.rs_part = rs_part; r.C = C; r.rowsum = bias_grad;
-    r.M = M; r.N = N; r.sk = skd; r.batch = batch; r.scm = scm; r.bsc = bsc; r.bsrs = bsc;
-    red_emit(st, (E.red_group && E.red_group->count < RedGroup::MAXG) ? E.red_group : nullptr, &r, 1);
-    return;
-  }
-#endif
-  if (E.need_parts) { E.parts_failed = true; return; }
-  gemm(E, st, batch, M, N, (int)n, A, sam, sak, bsa, B, sbk, sbn, bsb, C, scm, 1, bsc, false, nullptr, 0, false, nullptr, 0,
-       0, 0, sk, bias_grad, bsc);
-}
 
 // ------------------------------------------------------------------------------------------------
 // Small-batch forward for hidden 128 (the background network at the reference's native batch, 1200 rays x 14
@@ -1581,7 +540,7 @@ static void launch_small_rt(hipStream_t st, const Args& f, int K, bool bf, int r
 
 // row tiles per workgroup: the smallest RT for which K * ceil(n / (16 RT)) workgroups fit the chip in one round;
 // 0 = not a small batch
-static int small_batch_rt(const GemmEnv& E, int H, long n, int K) {
+static int small_batch_rt(int operands, int H, long n, int K) {
   if (H != FS_H) return 0;
   for (int rt = 1; rt <= 5; ++rt)
     if ((long)K * ((n + 16 * rt - 1) / (16 * rt)) <= 256) return rt;
@@ -1589,29 +548,11 @@ static int small_batch_rt(const GemmEnv& E, int H, long n, int K) {
   // step, 38 400: 0.53 vs 0.65); beyond that the GEMM path runs near the MFMA peak
   // (fp32 and bf16 modes: the one-launch kernels exist for both; fp16 keeps the GEMM path from two rounds on)
 #ifdef OBJ_NO_SMALL_BF16        // diagnostic: the bf16 mode on the GEMM path from two rounds on (tools/bg_ab.py)
-  if (E.operands == 0 && (long)K * ((n + 79) / 80) <= 1024) return 5;
+  if (operands == 0 && (long)K * ((n + 79) / 80) <= 1024) return 5;
 #else
-  if (E.operands != 2 && (long)K * ((n + 79) / 80) <= 1024) return 5;
+  if (operands != 2 && (long)K * ((n + 79) / 80) <= 1024) return 5;
 #endif
   return 0;
-}
-
-static void flush_group(GemmEnv& E, hipStream_t st, GemmGroup& gr) {
-  E.group = nullptr;
-  if (gr.count == 0) return;
-  int mx = 1, my = 1;
-  for (int i = 0; i < gr.count; ++i) {
-    mx = std::max(mx, (gr.g[i].N + 63) / 64);
-    my = std::max(my, (gr.g[i].M + 63) / 64);
-  }
-  if (E.group16 && OBJ_GROUP16_WIDE)
-    hipLaunchKernelGGL(gemm_group16_kernel, dim3((mx + 1) / 2, (my + 1) / 2, gr.zbeg[gr.count]), dim3(OBJ_GROUP16_WIDE ? 512 : 256), 0, st, gr);
-  else if (E.group16) hipLaunchKernelGGL(gemm_group16_kernel, dim3(mx, my, gr.zbeg[gr.count]), dim3(256), 0, st, gr);
-  else hipLaunchKernelGGL(gemm_group_kernel, dim3((mx + 1) / 2, (my + 1) / 2, gr.zbeg[gr.count] + gr.task.blocks), dim3(512), 0, st, gr);
-  gr.count = 0;
-  gr.task.blocks = 0;
-  E.group16 = false;
-  E.red_group = nullptr;                 // (the caller launches the collected reductions: launch_reductions)
 }
 
 // Activation loads of the kernels around the GEMMs: act = 0 fp32 storage, 1 bf16, 2 fp16 (the 16-bit modes keep
@@ -1836,40 +777,12 @@ __global__ void copy_cols_kernel(long rows, int cols, const float* src, long lds
 // ------------------------------------------------------------------------------------------------
 // Feature-distillation branch with the 512-d head hoisted past the compositing, any hidden width Hh
 // (the hidden-32 fused kernel has its own copies in objnerf_train.hip).
-// beta = b_of . g, |g| of ray r of object k (gt_feat [K][R][C]) into the last two columns of its rayin record  (u =
-// W_of^T g is a GEMM): the 16 lanes of a DPP row share the ray
-__device__ __forceinline__ void featg_ray_stats(const float* B, const int C, const int R, const float* gt_feat,
-                                                float* rayin, const int rin_ld, const int k, const long r, const int l16) {
-  float bs = 0.f, gs = 0.f;
-  if (r < R) {
-    const float* gp = gt_feat + ((long)k * R + r) * C;
-    for (int cc = l16; cc < C; cc += 16) {
-      const float gv = gp[cc];
-      bs = fmaf(B[cc], gv, bs);
-      gs = fmaf(gv, gv, gs);
-    }
-  }
-  bs = dpp_rowsum16(bs);
-  gs = dpp_rowsum16(gs);
-  if (r < R && l16 == 0) {
-    float* o = rayin + ((long)k * R + r) * rin_ld;
-    o[rin_ld - 2] = bs;
-    o[rin_ld - 1] = sqrtf(gs);
-  }
-}
 __global__ __launch_bounds__(256) void featg_rowstats_kernel(const float* params, long p_stride, int off_b, int C, int R,
                                                              int rin_ld, const float* gt_feat, float* rayin) {
   const int k = blockIdx.y;
   const int l16 = threadIdx.x & 15;
   const long r = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
   featg_ray_stats(params + (long)k * p_stride + off_b, C, R, gt_feat, rayin, rin_ld, k, r, l16);
-}
-// Entry h of [wb | bb], wb = W_of^T b_of (h < Hh), bb = b_of . b_of (h == Hh): one wave per entry
-__device__ __forceinline__ float featg_wb_entry(const float* W, const float* B, const int C, const int Hh, const int h,
-                                                const int lane) {
-  float acc = 0.f;
-  for (int cc = lane; cc < C; cc += 64) acc = fmaf(h < Hh ? W[(long)cc * Hh + h] : B[cc], B[cc], acc);
-  return wave_sum64(acc);
 }
 // [wb | bb] appended to the Gram matrix: gram[k][Hh * Hh + h], [Hh * Hh + Hh]
 __global__ __launch_bounds__(64) void featg_wb_kernel(const float* params, long p_stride, int off_w, int off_b, int C,
@@ -1930,38 +843,6 @@ __global__ __launch_bounds__(256) void featg_finish_kernel(const float* params, 
   grads[(long)k * p_stride + (hh < Hh ? off_w + (long)cc * Hh + hh : off_b + cc)] = gr;
 }
 
-// FeatPrepTask (512 threads per workgroup): featg_wb_kernel's, featg_rowstats_kernel's work and the [W_of | b_of] copy.
-// b = (object, pass-local index)
-__device__ void feat_prep_task(const FeatPrepTask& t, int b) {
-  const int per = t.nb_wb + t.nb_rs + t.nb_snap;
-  const int k = b / per;
-  b -= k * per;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const float* W = t.params + (long)k * t.ps + t.off_w;
-  const float* B = t.params + (long)k * t.ps + t.off_b;
-  if (b < t.nb_wb) {                                       // wb[h] = W_of[:, h] . b_of (h < Hh), bb = b_of . b_of: a wave per entry
-    const int h = 8 * b + wv;
-    if (h <= t.Hh) {
-      const float acc = featg_wb_entry(W, B, t.C, t.Hh, h, lane);
-      if (lane == 0) t.gram[(long)k * t.gstride + (long)t.Hh * t.Hh + h] = acc;
-    }
-    return;
-  }
-  b -= t.nb_wb;
-  if (b < t.nb_rs) {                                       // beta, |g| of 32 rays: 16 lanes per ray
-    const int l16 = tid & 15;
-    const long r = (long)b * 32 + (tid >> 4);
-    featg_ray_stats(B, t.C, t.R, t.gt_feat, t.rayin, t.rin_ld, k, r, l16);
-    return;
-  }
-  b -= t.nb_rs;
-  if (t.snap) {                                            // [W_of (C x Hh) | b_of (C)] as they are BEFORE the step
-    float* o = t.snap + (long)k * ((long)t.C * (t.Hh + 1));
-    const long tot = (long)t.C * (t.Hh + 1);
-    for (long i = (long)b * 2048 + tid; i < tot && i < (long)(b + 1) * 2048; i += 512)
-      o[i] = i < (long)t.C * t.Hh ? W[i] : B[i - (long)t.C * t.Hh];
-  }
-}
 // featg_finish_kernel + the head's AdamW in one launch (the one-launch background iteration with an optimiser attached):
 // the entry's gradient is formed from the COPY of [W_of | b_of] (FeatPrepTask; a gradient needs a whole row of W_of that
 // other threads of this launch are stepping) and stepped at once as the feature group [lo2, hi2) (objnerf_step_tail.h),
@@ -1997,17 +878,13 @@ __global__ __launch_bounds__(256) void featg_finish_adamw_kernel(const float* sn
 
 inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
-struct Offs {
-  int64_t o[OBJNERF_N_TENSORS + 1];
-  int64_t ps;
-};
 
 // workspace carve (floats)
 struct WS {
   float *emb, *h1, *h2, *h3, *h4, *hc, *hf, *alpha, *color, *d_alpha, *d_color, *dhead;
   float *d_hf, *rayin, *gram, *rayfeat, *X1, *X2, *Tm, *mom;      // feature branch (hoisted head)
   float *dA, *dB_, *dC, *dD, *dE, *d_emb, *dBpe, *pts;
-  float* parts; size_t parts_floats;      // split-K partial slabs of the step's weight-gradient GEMMs (wgrad(E, ))
+  float* parts; size_t parts_floats;      // split-K partial slabs of the step's weight-gradient GEMMs (wgrad())
   float* loss_part;                       // [K R][4] block partials of the loss terms
   float* packb;                           // [K][90112] 16-bit: packed B image of the AFULL layer GEMM in flight
   size_t act_floats;                      // room of each of h1 .. hc (floats)
@@ -2017,7 +894,7 @@ struct WS {
 
 // the 16-bit modes keep h1 .. hc in the operand type when the resident-panel GEMMs serve the shape (hidden 256, >= 4096
 // samples per object): those five buffers then take half the room
-static bool acts16_shape(int H, long n) { return OBJ_ACT16 && OBJ_G16_AFULL && H == 256 && n >= 4096; }
+static bool acts16_shape(int H, long n) { return H == 256 && n >= 4096; }
 static WS carve(char* base, int H, int C, long n, long R, int K, bool feat, bool half_acts = false) {
   WS w;
   char* p = base;
@@ -2043,7 +920,7 @@ static WS carve(char* base, int H, int C, long n, long R, int K, bool feat, bool
   w.dBpe = take((size_t)K * 64);
   w.pts = take((size_t)K * n * 3);          // sample positions of the origins / directions form of the batch
   {
-    // every weight-gradient GEMM of the step with its own slice count (wgrad(E, )): (M, N, samples, has bias)
+    // every weight-gradient GEMM of the step with its own slice count (wgrad()): (M, N, samples, has bias)
     const size_t XC = (size_t)H + 1, Hs = (size_t)H;
     size_t tot = 0;
     auto add = [&](int M, int N, long ns, bool bias) {
@@ -2083,28 +960,23 @@ size_t train_workspace_bytes(const objnerf_net* net, int K, int R, int S, int fe
 
 }  // namespace objgen
 
-// objnerf_context: the helper streams + events of the layer-wise path, owned by the CALLER (objnerf_context_create /
+// objnerf_context: the helper stream + events of the layer-wise path, owned by the CALLER (objnerf_context_create /
 // _destroy are the only entries of the library that create anything).  Without one every launch stays on `stream`.
 struct objnerf_context {
-  static constexpr int NEV = 16, NS = 3;
-  hipStream_t s = nullptr;             // = all[0]
-  hipStream_t all[NS];                 // train_step forks onto all[0] only (all[1..] and their events are created but idle)
-  hipEvent_t ev[NEV];
-  hipEvent_t done, done_all[NS];
-  bool own = false;                    // false: single-stream stand-in (all[] = the caller's stream, no events)
+  static constexpr int NEV = 16;
+  hipStream_t s = nullptr;             // the side stream train_step forks onto
+  hipEvent_t ev[NEV];                  // fork events, used round-robin
+  hipEvent_t done, done_all;           // joins: the feature preparation, the whole side stream
+  bool own = false;                    // false: single-stream stand-in (s = the caller's stream, no events)
 };
 
 extern "C" int objnerf_context_create(objnerf_context** out) {
   if (!out) return OBJNERF_EINVAL;
   objnerf_context* c = new objnerf_context();
-  bool ok = true;
-  for (int i = 0; i < objnerf_context::NS; ++i) {   // non-blocking: never synchronises with the null stream
-    ok &= hipStreamCreateWithFlags(&c->all[i], hipStreamNonBlocking) == hipSuccess;
-    ok &= hipEventCreateWithFlags(&c->done_all[i], hipEventDisableTiming) == hipSuccess;
-  }
+  bool ok = hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking) == hipSuccess;   // never synchronises with the null stream
   for (int i = 0; i < objnerf_context::NEV; ++i) ok &= hipEventCreateWithFlags(&c->ev[i], hipEventDisableTiming) == hipSuccess;
   ok &= hipEventCreateWithFlags(&c->done, hipEventDisableTiming) == hipSuccess;
-  c->s = c->all[0];
+  ok &= hipEventCreateWithFlags(&c->done_all, hipEventDisableTiming) == hipSuccess;
   c->own = true;
   if (!ok) { delete c; return OBJNERF_ELAUNCH; }
   *out = c;
@@ -2114,9 +986,10 @@ extern "C" int objnerf_context_create(objnerf_context** out) {
 extern "C" int objnerf_context_destroy(objnerf_context* c) {
   if (!c) return OBJNERF_OK;
   if (c->own) {
-    for (int i = 0; i < objnerf_context::NS; ++i) { (void)hipStreamDestroy(c->all[i]); (void)hipEventDestroy(c->done_all[i]); }
+    (void)hipStreamDestroy(c->s);
     for (int i = 0; i < objnerf_context::NEV; ++i) (void)hipEventDestroy(c->ev[i]);
     (void)hipEventDestroy(c->done);
+    (void)hipEventDestroy(c->done_all);
   }
   delete c;
   return OBJNERF_OK;
@@ -2183,60 +1056,71 @@ struct NetView {
   const float* emb; float* d_emb;                           // [K][n][OBJ_EMB]
   float *h1, *h2, *h3, *h4, *hc, *hf;
   float *d_hc, *d_h4, *d_h3, *d_h2, *d_h1, *d_hf;
+  // storage of those buffers: act16 -- h1 .. hc and d_hc .. d_h1 hold the step's 16-bit operand type (the 16-bit modes at
+  // hidden 256, train_step_small in bf16 mode); hf16 -- so do hf and d_hf (train_step_small in bf16 mode only).  emb,
+  // d_emb, parameters and gradients are always fp32.
+  bool act16, hf16;
+  float grad_scale;    // d_hc .. d_h1, d_hf are stored multiplied by this power of two (Gemm::a_scale; fp16 mode)
+  bool out16(const LayerDesc& L) const { return L.w == OBJNERF_T_FL_W ? hf16 : act16; }      // a layer's out / d_out
 };
-struct Rows { const float* p; long ld, bs; };               // a [K][n][ld] operand: row stride, batch stride
-static Rows main_rows(const NetView& c, const LayerDesc& L, const float* h) {
-  return L.from_emb() ? Rows{c.emb, OBJ_EMB, c.n * OBJ_EMB} : Rows{h, c.H, c.n * c.H};
+// the [K][n][ld] operands of a layer: its main input (an activation, or x1 of emb) and its side input (columns of emb)
+static Operand main_rows(const NetView& c, const LayerDesc& L, const float* h) {
+  return L.from_emb() ? op_rows(c.emb, OBJ_EMB, c.n * OBJ_EMB) : op_rows(h, c.H, c.n * c.H, c.act16);
 }
-static Rows side_rows(const NetView& c, const LayerDesc& L) { return Rows{c.emb + L.side_col, OBJ_EMB, c.n * OBJ_EMB}; }
+static Operand side_rows(const NetView& c, const LayerDesc& L) { return op_rows(c.emb + L.side_col, OBJ_EMB, c.n * OBJ_EMB); }
 
 // out = relu([in | side] W^T + b).  fuse2: [in | side] as ONE contraction (the resident-panel kernel reads the side
 // input as its second A source: no round trip of the partial result)
-static void layer_fwd(GemmEnv& E, hipStream_t st, const NetView& c, const LayerDesc& L, const float* in, float* out,
+static void layer_fwd(GemmStep& E, hipStream_t st, const NetView& c, const LayerDesc& L, const float* in, float* out,
                       bool fuse2 = false) {
   const int H = c.H, K = c.K, M = (int)c.n;
-  const long nH = c.n * H, ps = c.ps;
-  const Rows a = main_rows(c, L, in), s = side_rows(c, L);
+  const long ps = c.ps;
+  const Operand a = main_rows(c, L, in), s = side_rows(c, L), o = op_rows(out, H, c.n * H, c.out16(L));
   const float *W = c.P + c.off[L.w], *b = c.P + c.off[L.b];
   if (!L.in_side || fuse2) {
-    if (L.in_side) E.a2 = A2Src{s.p, s.ld, s.bs, L.in_main};
-    gemm(E, st, K, M, H, L.ld(), a.p, a.ld, 1, a.bs, W, 1, L.ld(), ps, out, H, 1, nH, false, b, ps, true);
+    GemmOpts f = {.relu = true, .bias = b, .bsbias = ps};
+    if (L.in_side) f.a2 = A2Src{s.p, s.s0, s.bs, L.in_main};
+    gemm(E, st, K, M, H, L.ld(), a, op_cols(W, L.ld(), ps), o, f);
   } else {
-    gemm(E, st, K, M, H, L.in_main, a.p, a.ld, 1, a.bs, W, 1, L.ld(), ps, out, H, 1, nH);
-    gemm(E, st, K, M, H, L.in_side, s.p, s.ld, 1, s.bs, W + L.in_main, 1, L.ld(), ps, out, H, 1, nH, true, b, ps, true);
+    gemm(E, st, K, M, H, L.in_main, a, op_cols(W, L.ld(), ps), o);
+    gemm(E, st, K, M, H, L.in_side, s, op_cols(W + L.in_main, L.ld(), ps), o,
+         {.accumulate = true, .relu = true, .bias = b, .bsbias = ps});
   }
 }
 // d W = d_out^T [in | side], d b = column sums of d_out (riding on the main part's GEMM: row sums of its operand tile)
-static void layer_wgrad(GemmEnv& E, hipStream_t st, const NetView& c, const LayerDesc& L, const float* d_out,
-                        const float* in) {
+static void layer_wgrad(GemmStep& E, hipStream_t st, const WgradHow& how, const NetView& c, const LayerDesc& L,
+                        const float* d_out, const float* in) {
   const int H = c.H, K = c.K;
-  const long n = c.n, nH = n * H, ps = c.ps;
-  const Rows a = main_rows(c, L, in), s = side_rows(c, L);
+  const long n = c.n, ps = c.ps;
+  const Operand a = main_rows(c, L, in), s = side_rows(c, L), dT = op_cols(d_out, H, n * H, c.out16(L));
   float *dW = c.G + c.off[L.w], *db = c.G + c.off[L.b];
-  wgrad(E, st, K, H, L.in_main, n, d_out, 1, H, nH, a.p, a.ld, 1, a.bs, dW, L.ld(), ps, db);
-  if (L.in_side) wgrad(E, st, K, H, L.in_side, n, d_out, 1, H, nH, s.p, s.ld, 1, s.bs, dW + L.in_main, L.ld(), ps);
+  wgrad(E, st, how, K, H, L.in_main, n, dT, a, op_rows(dW, L.ld(), ps), db, c.grad_scale);
+  if (L.in_side) wgrad(E, st, how, K, H, L.in_side, n, dT, s, op_rows(dW + L.in_main, L.ld(), ps), nullptr, c.grad_scale);
 }
 // d_in (+)= (d_out W_main) o [mask > 0] and d_emb[:, side columns] (+)= d_out W_side; the in layer's input IS x1, so its
 // main part lands in d_emb.  fold_dhead (colour layer without the feature branch): the alpha head's rank-1 term
 // wa x dhead[:, 0] is added in the epilogue (Gemm::biasrow), so d_in is written once instead of written, read and written.
-static void layer_dgrad(GemmEnv& E, hipStream_t st, const NetView& c, const LayerDesc& L, const float* d_out, float* d_in,
+static void layer_dgrad(GemmStep& E, hipStream_t st, const NetView& c, const LayerDesc& L, const float* d_out, float* d_in,
                         const float* mask, bool accumulate, bool side_accumulate = false, const float* fold_dhead = nullptr) {
   const int H = c.H, K = c.K, M = (int)c.n;
   const long n = c.n, nH = n * H, ps = c.ps;
   const float* W = c.P + c.off[L.w];
-  float* out = L.from_emb() ? c.d_emb : d_in;
-  const long ldo = L.from_emb() ? OBJ_EMB : H, bso = n * ldo;
-  const float* wa = fold_dhead ? c.P + c.off[OBJNERF_T_ALPHA_W] : nullptr;      // (the folded form overwrites)
-  if (fold_dhead) { E.biasrow = fold_dhead; E.bsbr = n * 4; E.sbr = 4; }
-  gemm(E, st, K, M, L.in_main, H, d_out, H, 1, nH, W, L.ld(), 1, ps, out, ldo, 1, bso, accumulate && !wa, wa, wa ? ps : 0,
-       false, mask, mask ? H : 0, mask ? 1 : 0, mask ? nH : 0);
-  E.biasrow = nullptr; E.bsbr = 0; E.sbr = 1;
+  const Operand d = op_rows(d_out, H, nH, c.out16(L));
+  const Operand out = L.from_emb() ? op_rows(c.d_emb, OBJ_EMB, n * OBJ_EMB) : op_rows(d_in, H, nH, c.act16);
+  GemmOpts o = {.accumulate = accumulate, .a_scale = c.grad_scale};
+  if (mask) o.mask = op_rows(mask, H, nH, c.act16);
+  if (fold_dhead) {                                                             // (the folded form overwrites)
+    o.accumulate = false;
+    o.bias = c.P + c.off[OBJNERF_T_ALPHA_W]; o.bsbias = ps;
+    o.biasrow = fold_dhead; o.bsbr = n * 4; o.sbr = 4;
+  }
+  gemm(E, st, K, M, L.in_main, H, d, op_rows(W, L.ld(), ps), out, o);
   if (L.in_side)
-    gemm(E, st, K, M, L.in_side, H, d_out, H, 1, nH, W + L.in_main, L.ld(), 1, ps, c.d_emb + L.side_col, OBJ_EMB, 1,
-         n * OBJ_EMB, side_accumulate);
+    gemm(E, st, K, M, L.in_side, H, d, op_rows(W + L.in_main, L.ld(), ps), op_rows(c.d_emb + L.side_col, OBJ_EMB, n * OBJ_EMB),
+         {.accumulate = side_accumulate, .a_scale = c.grad_scale});
 }
 // h1 .. hc, alpha / color and (hf != NULL) the feature layer.  act16: h1 .. hc live in the operand type (train_step)
-static void forward_chain(GemmEnv& E, hipStream_t st, const NetView& c, float* alpha, float* color, float* hf, int act16) {
+static void forward_chain(GemmStep& E, hipStream_t st, const NetView& c, float* alpha, float* color, float* hf, int act16) {
   const int H = c.H;
   const bool fuse2 = panel_ok(E, (int)c.n, H, H + OBJ_E1, 1, 1, false, c.K) && H == 256;
   layer_fwd(E, st, c, layer_desc(L_IN, H), nullptr, c.h1);
@@ -2251,27 +1135,27 @@ static void forward_chain(GemmEnv& E, hipStream_t st, const NetView& c, float* a
 }
 // the weight gradients alone (the dgrad chain ran in a kernel of its own): colour, mid2, cat, mid1, in; the feature
 // layer first (train_step's small-batch branch) or last (train_step_small) -- GemmGroup slots and slab addresses follow
-static void wgrad_chain(GemmEnv& E, hipStream_t st, const NetView& c, bool feat, bool feat_first) {
+static void wgrad_chain(GemmStep& E, hipStream_t st, const WgradHow& how, const NetView& c, bool feat, bool feat_first) {
   const int H = c.H;
-  if (feat && feat_first) layer_wgrad(E, st, c, layer_desc(L_FL, H), c.d_hf, c.h4);
-  layer_wgrad(E, st, c, layer_desc(L_CL, H), c.d_hc, c.h4);
-  layer_wgrad(E, st, c, layer_desc(L_M2, H), c.d_h4, c.h3);
-  layer_wgrad(E, st, c, layer_desc(L_CAT, H), c.d_h3, c.h2);
-  layer_wgrad(E, st, c, layer_desc(L_M1, H), c.d_h2, c.h1);
-  layer_wgrad(E, st, c, layer_desc(L_IN, H), c.d_h1, nullptr);
-  if (feat && !feat_first) layer_wgrad(E, st, c, layer_desc(L_FL, H), c.d_hf, c.h4);
+  if (feat && feat_first) layer_wgrad(E, st, how, c, layer_desc(L_FL, H), c.d_hf, c.h4);
+  layer_wgrad(E, st, how, c, layer_desc(L_CL, H), c.d_hc, c.h4);
+  layer_wgrad(E, st, how, c, layer_desc(L_M2, H), c.d_h4, c.h3);
+  layer_wgrad(E, st, how, c, layer_desc(L_CAT, H), c.d_h3, c.h2);
+  layer_wgrad(E, st, how, c, layer_desc(L_M1, H), c.d_h2, c.h1);
+  layer_wgrad(E, st, how, c, layer_desc(L_IN, H), c.d_h1, nullptr);
+  if (feat && !feat_first) layer_wgrad(E, st, how, c, layer_desc(L_FL, H), c.d_hf, c.h4);
 }
 // the layer-wise backward from d_hc / d_h4 (heads_bwd_kernel) and d_hf: per layer the weight gradient on `wst` and the
 // input gradient on `st`; fork() runs ahead of every layer but the feature layer (whose caller has just forked).
 // d_emb needs no zero fill: the first dgrad into each column block overwrites (x2: feature layer if present, else
 // colour layer; x1: cat layer), later ones accumulate; columns 0..2 (d t) are never read.
 template <class Fork>
-static void backward_chain(GemmEnv& E, hipStream_t st, hipStream_t wst, const NetView& c, bool feat,
+static void backward_chain(GemmStep& E, hipStream_t st, hipStream_t wst, const NetView& c, bool feat,
                            const float* fold_dhead, Fork fork) {
   const int H = c.H;
   if (feat) {     // feature layer: grads + contributions to d_h4 / d_x2
     const LayerDesc L = layer_desc(L_FL, H);
-    layer_wgrad(E, wst, c, L, c.d_hf, c.h4);
+    layer_wgrad(E, wst, {}, c, L, c.d_hf, c.h4);
     layer_dgrad(E, st, c, L, c.d_hf, c.d_h4, nullptr, true, false);
   }
   const struct { int l; const float* d_out; float* h; float* d_in; bool acc; } steps[5] = {
@@ -2283,7 +1167,7 @@ static void backward_chain(GemmEnv& E, hipStream_t st, hipStream_t wst, const Ne
   for (const auto& s : steps) {
     const LayerDesc L = layer_desc(s.l, H);
     fork();
-    layer_wgrad(E, wst, c, L, s.d_out, s.h);
+    layer_wgrad(E, wst, {}, c, L, s.d_out, s.h);
     layer_dgrad(E, st, c, L, s.d_out, s.d_in, s.h, s.acc, s.l == L_CL && feat, s.l == L_CL ? fold_dhead : nullptr);
   }
 }
@@ -2315,35 +1199,37 @@ template <class T> static void set_forward_offsets(T& f, const int64_t* off) {
   f.o_oc_w = (int)off[OBJNERF_T_OC_W]; f.o_oc_b = (int)off[OBJNERF_T_OC_B];
 }
 
-// ---- the hoisted 512-d feature head on the caller's GemmEnv and stream.  The head is NOT applied per
+// ---- the hoisted 512-d feature head on the caller's GemmStep and stream.  The head is NOT applied per
 // sample: per object G = W_of^T W_of (+ wb, bb), per ray u = W_of^T g, beta, |g| ahead of the loss; behind it the head's
 // gradient d W_of = gt_feat^T [a fh] + W_of M2 + b_of m1^T, d b_of = gt_feat^T [a O] + W_of m1 + b_of s2 from the moments
 // [M2 m1; . s2] = [c fh | c O]^T [fh | O]: two split-K GEMMs over the rays + a small finish
-struct FeatHeadArgs { int K, R, Hh, C; const float* P; long ps; int off_w, off_b; const float* gt_feat; };
-static void feat_gram_gemm(GemmEnv& E, hipStream_t st, const FeatHeadArgs& h, float* gram, long gst) {
-  gemm(E, st, h.K, h.Hh, h.Hh, h.C, h.P + h.off_w, 1, h.Hh, h.ps, h.P + h.off_w, h.Hh, 1, h.ps, gram, h.Hh, 1, gst);
+static void feat_gram_gemm(GemmStep& E, hipStream_t st, const FeatHeadArgs& h, float* gram, long gst, GroupLaunch* group = nullptr) {
+  const float* W = h.P + h.off_w;
+  gemm(E, st, h.K, h.Hh, h.Hh, h.C, op_cols(W, h.Hh, h.ps), op_rows(W, h.Hh, h.ps), op_rows(gram, h.Hh, gst), {.group = group});
 }
-static void feat_rays_gemm(GemmEnv& E, hipStream_t st, const FeatHeadArgs& h, float* rayin) {
+static void feat_rays_gemm(GemmStep& E, hipStream_t st, const FeatHeadArgs& h, float* rayin, GroupLaunch* group = nullptr) {
   const long R = h.R;
-  gemm(E, st, h.K, h.R, h.Hh, h.C, h.gt_feat, h.C, 1, R * h.C, h.P + h.off_w, h.Hh, 1, h.ps, rayin, h.Hh + 2, 1,
-       R * (h.Hh + 2));
+  gemm(E, st, h.K, h.R, h.Hh, h.C, op_rows(h.gt_feat, h.C, R * h.C), op_rows(h.P + h.off_w, h.Hh, h.ps),
+       op_rows(rayin, h.Hh + 2, R * (h.Hh + 2)), {.group = group});
 }
-static void feat_gram_enqueue(GemmEnv& E, hipStream_t st, const FeatHeadArgs& h, float* gram, long gst) {
+static void feat_gram_enqueue(GemmStep& E, hipStream_t st, const FeatHeadArgs& h, float* gram, long gst) {
   feat_gram_gemm(E, st, h, gram, gst);
   hipLaunchKernelGGL(featg_wb_kernel, dim3(h.Hh + 1, h.K), dim3(64), 0, st, h.P, h.ps, h.off_w, h.off_b, h.C, h.Hh, gram, gst);
 }
-static void feat_prep_enqueue(GemmEnv& E, hipStream_t st, const FeatHeadArgs& h, const FeatHead& f) {
+static void feat_prep_enqueue(GemmStep& E, hipStream_t st, const FeatHeadArgs& h, const FeatHead& f) {
   feat_gram_enqueue(E, st, h, f.gram, (long)h.Hh * h.Hh + h.Hh + 1);
   feat_rays_gemm(E, st, h, f.rayin);
   hipLaunchKernelGGL(featg_rowstats_kernel, dim3((unsigned)((h.R + 15) / 16), h.K), dim3(256), 0, st, h.P, h.ps, h.off_b, h.C,
                      h.R, h.Hh + 2, h.gt_feat, f.rayin);
 }
-// T = gt_feat^T [a fh | a O], M = [c fh | c O]^T [fh | O] over the rays (X1 / X2: featg_scale_kernel or the fused kernel)
-static void feat_moments_enqueue(GemmEnv& E, hipStream_t st, const FeatHeadArgs& h, const FeatHead& f) {
+// T = gt_feat^T [a fh | a O], M = [c fh | c O]^T [fh | O] over the rays (X1 / X2: featg_scale_kernel or the fused kernel);
+// targets and moments, not back-propagated gradients: no gradient scale
+static void feat_moments_enqueue(GemmStep& E, hipStream_t st, const WgradHow& how, const FeatHeadArgs& h, const FeatHead& f) {
   const int XC = h.Hh + 1;
   const long R = h.R;
-  wgrad(E, st, h.K, h.C, XC, R, h.gt_feat, 1, h.C, R * h.C, f.X1, XC, 1, R * XC, f.Tm, XC, (long)h.C * XC);
-  wgrad(E, st, h.K, XC, XC, R, f.X2, 1, XC, R * XC, f.rayfeat, h.Hh + 3, 1, R * (h.Hh + 3), f.mom, XC, (long)XC * XC);
+  wgrad(E, st, how, h.K, h.C, XC, R, op_cols(h.gt_feat, h.C, R * h.C), op_rows(f.X1, XC, R * XC), op_rows(f.Tm, XC, (long)h.C * XC));
+  wgrad(E, st, how, h.K, XC, XC, R, op_cols(f.X2, XC, R * XC), op_rows(f.rayfeat, h.Hh + 3, R * (h.Hh + 3)),
+        op_rows(f.mom, XC, (long)XC * XC));
 }
 // d W_of = T + W_of M + b_of m^T, d b_of likewise
 static void feat_finish_enqueue(hipStream_t st, const FeatHeadArgs& h, const FeatHead& f, float* grads) {
@@ -2359,7 +1245,16 @@ static NetView net_view(const WS& w, const float* P, float* G, long ps, const in
   c.emb = w.emb; c.d_emb = w.d_emb;
   c.h1 = w.h1; c.h2 = w.h2; c.h3 = w.h3; c.h4 = w.h4; c.hc = w.hc; c.hf = w.hf;
   c.d_hc = w.dA; c.d_h4 = w.dB_; c.d_h3 = w.dC; c.d_h2 = w.dD; c.d_h1 = w.dE; c.d_hf = w.d_hf;
+  c.act16 = c.hf16 = false; c.grad_scale = 1.0f;      // (fp32 storage; the 16-bit steps say otherwise)
   return c;
+}
+// the step's constants from its carve
+static GemmStep gemm_step(const WS& w, int operands, int K) {
+  GemmStep E;
+  E.operands = operands;
+  E.parts = w.parts; E.parts_cap = w.parts_floats;
+  E.packb = w.packb; E.packb_entries = w.packb ? K : 0;
+  return E;
 }
 // test hook (objnerf_train_args.relu_masks): the iteration's ReLU branch bits; act16 / hf16: storage type of h1 .. hc / hf
 static void emit_relu_masks(hipStream_t st, const NetView& c, uint8_t* masks, int act16, int hf16) {
@@ -2375,16 +1270,22 @@ static FeatHead feat_head_view(const WS& w) { return {w.gram, w.rayin, w.rayfeat
 // The one-launch small-batch iteration: train_small_kernel -> the seven weight-gradient GEMMs as ONE grouped launch ->
 // ONE reduction launch (weight-gradient slices, head / d B / loss partials, status, optionally AdamW).  Everything on
 // the caller's stream: three dependent launches need no helper stream and no events.
-static int train_step_small(const objnerf_net* net, const objnerf_train_args* a, hipStream_t st, GemmEnv& E, const WS& w,
+static int train_step_small(const objnerf_net* net, const objnerf_train_args* a, hipStream_t st, const WS& w,
                             const int64_t* off, bool bf, int* done) {
   const int H = net->hidden, K = a->K, S = a->S, C = net->feat_dim;
+  // every GEMM of this step goes through a grouped launch, which has its own operand type (bf16 mode: the weight
+  // gradients' group); whatever a group does not take is an fp32 GEMM
+  GemmStep E = gemm_step(w, 0, K);
   const long n = (long)a->R * S, ps = a->p_stride;
   const bool feat = a->gt_feat != nullptr;
   const int rpw = sf_rays_per_wg(S, feat);
   const int nwg = (int)(((long)a->R + rpw - 1) / rpw);
   const float* P = a->params;
   float* G = a->grads;
-  const NetView c = net_view(w, P, G, ps, off, K, n, H);
+  NetView c = net_view(w, P, G, ps, off, K, n, H);
+  // bf16 mode: train_small_kernel stores h1 .. hc (hf, d_hf) and d_hc .. d_h1 as bf16 (objnerf_small_body.h, `hst`); the
+  // grouped launch passes them through unconverted
+  c.act16 = bf; c.hf16 = bf && a->gt_feat != nullptr;
   const FeatHeadArgs fh = feat_head_args(c, a->R, C, a->gt_feat); const FeatHead fhb = feat_head_view(w);
   const bool self_counts = (a->mode & OBJNERF_TRAIN_SELF_COUNTS) != 0;
   if (self_counts && K > 1) {        // several objects: the cross-object flags need every object's labels (one small launch)
@@ -2398,26 +1299,22 @@ static int train_step_small(const objnerf_net* net, const objnerf_train_args* a,
   if (feat) {
     // the 512-d head's preparation does not depend on the forward pass: ahead of the fused launch
     const long gst = (long)H * H + H + 1;
-    E.operands = 0;
     // Round 6: ONE launch for the four (the two GEMMs as a group, wb / bb, the rays' beta and |g| and -- with an optimiser
     // attached -- the copy of [W_of | b_of] the head's finish reads, as extra workgroups of the same launch: FeatPrepTask)
     head_snap = a->optim ? E.parts_alloc((size_t)K * C * XC) : nullptr;
-    GemmGroup g0;
-    g0.count = 0;
-    E.group = &g0; E.group16 = false;
-    feat_gram_gemm(E, st, fh, w.gram, gst);
-    feat_rays_gemm(E, st, fh, w.rayin);
+    GroupLaunch g0;
+    feat_gram_gemm(E, st, fh, w.gram, gst, &g0);
+    feat_rays_gemm(E, st, fh, w.rayin, &g0);
     if (E.error) return OBJNERF_EINVAL;
-    if (g0.count == 2) {
-      FeatPrepTask& t = g0.task;
+    if (g0.g.count == 2) {
+      FeatPrepTask& t = g0.g.task;
       t.params = P; t.ps = ps; t.off_w = fh.off_w; t.off_b = fh.off_b; t.C = C; t.Hh = H; t.R = (int)R; t.rin_ld = H + 2;
       t.K = K; t.gt_feat = a->gt_feat; t.rayin = w.rayin; t.gram = w.gram; t.gstride = gst; t.snap = head_snap;
       t.nb_wb = (H + 1 + 7) / 8; t.nb_rs = (int)((R + 31) / 32);
       t.nb_snap = head_snap ? (int)(((long)C * XC + 2047) / 2048) : 0;
       t.blocks = K * (t.nb_wb + t.nb_rs + t.nb_snap);
-      flush_group(E, st, g0);
+      group_launch(st, g0);
     } else {      // (cannot happen for these shapes: the group is dropped, all four launches are redone ungrouped)
-      E.group = nullptr;
       head_snap = nullptr;
       feat_prep_enqueue(E, st, fh, fhb);
     }
@@ -2453,13 +1350,6 @@ static int train_step_small(const objnerf_net* net, const objnerf_train_args* a,
   }
   if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
   if (a->relu_masks) emit_relu_masks(st, c, a->relu_masks, bf ? 1 : 0, bf ? 1 : 0);
-  if (bf) {
-    // bf16 mode: the kernel above stored h1 .. hc (hf, d_hf) and d_hc .. d_h1 as bf16 (objnerf_small_body.h, `hst`); gemm(E, )
-    // recognises 16-bit operands by address and the grouped launch passes them through unconverted
-    E.act16_lo = (const char*)w.h1;
-    E.act16_hi = feat ? (const char*)(w.d_hf + (size_t)K * n * H) : (const char*)(w.hc + w.act_floats);
-    E.grad16_lo = (const char*)w.dA; E.grad16_hi = (const char*)(w.dE + w.act_floats);
-  }
   // ---- the step's reductions, collected: head partials, d B partials, the weight gradients' split-K slices
   RedGroup red;
   red.count = 0;
@@ -2467,18 +1357,11 @@ static int train_step_small(const objnerf_net* net, const objnerf_train_args* a,
                                head_red_item(c, OBJNERF_T_OC_W, OBJNERF_T_OC_B, 3, f.partW, f.rsW, nwg),
                                pe_red_item(c, f.pe_part, nwg)};
   red_emit(st, &red, partials, 3);
-  E.operands = 0;                   // (the grouped launch picks its operand type through group16)
-  E.a_scale = 1.0f;
-  GemmGroup group;
-  group.count = 0;
-  E.group = &group;
-  E.group16 = bf;
-  E.red_group = &red;
-  E.need_parts = true;              // no zero-filled gradient arena here: the deterministic slab form or an error
   // Split-K slices of the grouped launch: its seven GEMMs are ONE 128 x 128 tile each, so `slices` is also the number of
   // workgroups per GEMM.  ~2 rounds of the chip (7 x 37 = 259 workgroups at least), at most ~1024 samples per slice
   // beyond that: every slice writes its partial tile to HBM and the reduction reads it back -- 128 slices at the
   // benchmark's 76 800 background samples were 48 MB each way for 0.4 MB of gradient (reduction 131 us).
+  int max_slices;
   {
     long want = (n + 1023) / 1024;
     if (want < 36) want = 36;
@@ -2487,23 +1370,22 @@ static int train_step_small(const objnerf_net* net, const objnerf_train_args* a,
     const int cu = 256, ng = feat ? 9 : 7;
     long rounds = (want * ng + cu / 2) / cu;
     if (rounds < 1) rounds = 1;
-    E.max_slices = (int)(rounds * cu / ng);
+    max_slices = (int)(rounds * cu / ng);
   }
-  wgrad_chain(E, st, c, feat, false);       // (the feature layer LAST here: the slots of the other seven do not move with it)
+  // (need_parts: no zero-filled gradient arena here -- the deterministic slab form or an error)
+  GroupLaunch group(bf, max_slices, &red);
+  wgrad_chain(E, st, {.group = &group, .need_parts = true}, c, feat, false);      // (the feature layer LAST here: the slots of
+                                                                                  // the other seven do not move with it)
   if (E.parts_failed || E.error) return OBJNERF_EINVAL;
-  flush_group(E, st, group);
+  group_launch(st, group);
   if (feat) {
     // the 512-d head's moments over the RAYS (featg_finish_kernel turns them into d W_of, d b_of after the reduction).
     // A grouped launch of their own: inside the other one their 512-row output made it 5x slower (1.82 against 0.35 ms
     // at the benchmark's background batch -- every GEMM of the group is then launched over four row tiles)
-    GemmGroup g2;
-    g2.count = 0;
-    E.group = &g2; E.group16 = false; E.operands = 0; E.red_group = &red; E.max_slices = 0;
-    feat_moments_enqueue(E, st, fh, fhb);
+    GroupLaunch g2(false, 0, &red);
+    feat_moments_enqueue(E, st, {.group = &g2, .need_parts = true}, fh, fhb);
     if (E.parts_failed || E.error) return OBJNERF_EINVAL;
-    RedGroup* keep = E.red_group;
-    flush_group(E, st, g2);              // (launches whatever was collected; GEMMs the group does not take were launched at once)
-    E.red_group = keep;
+    group_launch(st, g2);                // (launches whatever was collected; GEMMs the group does not take were launched at once)
   }
   red.tail.loss_part = f.loss_part; red.tail.loss_blocks = nwg; red.tail.K = K; red.tail.loss_terms = a->loss_terms;
   red.tail.status = a->status;
@@ -2547,8 +1429,7 @@ static int train_step_small(const objnerf_net* net, const objnerf_train_args* a,
 int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* stream, int* done) {
   objnerf_train_args a_local = *a_in;
   const objnerf_train_args* a = &a_local;
-  GemmEnv E;                                   // this call's GEMM environment (nothing outlives the call)
-  E.operands = (a->mode & OBJNERF_TRAIN_FP16) ? 2 : (a->mode & OBJNERF_TRAIN_BF16) ? 1 : 0;
+  const int operands = (a->mode & OBJNERF_TRAIN_FP16) ? 2 : (a->mode & OBJNERF_TRAIN_BF16) ? 1 : 0;
   const int H = net->hidden, C = net->feat_dim, K = a->K;
   if (H % 32 != 0 || net->n_freqs != 6) return OBJNERF_ENOTSUP;
   const bool feat = a->gt_feat != nullptr;
@@ -2560,8 +1441,6 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
   const bool half_acts = (a->mode & (OBJNERF_TRAIN_FP16 | OBJNERF_TRAIN_BF16)) != 0 && acts16_shape(H, n);
   WS w = carve((char*)a->workspace, H, C, n, (long)a->R, K, feat, half_acts);
   if (a->workspace_bytes < w.bytes) return OBJNERF_EINVAL;
-  E.parts = w.parts; E.parts_cap = w.parts_floats; E.parts_off = 0;
-  E.packb = w.packb; E.packb_entries = w.packb ? K : 0;
   // ---- small batches of the hidden-128 network without the feature loss: ONE forward + loss + backward launch, the
   // grouped weight gradients, one reduction launch (objnerf_small_body.h)
   {
@@ -2575,9 +1454,10 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
     if (H == FS_H && S >= 4 && S <= 64 && (long)K * nwg <= 1536 && !half_acts && K <= 65535 &&
         nwg * 63 <= n * 4 && nwg * (4L * H + 4) <= n * 129 &&
         !(a->mode & OBJNERF_TRAIN_LAYERWISE && K > 8) && (!feat || (C % 4 == 0 && a->R >= 1)))
-      return train_step_small(net, a, st, E, w, off, E.operands == 1, done);
+      return train_step_small(net, a, st, w, off, operands == 1, done);
 #endif
   }
+  GemmStep E = gemm_step(w, operands, K);      // this call's GEMM constants (nothing outlives the call)
   if (a->mode & OBJNERF_TRAIN_SELF_COUNTS) {
     const int rc0 = objnerf_label_counts(K, a->R, a->labels, const_cast<int32_t*>(a->counts), const_cast<int32_t*>(a->flags),
                                          stream);
@@ -2593,13 +1473,21 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
   }
   const float* P = a->params;
   float* G = a->grads;
-  const NetView c = net_view(w, P, G, ps, off, K, n, H);
+  // 16-bit modes at hidden 256 (configs[4]): h1 .. hc and d_hc .. d_h1 live in the operand type -- written by the forward
+  // GEMMs' epilogues, read as panels / masks / weight-gradient operands and by the head kernels (act_ld).  Their buffers
+  // keep the fp32 spacing in the workspace.  hf / d_hf stay fp32.
+  const int act16 = half_acts ? operands : 0;
+  // fp16 operands: every backward GEMM has the back-propagated gradient as its A operand.  Those values are of order
+  // (loss scale) / R per ray times a per-sample weight -- mostly below fp16's smallest normal number (6.1e-5) -- so A is
+  // scaled by ~8 R (a power of two: exact) before rounding and the product scaled back (Gemm::a_scale).
+  const float grad_scale = exp2f(floorf(log2f((float)a->R)) + 3.0f);
+  NetView c = net_view(w, P, G, ps, off, K, n, H);
+  c.act16 = act16 != 0; c.grad_scale = grad_scale;
   const FeatHeadArgs fh = feat_head_args(c, a->R, C, a->gt_feat); const FeatHead fhb = feat_head_view(w);
 
   // helper stream: work that only READS what the main chain produced (or, for the feature preparation below, only
   // parameters and inputs) runs beside it; fork = the side stream waits for everything enqueued on `st` so far
   Side single;                                   // no context: one stream, program order replaces every event
-  for (int i = 0; i < Side::NS; ++i) single.all[i] = st;
   single.s = st;
   Side& sd = a->context ? *(Side*)a->context : single;
   const bool multi = sd.own;
@@ -2631,20 +1519,11 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
   if (rc) return rc;
   dim3 eg((unsigned)((n + 15) / 16), (unsigned)K);      // 16 lanes per sample row
   const size_t head_lds = (size_t)4 * H * sizeof(float);
-  const int small_rt = small_batch_rt(E, H, n, K);
-  // the small-batch kernels come in fp32 and bf16-MFMA form (fp16 mode: fp32 there); their weight-gradient GEMMs stay
-  // fp32 (one grouped launch)
-  const bool small_bf = small_rt && E.operands == 1;
-  if (small_rt) E.operands = 0;
-  // 16-bit modes at hidden 256 (configs[4]): h1 .. hc live in the operand type -- written by the forward GEMMs'
-  // epilogues, read as panels / masks / weight-gradient operands and by the head kernels (act_ld).  Their buffers keep
-  // the fp32 spacing in the workspace; gemm(E, ) recognises them by address.
-  const int act16 = half_acts ? E.operands : 0;
+  const int small_rt = small_batch_rt(operands, H, n, K);
+  // the small-batch kernels come in fp32 and bf16-MFMA form (fp16 mode: fp32 there); the GEMMs behind them -- the
+  // feature head's moments, the grouped weight gradients -- are fp32 whatever the mode (WgradHow::fp32, the group's type)
+  const bool small_bf = small_rt && operands == 1;
   if (act16 && !panel_ok(E, (int)n, H, H + OBJ_E1, 1, 1, false, K)) return OBJNERF_EINVAL;      // (cannot happen: same conditions)
-  if (act16) {
-    E.act16_lo = (const char*)w.h1; E.act16_hi = (const char*)(w.hc + w.act_floats);
-    E.grad16_lo = (const char*)w.dA; E.grad16_hi = (const char*)(w.dE + w.act_floats);
-  }
   if (small_rt) {
     FwdSmall f;
     f.n = n; f.feat = feat ? 1 : 0; f.params = P; f.ps = ps; f.emb = w.emb;
@@ -2675,11 +1554,6 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
   // Weight-gradient GEMMs only READ the d-output / activation buffers and write the gradient arena, so they run on a
   // side stream beside the dgrad chain (each of these GEMMs alone leaves most of the chip idle).  Every d_h has its own
   // buffer: nothing a side-stream GEMM reads is overwritten before the join at the end.
-  // fp16 operands: every backward GEMM has the back-propagated gradient as its A operand.  Those values are of order
-  // (loss scale) / R per ray times a per-sample weight -- mostly below fp16's smallest normal number (6.1e-5) -- so A is
-  // scaled by ~8 R (a power of two: exact) before rounding and the product scaled back (Gemm::a_scale).
-  const float grad_scale = exp2f(floorf(log2f((float)a->R)) + 3.0f);
-  E.a_scale = grad_scale;
   const bool fold_a = !feat && !small_rt;      // (layer_dgrad's fold_dhead form of the colour layer)
   hipLaunchKernelGGL(heads_bwd_kernel, eg, dim3(256), head_lds, st, H, n, w.hc, w.color, w.d_alpha, w.d_color, P, ps,
                      (int)off[OBJNERF_T_ALPHA_W], (int)off[OBJNERF_T_OC_W], w.dhead, c.d_hc, fold_a ? nullptr : c.d_h4, act16,
@@ -2688,10 +1562,10 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
   // (every bias gradient rides on its layer's weight-gradient GEMM: row sums of the d-output operand tile)
   fork();
   if (H > 256) {
-    wgrad(E, ss, K, 1, H, n, w.dhead, 1, 4, n * 4, w.h4, H, 1, n * H, G + off[OBJNERF_T_ALPHA_W], H, ps,
-          G + off[OBJNERF_T_ALPHA_B]);
-    wgrad(E, ss, K, 3, H, n, w.dhead + 1, 1, 4, n * 4, w.hc, H, 1, n * H, G + off[OBJNERF_T_OC_W], H, ps,
-          G + off[OBJNERF_T_OC_B]);
+    wgrad(E, ss, {}, K, 1, H, n, op_cols(w.dhead, 4, n * 4), op_rows(w.h4, H, n * H, c.act16),
+          op_rows(G + off[OBJNERF_T_ALPHA_W], H, ps), G + off[OBJNERF_T_ALPHA_B], grad_scale);
+    wgrad(E, ss, {}, K, 3, H, n, op_cols(w.dhead + 1, 4, n * 4), op_rows(w.hc, H, n * H, c.act16),
+          op_rows(G + off[OBJNERF_T_OC_W], H, ps), G + off[OBJNERF_T_OC_B], grad_scale);
   } else {
     // 64 samples per block (32 iterations of a 2-row pass at H = 128): the loop is a chain of load latencies, so the
     // reduction wants many short blocks (512 samples per block: 183 us for the background batch; now ~25 us)
@@ -2720,9 +1594,7 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
     hipLaunchKernelGGL(featg_scale_kernel, dim3((unsigned)((nr * XC + 255) / 256)), dim3(256), 0, ss, nr, H, w.rayfeat, w.X1,
                        w.X2);
     (void)hipMemsetAsync(w.Tm, 0, ((size_t)K * C * XC + (size_t)K * XC * XC) * 4, ss);
-    E.a_scale = 1.0f;                       // (targets and moments of the feature head: not gradients)
-    feat_moments_enqueue(E, ss, fh, fhb);
-    E.a_scale = grad_scale;
+    feat_moments_enqueue(E, ss, {.fp32 = small_rt != 0}, fh, fhb);
     feat_finish_enqueue(ss, fh, fhb, G);
   }
   if (small_rt) {
@@ -2735,13 +1607,10 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
     set_weight_offsets(b, off);
     launch_small_rt(st, b, K, small_bf, small_rt);
     fork();
-    GemmGroup group;
-    group.count = 0;
-    E.group = &group;
-    E.group16 = small_bf;             // bf16 mode: the weight gradients take bf16 operands like every other GEMM of the mode
-    E.red_group = &step_red;
-    wgrad_chain(E, ss, c, feat, true);
-    flush_group(E, ss, group);
+    GroupLaunch group(small_bf, 0, &step_red);      // bf16 mode: the weight gradients take bf16 operands like every other
+                                                    // GEMM of the mode
+    wgrad_chain(E, ss, {.group = &group}, c, feat, true);
+    group_launch(ss, group);
   } else {
     backward_chain(E, st, ss, c, feat, fold_a ? w.dhead : nullptr, fork);
   }
@@ -2760,8 +1629,8 @@ int train_step(const objnerf_net* net, const objnerf_train_args* a_in, void* str
                        G + off[OBJNERF_T_PE_B], ps);
   }
   if (multi) {   // join: the caller's stream continues after the weight gradients
-    (void)hipEventRecord(sd.done_all[0], ss);
-    (void)hipStreamWaitEvent(st, sd.done_all[0], 0);
+    (void)hipEventRecord(sd.done_all, ss);
+    (void)hipStreamWaitEvent(st, sd.done_all, 0);
   }
   launch_reductions(st, step_red);
   if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
@@ -2782,7 +1651,7 @@ int eval_points(const objnerf_net* net, int K, long N, const float* params, long
   const int H = net->hidden, C = net->feat_dim;
   if (H % 32 != 0 || net->n_freqs != 6) return OBJNERF_ENOTSUP;
   if (!workspace || workspace_bytes < eval_workspace_bytes(net, K, N) - 256) return OBJNERF_EINVAL;
-  GemmEnv E;                                   // fp32
+  GemmStep E;                                  // fp32, no scratch
   int64_t off[OBJNERF_N_TENSORS + 1];
   objnerf_param_layout(net, off);
   hipStream_t st = (hipStream_t)stream;
@@ -2797,14 +1666,15 @@ int eval_points(const objnerf_net* net, int K, long N, const float* params, long
     if (rc) return rc;
     emb = emb_ws;
   }
-  NetView c = {};
+  NetView c = {};                              // (fp32 storage)
+  c.grad_scale = 1.0f;
   c.P = params; c.ps = p_stride; c.off = off; c.K = K; c.n = N; c.H = H; c.emb = emb;
   c.h1 = bA; c.h2 = bB; c.h3 = bA; c.h4 = bB; c.hc = bA;
   float* hf = (out_hfeat || out_clip) ? (out_hfeat ? out_hfeat : bC) : nullptr;
   forward_chain(E, st, c, out_alpha, out_color, hf, 0);
   if (out_clip)
-    gemm(E, st, K, N, C, H, hf, H, 1, N * H, params + off[OBJNERF_T_OF_W], 1, H, p_stride, out_clip, C, 1, N * C, false,
-         params + off[OBJNERF_T_OF_B], p_stride, false);
+    gemm(E, st, K, N, C, H, op_rows(hf, H, N * H), op_cols(params + off[OBJNERF_T_OF_W], H, p_stride),
+         op_rows(out_clip, C, N * C), {.bias = params + off[OBJNERF_T_OF_B], .bsbias = p_stride});
   if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
   return OBJNERF_OK;
 }
@@ -2835,9 +1705,9 @@ int mlp_backward(const objnerf_net* net, int K, long N, const float* params, lon
   int64_t off[OBJNERF_N_TENSORS + 1];
   objnerf_param_layout(net, off);
   hipStream_t st = (hipStream_t)stream;
-  GemmEnv E;
   WS w = carve((char*)workspace, H, C, n, 1, K, feat);
-  E.parts = w.parts; E.parts_cap = w.parts_floats; E.parts_off = 0;
+  GemmStep E;                         // fp32; no packed-B scratch
+  E.parts = w.parts; E.parts_cap = w.parts_floats;
   const float* P = params;
   float* G = grads;
   NetView c = net_view(w, P, G, ps, off, K, n, H);
@@ -2850,16 +1720,19 @@ int mlp_backward(const objnerf_net* net, int K, long N, const float* params, lon
   hipLaunchKernelGGL(heads_bwd_kernel, dim3((unsigned)((n + 15) / 16), (unsigned)K), dim3(256), (size_t)4 * H * sizeof(float),
                      st, H, n, w.hc, w.color, d_alpha, d_color, P, ps, (int)off[OBJNERF_T_ALPHA_W], (int)off[OBJNERF_T_OC_W],
                      w.dhead, c.d_hc, c.d_h4, 0, 1.0f);
-  wgrad(E, st, K, 1, H, n, w.dhead, 1, 4, n * 4, w.h4, H, 1, nH, G + off[OBJNERF_T_ALPHA_W], H, ps, G + off[OBJNERF_T_ALPHA_B]);
-  wgrad(E, st, K, 3, H, n, w.dhead + 1, 1, 4, n * 4, w.hc, H, 1, nH, G + off[OBJNERF_T_OC_W], H, ps, G + off[OBJNERF_T_OC_B]);
+  wgrad(E, st, {}, K, 1, H, n, op_cols(w.dhead, 4, n * 4), op_rows(w.h4, H, nH), op_rows(G + off[OBJNERF_T_ALPHA_W], H, ps),
+        G + off[OBJNERF_T_ALPHA_B]);
+  wgrad(E, st, {}, K, 3, H, n, op_cols(w.dhead + 1, 4, n * 4), op_rows(w.hc, H, nH), op_rows(G + off[OBJNERF_T_OC_W], H, ps),
+        G + off[OBJNERF_T_OC_B]);
   if (feat) {
     // 512-d head: d W_of = d_clip^T hf, d b_of = column sums, d_hf = (d_clip W_of) o [hf > 0]
-    GemmEnv Eh;                       // (its slabs have a region of their own behind the carve)
+    GemmStep Eh;                      // (its slabs have a region of their own behind the carve)
     Eh.parts = (float*)((char*)workspace + w.bytes);
     Eh.parts_cap = (size_t)K * wgrad_slices(K, C, H, n) * ((size_t)C * H + C) + 256;
-    wgrad(Eh, st, K, C, H, n, d_clip, 1, C, n * C, w.hf, H, 1, nH, G + off[OBJNERF_T_OF_W], H, ps, G + off[OBJNERF_T_OF_B]);
-    gemm(E, st, K, n, H, C, d_clip, C, 1, n * C, P + off[OBJNERF_T_OF_W], H, 1, ps, w.d_hf, H, 1, nH, false, nullptr, 0, false,
-         w.hf, H, 1, nH);
+    wgrad(Eh, st, {}, K, C, H, n, op_cols(d_clip, C, n * C), op_rows(w.hf, H, nH), op_rows(G + off[OBJNERF_T_OF_W], H, ps),
+          G + off[OBJNERF_T_OF_B]);
+    gemm(E, st, K, n, H, C, op_rows(d_clip, C, n * C), op_rows(P + off[OBJNERF_T_OF_W], H, ps), op_rows(w.d_hf, H, nH),
+         {.mask = op_rows(w.hf, H, nH)});
   }
   backward_chain(E, st, st, c, feat, nullptr, [] {});
   if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
@@ -2907,54 +1780,47 @@ FeatHead feat_head_carve(char* base, int K, int R, int Hh, int C) {
   f.parts = take(f.parts_floats);
   return f;
 }
-int feat_head_prep(void* stream, int K, int R, int Hh, int C, const float* params, long p_stride, long off_w, long off_b,
-                   const float* gt_feat, const FeatHead& f, int operands) {
-  GemmEnv E;
+int feat_head_prep(void* stream, const FeatHeadArgs& h, const FeatHead& f, int operands) {
+  GemmStep E;
   E.operands = operands;
-  feat_prep_enqueue(E, (hipStream_t)stream, FeatHeadArgs{K, R, Hh, C, params, p_stride, (int)off_w, (int)off_b, gt_feat}, f);
+  feat_prep_enqueue(E, (hipStream_t)stream, h, f);
   if (E.error) return OBJNERF_EINVAL;
   return hipGetLastError() == hipSuccess ? OBJNERF_OK : OBJNERF_ELAUNCH;
 }
-int feat_head_grads(void* stream, int K, int R, int Hh, int C, const float* params, long p_stride, long off_w, long off_b,
-                    const float* gt_feat, const FeatHead& f, float* grads, int operands) {
-  GemmEnv E;
+int feat_head_grads(void* stream, const FeatHeadArgs& h, const FeatHead& f, float* grads, int operands) {
+  GemmStep E;
   E.operands = operands;
-  E.parts = f.parts; E.parts_cap = f.parts_floats; E.parts_off = 0;
-  E.need_parts = true;
-  const FeatHeadArgs h = {K, R, Hh, C, params, p_stride, (int)off_w, (int)off_b, gt_feat};
-  feat_moments_enqueue(E, (hipStream_t)stream, h, f);
+  E.parts = f.parts; E.parts_cap = f.parts_floats;
+  feat_moments_enqueue(E, (hipStream_t)stream, {.need_parts = true}, h, f);
   if (E.parts_failed || E.error) return OBJNERF_EINVAL;
   feat_finish_enqueue((hipStream_t)stream, h, f, grads);
   return hipGetLastError() == hipSuccess ? OBJNERF_OK : OBJNERF_ELAUNCH;
 }
 
 // G = W_of^T W_of, wb = W_of^T b_of, bb = b_of . b_of of K objects: gram[k][Hh * Hh | Hh | 1], batch stride gstride
-void feat_gram(void* stream, int K, const float* params, long p_stride, int off_w, int off_b, int C, int Hh, float* gram,
-               long gstride) {
-  GemmEnv E;
-  feat_gram_enqueue(E, (hipStream_t)stream, FeatHeadArgs{K, 0, Hh, C, params, p_stride, off_w, off_b, nullptr}, gram, gstride);
+void feat_gram(void* stream, const FeatHeadArgs& h, float* gram, long gstride) {
+  GemmStep E;
+  feat_gram_enqueue(E, (hipStream_t)stream, h, gram, gstride);
 }
 // out[k][m][:] = W_of[k] hfeat[k][m] + b_of[k] * weight[k][m]   (model.py:101 applied after compositing; weight NULL = 1)
-void feature_head(void* stream, int K, long n, int Hh, int C, const float* params, long p_stride, long off_w, long off_b,
-                  const float* hfeat, const float* weight, float* out) {
-  GemmEnv E;
-  E.biasrow = weight; E.bsbr = n;
-  gemm(E, (hipStream_t)stream, K, (int)n, C, Hh, hfeat, Hh, 1, n * Hh, params + off_w, 1, Hh, p_stride, out, C, 1, n * C, false,
-       params + off_b, p_stride, false);
+void feature_head(void* stream, const FeatHeadArgs& h, long n, const float* hfeat, const float* weight, float* out) {
+  GemmStep E;
+  gemm(E, (hipStream_t)stream, h.K, (int)n, h.C, h.Hh, op_rows(hfeat, h.Hh, n * h.Hh), op_cols(h.P + h.off_w, h.Hh, h.ps),
+       op_rows(out, h.C, n * h.C), {.bias = h.P + h.off_b, .bsbias = h.ps, .biasrow = weight, .bsbr = n});
 }
-void gemm_f32(void* stream, int batch, int M, int N, int Kd, const float* A, long sam, long sak, long bsa, const float* B,
-              long sbk, long sbn, long bsb, float* C, long scm, long scn, long bsc, bool accumulate) {
-  GemmEnv E;
-  gemm(E, (hipStream_t)stream, batch, M, N, Kd, A, sam, sak, bsa, B, sbk, sbn, bsb, C, scm, scn, bsc, accumulate);
+void gemm_f32(void* stream, int batch, int M, int N, int Kd, const Operand& A, const Operand& B, const Operand& C,
+              bool accumulate) {
+  GemmStep E;
+  gemm(E, (hipStream_t)stream, batch, M, N, Kd, A, B, C, {.accumulate = accumulate});
 }
 size_t wgrad_parts_floats(int batch, int M, int N, long n) {
   return (size_t)batch * wgrad_slices(batch, M, N, n) * M * N + 64;
 }
-void wgrad_f32(void* stream, int batch, int M, int N, long n, const float* A, long sam, long sak, long bsa, const float* B,
-               long sbk, long sbn, long bsb, float* C, long scm, long bsc, float* parts, size_t parts_floats) {
-  GemmEnv E;
-  E.parts = parts; E.parts_cap = parts ? parts_floats : 0; E.parts_off = 0;
-  wgrad(E, (hipStream_t)stream, batch, M, N, n, A, sam, sak, bsa, B, sbk, sbn, bsb, C, scm, bsc);
+void wgrad_f32(void* stream, int batch, int M, int N, long n, const Operand& A, const Operand& B, const Operand& C,
+               float* parts, size_t parts_floats) {
+  GemmStep E;
+  E.parts = parts; E.parts_cap = parts ? parts_floats : 0;
+  wgrad(E, (hipStream_t)stream, {}, batch, M, N, n, A, B, C);
 }
 
 }  // namespace objgen

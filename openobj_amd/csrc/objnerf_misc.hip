@@ -951,8 +951,8 @@ int objnerf_feature_head(const objnerf_net* net, int32_t K, int64_t n, const flo
   int64_t offs[OBJNERF_N_TENSORS + 1];
   if (objnerf_param_layout(net, offs) < 0) return OBJNERF_EINVAL;
   // a batched GEMM [n x H] [H x C] with the bias scaled per row (objnerf_generic.hip)
-  objgen::feature_head(stream, K, (long)n, net->hidden, net->feat_dim, params, (long)p_stride, (long)offs[OBJNERF_T_OF_W],
-                       (long)offs[OBJNERF_T_OF_B], hfeat, weight, out);
+  objgen::feature_head(stream, {K, 0, net->hidden, net->feat_dim, params, (long)p_stride, (int)offs[OBJNERF_T_OF_W],
+                                (int)offs[OBJNERF_T_OF_B], nullptr}, (long)n, hfeat, weight, out);
   CHECK_LAUNCH();
   return OBJNERF_OK;
 }

@@ -817,7 +817,7 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
   int fin_G = 0;
   if (feat) {
     const bool pre_one = C <= FEAT_PRE_MAXC && C % 16 == 0;
-    if (!pre_one) objgen::feat_gram(stream, a->K, a->params, (long)a->p_stride, d.L.of_w, d.L.of_b, C, 32, ws.gram, GRAM);
+    if (!pre_one) objgen::feat_gram(stream, {a->K, 0, 32, C, a->params, (long)a->p_stride, d.L.of_w, d.L.of_b, nullptr}, ws.gram, GRAM);
     // u = gt_feat W_of  ([R x C] [C x 32] per object) on the batched MFMA GEMM; beta, |g| beside it
     if (pre_one) {
       // u, beta, |g| in one pass over gt_feat (feat_pre_kernel)
@@ -833,8 +833,9 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
                          d.L.of_w, d.L.of_b, C, a->R, a->gt_feat, ws.rayin, ws.gram, ws.head_snap, a->labels,
                          counts_in_pre ? const_cast<int32_t*>(a->counts) : nullptr);
     } else {
-      objgen::gemm_f32(stream, a->K, a->R, 32, C, a->gt_feat, C, 1, (long)a->R * C, a->params + d.L.of_w, 32, 1,
-                       (long)a->p_stride, ws.rayin, RAYIN, 1, (long)a->R * RAYIN, false);
+      objgen::gemm_f32(stream, a->K, a->R, 32, C, objgen::op_rows(a->gt_feat, C, (long)a->R * C),
+                       objgen::op_rows(a->params + d.L.of_w, 32, (long)a->p_stride),
+                       objgen::op_rows(ws.rayin, RAYIN, (long)a->R * RAYIN), false);
       hipLaunchKernelGGL(feat_rowstats_kernel, dim3((a->R + 15) / 16, a->K), dim3(256), 0, st, a->params,
                          (long)a->p_stride, d.L.of_b, C, a->R, a->gt_feat, ws.rayin);
     }
@@ -862,10 +863,12 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
     } else {
       hipLaunchKernelGGL(feat_scale_kernel, dim3((unsigned)((nr * XCOLS + 255) / 256)), dim3(256), 0, st, nr, ws.rayfeat, ws.X1, ws.X2);
       (void)hipMemsetAsync(ws.Tm, 0, ((size_t)a->K * C * XCOLS + (size_t)a->K * XCOLS * XCOLS) * 4, st);
-      objgen::wgrad_f32(stream, a->K, C, XCOLS, a->R, a->gt_feat, 1, C, (long)a->R * C, ws.X1, XCOLS, 1, (long)a->R * XCOLS, ws.Tm,
-                        XCOLS, (long)C * XCOLS, ws.parts_t, objgen::wgrad_parts_floats(a->K, C, XCOLS, a->R));
-      objgen::wgrad_f32(stream, a->K, XCOLS, XCOLS, a->R, ws.X2, 1, XCOLS, (long)a->R * XCOLS, ws.rayfeat, RAYFEAT, 1,
-                        (long)a->R * RAYFEAT, ws.mom, XCOLS, (long)XCOLS * XCOLS, ws.parts_m,
+      objgen::wgrad_f32(stream, a->K, C, XCOLS, a->R, objgen::op_cols(a->gt_feat, C, (long)a->R * C),
+                        objgen::op_rows(ws.X1, XCOLS, (long)a->R * XCOLS), objgen::op_rows(ws.Tm, XCOLS, (long)C * XCOLS),
+                        ws.parts_t, objgen::wgrad_parts_floats(a->K, C, XCOLS, a->R));
+      objgen::wgrad_f32(stream, a->K, XCOLS, XCOLS, a->R, objgen::op_cols(ws.X2, XCOLS, (long)a->R * XCOLS),
+                        objgen::op_rows(ws.rayfeat, RAYFEAT, (long)a->R * RAYFEAT),
+                        objgen::op_rows(ws.mom, XCOLS, (long)XCOLS * XCOLS), ws.parts_m,
                         objgen::wgrad_parts_floats(a->K, XCOLS, XCOLS, a->R));
     }
     if (one_pass && pre_one) {      // finalize_kernel forms the head's gradient itself (round 6: one launch fewer)

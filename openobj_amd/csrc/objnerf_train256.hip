@@ -2206,8 +2206,9 @@ static int run(const objnerf_net* net, const objnerf_train_args* a, hipStream_t 
     // the hoisted 512-d head: per object G = W_of^T W_of (+ wb, bb), per ray u = W_of^T g, beta, |g| -- ahead
     // of kernel A, with the operand type of the mode (16-bit GEMM operands, like the layer-wise path)
     fh = objgen::feat_head_carve(base + p.off_feat, K, a->R, HID, C);
-    const int rc = objgen::feat_head_prep(st, K, a->R, HID, C, a->params, (long)a->p_stride, off[OBJNERF_T_OF_W],
-                                          off[OBJNERF_T_OF_B], a->gt_feat, fh, (a->mode & OBJNERF_TRAIN_FP16) ? 2 : 1);
+    const int rc = objgen::feat_head_prep(st, {K, a->R, HID, C, a->params, (long)a->p_stride, (int)off[OBJNERF_T_OF_W],
+                                               (int)off[OBJNERF_T_OF_B], a->gt_feat}, fh,
+                                          (a->mode & OBJNERF_TRAIN_FP16) ? 2 : 1);
     if (rc) return rc;
     const long tot = (long)K * GIMG_PIECES * 64;
     hipLaunchKernelGGL((packg256_kernel<OT>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, K, fh.gram,
@@ -2264,8 +2265,8 @@ static int run(const objnerf_net* net, const objnerf_train_args* a, hipStream_t 
   hipLaunchKernelGGL(finalize256_kernel, dim3((unsigned)((fn.P + 255) / 256), (unsigned)K), dim3(256), 0, st, fn);
   if (FEAT) {
     // d W_of, d b_of from the rays' moments (two GEMMs over the rays + featg_finish_kernel)
-    const int rc = objgen::feat_head_grads(st, K, a->R, HID, C, a->params, (long)a->p_stride, off[OBJNERF_T_OF_W],
-                                           off[OBJNERF_T_OF_B], a->gt_feat, fh, a->grads,
+    const int rc = objgen::feat_head_grads(st, {K, a->R, HID, C, a->params, (long)a->p_stride, (int)off[OBJNERF_T_OF_W],
+                                                (int)off[OBJNERF_T_OF_B], a->gt_feat}, fh, a->grads,
                                            (a->mode & OBJNERF_TRAIN_FP16) ? 2 : 1);
     if (rc) return rc;
   }

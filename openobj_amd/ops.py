@@ -418,7 +418,7 @@ def precision_bits(p) -> int:
 
 
 class StreamContext:
-    """objnerf_context: the helper streams + events the layer-wise path forks onto.  Created on the current device;
+    """objnerf_context: the helper stream + events the layer-wise path forks onto.  Created on the current device;
     freed with the object (after a device synchronisation, so no step using it is in flight)."""
 
     def __init__(self, device):

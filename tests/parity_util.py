@@ -159,13 +159,13 @@ def sf_rays_per_wg(S, feat):
 
 def small128_route(K, R, S, feat, mode="bf16", H=128, C=512, layerwise=False):
     """Which kernels objgen::train_step runs for a hidden-H step of K objects x R rays x S samples.  Returns
-    ("A", RT, rpw, nwg): the one-launch iteration train_small_kernel<RT, mode == bf16, feat> (objnerf_generic.hip:2622-2634,
-    RT from train_step_small, :2502-2508); ("B", RT, 0, workgroups per object): mlp_fwd_small_kernel / mlp_bwd_small_kernel<RT>
-    (small_batch_rt, :1598-1611; launch grid :1565 / :1578); ("gemm", 0, 0, 0): the layer-wise GEMM chain.  In bf16 mode the
-    kernels are the BF = true instantiations on both routes (:2633 E.operands == 1; :2692 small_bf); in fp16 mode the
+    ("A", RT, rpw, nwg): the one-launch iteration train_small_kernel<RT, mode == bf16, feat> (objnerf_generic.hip, the
+    dispatch at the top of train_step; RT from train_step_small); ("B", RT, 0, workgroups per object): mlp_fwd_small_kernel / mlp_bwd_small_kernel<RT>
+    (small_batch_rt; launch grid: launch_small); ("gemm", 0, 0, 0): the layer-wise GEMM chain.  In bf16 mode the
+    kernels are the BF = true instantiations on both routes (train_step: operands == 1; small_bf); in fp16 mode the
     fp32 ones."""
     n = R * S
-    half_acts = mode in ("bf16", "fp16") and H == 256 and n >= 4096          # acts16_shape, :2075 / :2615
+    half_acts = mode in ("bf16", "fp16") and H == 256 and n >= 4096          # acts16_shape, half_acts in train_step
     if H == 128 and 4 <= S <= 64:
         rpw = sf_rays_per_wg(S, feat)
         nwg = (R + rpw - 1) // rpw

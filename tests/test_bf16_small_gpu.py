@@ -9,22 +9,23 @@ Two routes (objnerf_generic.hip, objgen::train_step; restated in parity_util.sma
      gemm_group16_kernel.
 
 Where the two routes round (the reading behind the specification flags below):
-  * mma_f / mma (objnerf_small_body.h:252-266, objnerf_generic.hip:1156-1169): BOTH operands -- the fp32 weight image and
+  * mma_f / mma (objnerf_small_body.h:252-266; objnerf_generic.hip, mlp_fwd_small_kernel): BOTH operands -- the fp32 weight image and
     the fp32 activations / embedding in LDS -- are converted by cvt_bf16x8 as the MFMA reads them.  The LDS copies that
     every other consumer reads stay fp32: rounded at the GEMM, not in storage -> act16 = False.
-  * the heads (objnerf_small_body.h:397-411, objnerf_generic.hip:1275-1291): fp32 dot products of the UNROUNDED h4 / hc
+  * the heads (objnerf_small_body.h:397-411; objnerf_generic.hip, the end of mlp_fwd_small_kernel): fp32 dot products of the UNROUNDED h4 / hc
     with fp32 head weights -> round_head_weights = False.  Their weight gradients are fp32 sums over the same LDS rows
-    (head_partials, objnerf_small_body.h:481-495) or head_wgrad_kernel on fp32 h4 / hc (objnerf_generic.hip:2760; act16 = 0
-    because acts16_shape needs hidden 256) -> round_head_grads = False.  heads_bwd_kernel (route B, :2739) likewise reads
+    (head_partials, objnerf_small_body.h:481-495) or head_wgrad_kernel on fp32 h4 / hc (objnerf_generic.hip, train_step; act16 = 0
+    because acts16_shape needs hidden 256) -> round_head_grads = False.  heads_bwd_kernel (route B, train_step) likewise reads
     fp32 hc / colour and writes fp32 d_hc.
-  * mma_b / mma of the backward (objnerf_small_body.h:635-651, objnerf_generic.hip:1382-1401): the weight image is rounded
+  * mma_b / mma of the backward (objnerf_small_body.h:635-651; objnerf_generic.hip, mlp_bwd_small_kernel): the weight image is rounded
     when staged (put_wb / put_w), the fp32 d_h in LDS by cvt_bf16x8 at the MFMA: the back-propagated gradient is rounded
     as the next GEMM's operand, which is what the specification's activation rounding does on the way back.
   * the weight gradients: route A's `hst` (objnerf_small_body.h:295-297) stores h and d_h rounded for gemm_group16_kernel,
-    which on route B rounds the same fp32 values itself (group16 = small_bf, objnerf_generic.hip:2796): operands of the
+    which on route B rounds the same fp32 values itself (GroupLaunch group(small_bf, ..), objnerf_generic.hip, train_step): operands of the
     weight-gradient GEMMs rounded, as the specification's autograd of a rounded-operand matmul has them.
-  * the feature head.  Route A prepares the hoisted head with E.operands = 0 (objnerf_generic.hip:2456):
-    fp32, nothing rounded.  Route B calls feat_prep_enqueue BEFORE it clears E.operands (:2680 against :2693): the Gram
+  * the feature head.  Route A prepares the hoisted head on an fp32 GemmStep (objnerf_generic.hip,
+    train_step_small: gemm_step(w, 0, K)): fp32, nothing rounded.  Route B calls feat_prep_enqueue on the step's own
+    operand precision (train_step; only the GEMMs BEHIND the small-batch kernels ask for fp32, WgradHow::fp32): the Gram
     matrix and u = W_of^T g are bf16-operand GEMMs, W_of enters rounded while the density / colour heads do not -- a point
     the specification could not express; mlp_forward_stacked_16(round_feat_head=True) states it.
 """
@@ -294,8 +295,8 @@ def test_bf16_small_batch_step_does_not_depend_on_object_order(dev, case):
 @pytest.mark.parametrize("case", FP16_CASES, ids=_id)
 def test_fp16_mode_runs_the_fp32_small_batch_kernels(dev, case):
     """What two skips of test_16bit_spec_gpu.py say: on route A the fp16 mode rounds nothing.  objgen::train_step hands
-    train_step_small `E.operands == 1` (objnerf_generic.hip:2633) -- false for fp16 -- and train_step_small clears
-    E.operands before its GEMMs (:2456, :2525), so the launches are those of an fp32 step: bit-equal gradients and loss
+    train_step_small `operands == 1` (objnerf_generic.hip, train_step) -- false for fp16 -- and train_step_small runs
+    its GEMMs on an fp32 GemmStep (gemm_step(w, 0, K)), so the launches are those of an fp32 step: bit-equal gradients and loss
     terms to the fp32-mode step on a layerwise=True workspace (the sizing an fp16 workspace gets)."""
     (K, R, n1, n2), feat = case
     arena, _, b = _setup(dev, K, R, n1, n2, feat)
