@@ -344,7 +344,12 @@ int objnerf_label_counts(int32_t K, int32_t R, const uint8_t* labels, int32_t* c
  * Outputs: grads [K][P_stride] (same layout as params; entries of tensors without gradient are
  * left untouched), loss_terms [K][4], status [1] (bits as objnerf_step_batch_loss: 0 = a term above 1e5, 1 = a term
  * that is not finite; every path of this entry point -- fused hidden 32, one-launch hidden 128, layer-wise, fused
- * hidden 256 -- writes both).
+ * hidden 256 -- writes both).  The fused fp32 hidden-32 kernel without the feature loss does not evaluate rays the loss
+ * masks out (label 2: nothing of the ray; label 0: not its colour): with finite inputs that changes no bit of any
+ * output; a value that is NOT finite and confined to a label-2 ray (NaN points, z, gt_depth or gt_rgb) need no
+ * longer reach a loss term -- it does not where the ray's samples fill whole waves and its compositing pass holds only
+ * label-2 rays, as at 64 samples per ray -- so bit 1 may stay clear for it there, while the other paths, which multiply
+ * it by the zero mask, set it.
  * workspace: objnerf_train_workspace_bytes() bytes, 256-byte aligned (its with_feat argument: bit 0 = feature
  * loss, bit 1 = size for OBJNERF_TRAIN_LAYERWISE, bit 2 = size for the 16-bit modes only -- at hidden 256 they keep
  * the five activation and five gradient buffers in the operand type, a third less; a workspace sized without bit 2 serves every mode).

@@ -396,8 +396,26 @@ __device__ __forceinline__ void prio_layer(const int layer) {
 __device__ __forceinline__ void prio_layer(const int) {}
 #endif
 
+// embed32 without octaves 4, 5 (e.x2 is left alone), for a caller that does not evaluate the colour layer (the training
+// kernel, for a wave whose rays the colour loss masks out).  e.x1 gets the same values as from embed32, entry for entry:
+// octaves 0..3 never depend on a higher one.
+__device__ __forceinline__ void embed32_x1(Emb32& e, const Pe32& pe, const int g) {
+  if ((OBJ32_ABL) & 32) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) e.x1[i] = f32x4{pe.vh[i], pe.vl[i], pe.vh[i], pe.vl[i]};
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    float s[6], c[6];
+    pe32_octaves<0, 3, false>(pe.vh[i], pe.vl[i], s, c);
+    e.x1[i] = pe32_x1_tile(pe, i, g, s);
+  }
+}
+
+// mlp32_trunk in two pieces: everything up to h4 (all the density head needs), then the colour (and feature) layer.
 template <bool FEAT>
-__device__ __forceinline__ void mlp32_trunk(const float* wf, const float* sv, const int g, const Emb32& e, Acts& a) {
+__device__ __forceinline__ void mlp32_trunk_h4(const float* wf, const float* sv, const int g, const Emb32& e, Acts& a) {
   T32 acc = zero32();
   prio_layer(1);
 #pragma unroll
@@ -423,8 +441,11 @@ __device__ __forceinline__ void mlp32_trunk(const float* wf, const float* sv, co
     for (int r = 0; r < 4; ++r) acc.t[tt][r] = sv[SV_BM2 + 16 * tt + 4 * g + r];
   mma_f32(acc, wf, R_M2, a.h3);
   a.h4 = relu32(acc);
+}
+template <bool FEAT>
+__device__ __forceinline__ void mlp32_trunk_colour(const float* wf, const int g, const Emb32& e, Acts& a) {
   prio_layer(5);
-  acc = zero32();
+  T32 acc = zero32();
   mma_f32(acc, wf, R_CL, a.h4);
 #pragma unroll
   for (int T = 0; T < 3; ++T) mma_f16(acc, wf, R_CL + 32 + 16 * T, e.x2[T]);
@@ -437,6 +458,11 @@ __device__ __forceinline__ void mlp32_trunk(const float* wf, const float* sv, co
     a.hf = relu32(acc);
   }
   prio_layer(-1);
+}
+template <bool FEAT>
+__device__ __forceinline__ void mlp32_trunk(const float* wf, const float* sv, const int g, const Emb32& e, Acts& a) {
+  mlp32_trunk_h4<FEAT>(wf, sv, g, e, a);
+  mlp32_trunk_colour<FEAT>(wf, g, e, a);
 }
 // the four head pre-activations of the lane's sample, summed over the lane groups (every lane ends with all four)
 __device__ __forceinline__ void mlp32_head_sums(const float* sv, const int g, const Acts& a, float& sa, float& s0, float& s1,
@@ -462,6 +488,20 @@ __device__ __forceinline__ float mlp32_forward(const float* wf, const float* sv,
   const float mine = (g == 0) ? sa : ((g == 1) ? s0 : ((g == 2) ? s1 : s2));
   const float z = mine + sv[SV_HB + g];
   return (g == 0) ? z * 10.0f : sigmoid_acc(z);
+}
+// mlp32_forward without the colour layer, for samples whose colour enters no result (the training kernel, rays the colour
+// loss masks out): e.x2 is not read, a.hc is all zero, group 0 gets the same 10 * raw alpha as from mlp32_forward (the same
+// fmaf chain and cross-group sum) and groups 1..3 the finite placeholder 0.5 (the sigmoid of 0).
+__device__ __forceinline__ float mlp32_forward_density(const float* wf, const float* sv, const int g, const Emb32& e, Acts& a) {
+  mlp32_trunk_h4<false>(wf, sv, g, e, a);
+  a.hc = zero32();
+  float pa = 0.f;
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pa = fmaf(sv[SV_WA + 16 * tt + 4 * g + r], a.h4.t[tt][r], pa);
+  const float sa = xgroup_sum(pa);
+  return (g == 0) ? (sa + sv[SV_HB]) * 10.0f : 0.5f;
 }
 // the rendering form: EVERY lane group gets the density head (10 * raw alpha, model.py:88) and, groups 1..3, its own
 // colour channel after the sigmoid (group 0: 0)

@@ -8,6 +8,7 @@
 // all octaves) and the in-major conflict-free weight image (one ds_read_b64 per forward k-step, two ds_read_b128 per
 // transposed tile).  Per tile and wave: 560 MFMAs (602 before) and ~40 % fewer VALU instructions.
 #include <mutex>
+#include <type_traits>
 #define OBJ32_PIN 1        // this unit pins the MFMA issue order of mma_f16 and wg_pair (objnerf_mlp32.h)
 #include "objnerf_mlp32.h"
 #include "objnerf_train_common.h"
@@ -38,6 +39,12 @@ using namespace objtrain;
 #define OBJ32_WG_UNROLL_FAST 16
 #endif
 
+// 1: the instantiations that skip masked-out rays re-derive their lane constants at every phase (phase_lane below);
+// 0 exists to time the kernel without it (variant libraries only; profiles/masked_rays.txt)
+#ifndef OBJ32_PHASE_LANE
+#define OBJ32_PHASE_LANE 1
+#endif
+
 namespace {
 
 __device__ __forceinline__ void st_T32(float* stg_lane, const int rowbase, const T32& v) {
@@ -51,6 +58,13 @@ __device__ __forceinline__ void st_T16(float* stg_lane, const int rowbase, const
   if ((OBJ32_ABL) & 4) { asm volatile("" :: "v"(v)); return; }
 #pragma unroll
   for (int r = 0; r < 4; ++r) stg_lane[(rowbase + r) * STG_LD] = v[r];
+}
+// zeros to this wave's columns of rows rowbase .. rowbase + 16 NT - 1 (a wave whose rays the loss masks out: section 4.1.1
+// of DESIGN.md)
+template <int NT>
+__device__ __forceinline__ void st_zero(float* stg_lane, const int rowbase) {
+#pragma unroll
+  for (int T = 0; T < NT; ++T) st_T16(stg_lane, rowbase + 16 * T, zero4());
 }
 
 // D[out 0..31][in 16 cols] += sum_s dT[out][s] * aT[in][s] over the 128 staged samples (MFMA k-slot (step st, lane
@@ -188,11 +202,16 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
   // hook launch bit-equal to the production launch); the headline instantiation also unrolls its weight-gradient loops fully
   constexpr bool FAST = !FEAT;            // (measured in the feature instantiation too: 12.06 against 12.0 - 12.2 ms, no gain)
   constexpr int WGU = (!FEAT && !MASKS && SS == 64) ? OBJ32_WG_UNROLL_FAST : 8;
+  // Leave out the work of rays the loss masks out (label 2: everything; label 0: the colour layer).  Every part left out
+  // has an exact zero factor in the full computation, so the results are the same bits.  Not in the
+  // test-hook instantiation, whose outputs cover all rays and which is the control for that claim, and not (yet) with the
+  // feature loss, whose instantiations are register-tight.
+  constexpr bool SKIP = !FEAT && !MASKS;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
+  int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, g = lane >> 4;
+  int c = lane & 15, g = lane >> 4;
   float* sv = lds + sv_base(FEAT);
   float* s_alpha = lds + IMG;            // [4][TS]: 10 * raw alpha | colour[3]; overwritten in place by their gradients
   float* s_col = s_alpha + TS;
@@ -240,6 +259,22 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
   const float* wt1 = (const float*)__builtin_assume_aligned(lds + c * WROW + 8 * g + 4 * (1 - (g & 1)), 16);
   float* stg_lane = stg + (4 * g) * STG_LD + 16 * w + c;
   const float* lane_rd = stg + c * STG_LD + 32 * g;
+  int slot = 16 * w + c;
+  // The instantiations that leave masked-out work aside have more paths through a tile, and the allocator, at 256
+  // registers, then keeps the lane-derived constants above in scratch and reloads them inside the tile loop.  They
+  // re-derive them at every phase from a copy of the lane id the compiler cannot see through: a few VALU instructions
+  // per phase, and only the ones a phase uses are live in it.
+  auto phase_lane = [&]() {
+    if (!SKIP || !(OBJ32_PHASE_LANE)) return;
+    asm volatile("" : "+v"(lane));
+    c = lane & 15; g = lane >> 4;
+    slot = 16 * w + c;
+    wf = (const float*)__builtin_assume_aligned(lds + 4 * g * WROW + out_pos(c), 8);
+    wt0 = (const float*)__builtin_assume_aligned(lds + c * WROW + 8 * g + 4 * (g & 1), 16);
+    wt1 = (const float*)__builtin_assume_aligned(lds + c * WROW + 8 * g + 4 * (1 - (g & 1)), 16);
+    stg_lane = stg + (4 * g) * STG_LD + 16 * w + c;
+    lane_rd = stg + c * STG_LD + 32 * g;
+  };
 
   // persistent gradient accumulators
   f32x4 accA0 = zero4(), accA1 = zero4(), accB0 = zero4(), accB1 = zero4(), accC0 = zero4(), accC1 = zero4();
@@ -299,24 +334,71 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
   };
   const bool rows_mode = SS ? true : seg_is_rows(S);
   const SegRows seg_rows = SegRows::make(rows_mode ? S : 64, lane);
-  const int slot = 16 * w + c;
   float nx, ny, nz;
   fetch_point(t0, slot, nx, ny, nz);
+  // labels of the rays of a tile, fetched with its points: lane l holds ray l's in lb0 and, where a tile has more than 64
+  // rays, ray 64 + l's in lb1; 2 (unknown) where the tile has no such ray
+  auto fetch_labels = [&](const int tile_, int& lb0, int& lb1) {
+    lb0 = 2; lb1 = 2;
+    if (SKIP && tile_ < t1) {
+      const int r_ = tile_ * TR + lane;
+      if (lane < TR && r_ < R) lb0 = (int)a.labels[(long)k * R + r_];
+      if (TR > 64 && lane + 64 < TR && r_ + 64 < R) lb1 = (int)a.labels[(long)k * R + r_ + 64];
+    }
+  };
+  int nlb0, nlb1;
+  fetch_labels(t0, nlb0, nlb1);
   PT_INIT();
   for (int tile = t0; tile < t1; tile += tstep) {
     asm volatile("" ::: "memory");   // keep the LDS weight reads inside the loop (no LICM into registers)
+    phase_lane();
+    // what this tile may leave out: wave_* for the 16 samples of this wave, tile_* for all of its rays (every wave
+    // forms these from the same labels, so they agree).  A ray that does not exist counts as unknown.
+    //   wave_dead   only unknown rays: no forward pass, no input gradients; zeros to the wave's columns of the staging rows
+    //   wave_nocol  no ray of this object: no colour layer (forward, backward), no octaves 4, 5 of the encoding
+    //   tile_nocol  round A runs its two mid2 tile pairs only
+    //   tile_dead   every wave is dead and no weight-gradient round runs: the tile costs its barriers and the zero stores
+    // Every barrier stays outside these branches.  (tile_dead as a `continue` at this point, and dead paths that leave
+    // the registers that cross a phase undefined, both made the allocator spill inside the tile loop: 9.4 -> 14.9 ms.)
+    bool wave_dead = false, wave_nocol = false, tile_dead = false, tile_nocol = false;
+    if (SKIP) {
+      const unsigned long long known = __ballot(nlb0 != 2) | __ballot(nlb1 != 2);
+      const unsigned long long own = __ballot(nlb0 == 1) | __ballot(nlb1 == 1);
+      tile_dead = known == 0ull;
+      tile_nocol = own == 0ull;
+      if (SS == 64) {                 // the wave's 16 samples belong to ray w >> 2 of the tile
+        wave_dead = !((known >> (w >> 2)) & 1ull);
+        wave_nocol = !((own >> (w >> 2)) & 1ull);
+      } else {
+        const int q_ = slot / S;      // < 128: the lane's ray
+        const int l0 = __shfl(nlb0, q_ & 63, 64), l1 = __shfl(nlb1, q_ & 63, 64);
+        const int mine = q_ < 64 ? l0 : l1;
+        wave_dead = __all(mine == 2);
+        wave_nocol = __all(mine != 1);
+      }
+    }
     const int ray0 = tile * TR;
     // ---------------------------------------------------------------- 1. forward
     const int q = slot / S;
     const int ray = ray0 + q;
     const bool valid = (q < TR) && (ray < R);
     Pe32 pe;
-    pe32_project(sv, g, nx, ny, nz, scale, pe);     // (nx, ny, nz) fetched during the previous tile's phase C
-    PT(0);
     Acts act;
-    {
+    if (wave_dead) {
+      // no forward pass: finite placeholders (raw alpha 0, colour 0.5) for the compositing, which skips these rays too, or,
+      // in a pass that a live ray shares, multiplies what it makes of them by the zero masks
+      s_alpha[g * TS + slot] = (g == 0) ? 0.0f : 0.5f;
+      // (nothing reads these in a dead wave; they are given values because the allocator handles a register that is
+      // defined on every path far better than one that is not -- a few v_mov in a wave that has nothing else to do)
+      act.h1 = act.h2 = act.h3 = act.h4 = act.hc = zero32();
+      pe.t[0] = pe.t[1] = pe.t[2] = 0.f;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) pe.vh[i] = pe.vl[i] = 0.f;
+    } else {
+      pe32_project(sv, g, nx, ny, nz, scale, pe);     // (nx, ny, nz) fetched during the previous tile's phase C
+      PT(0);
       Emb32 e;                        // forward-only: the backward re-creates the embedding tile by tile
-      embed32(e, pe, g);
+      if (wave_nocol) embed32_x1(e, pe, g); else embed32(e, pe, g);
       PT(1);
       if (MASKS && a.emb_debug && valid) {     // test hook: this lane's share of its sample's embedding row
         float* er = a.emb_debug + (((long)k * R + ray) * S + (slot - q * S)) * (OBJ_E1 + OBJ_E2);
@@ -335,7 +417,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
             if (col >= 0) er[OBJ_E1 + col] = e.x2[T_][r_];
           }
       }
-      s_alpha[g * TS + slot] = mlp32_forward<FEAT>(wf, sv, g, e, act);
+      s_alpha[g * TS + slot] = wave_nocol ? mlp32_forward_density(wf, sv, g, e, act) : mlp32_forward<FEAT>(wf, sv, g, e, act);
     }
     if (MASKS && a.relu_masks) {      // test hook: ReLU branch bits of this lane's sample
       uint8_t* dst = a.relu_masks + (((long)k * R + (valid ? ray : 0)) * S + (slot - q * S)) * 24;
@@ -412,6 +494,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     } else if (FEAT && w * (64 / S) < TR) feat_inputs(w, 0, pf_uh, pf_beta, pf_ngv, pf_lab2);
     TILE_SYNC();
     PT(3);
+    phase_lane();
     // ---------------------------------------------------------------- 2. composite + loss (loss.py:27-101)
     auto composite_passes = [&](const auto& sg) {
       const int rpp = 64 / S;                       // rays per wave pass
@@ -426,6 +509,10 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         float gtd = pf_gtd, gr = pf_gr, gg = pf_gg, gb = pf_gb;
         int lab = pf_lab;
         if (ps != w) ray_inputs(ps, zz, gtd, gr, gg, gb, lab);      // (only when a tile has more than 8 passes)
+        if (SKIP && __all(lab == 2)) {      // only unknown rays (and lanes without one) in this pass: every mask is zero
+          if (on) { s_alpha[sl] = 0.0f; s_col[sl] = 0.0f; s_col[TS + sl] = 0.0f; s_col[2 * TS + sl] = 0.0f; }
+          continue;
+        }
         if (on) { al = s_alpha[sl]; c0 = s_col[sl]; c1 = s_col[TS + sl]; c2 = s_col[2 * TS + sl]; }
         const float occ = on ? sigmoid_acc(al) : 0.0f;               // render_rays.py:13
         const float fr = on ? (1.0f - occ) + 1e-10f : 1.0f;          // render_rays.py:38
@@ -683,13 +770,21 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     PT(4);
     TILE_SYNC();
     PT(5);
+    phase_lane();
     // ---------------------------------------------------------------- 3. backward
-    const float da = valid ? s_alpha[slot] : 0.0f;
-    const float dc0 = valid ? s_col[slot] : 0.0f;
-    const float dc1 = valid ? s_col[TS + slot] : 0.0f;
-    const float dc2 = valid ? s_col[2 * TS + slot] : 0.0f;
-    g_hb += (g == 0) ? da : ((g == 1) ? dc0 : ((g == 2) ? dc1 : dc2));
     float dps[6];
+    T32 d_hf, d_hc, d_h4, d_h3;
+    // phase A of a wave that has a ray the loss counts.  NC (a wave without a ray of this object, wave_nocol): d colour = 0,
+    // so d_hc = 0 and the colour layer adds nothing to d_h4, to d B or to the head gradients; its [h4 | x2] columns, which
+    // only ever meet d_hc, stay as they are (finite: the staging area starts a segment as zeros).
+    auto phase_a = [&](auto nc_) {
+    constexpr bool NC = decltype(nc_)::value;
+    const float da = valid ? s_alpha[slot] : 0.0f;
+    const float dc0 = (!NC && valid) ? s_col[slot] : 0.0f;
+    const float dc1 = (!NC && valid) ? s_col[TS + slot] : 0.0f;
+    const float dc2 = (!NC && valid) ? s_col[2 * TS + slot] : 0.0f;
+    if (NC) g_hb += (g == 0) ? da : 0.0f;
+    else g_hb += (g == 0) ? da : ((g == 1) ? dc0 : ((g == 2) ? dc1 : dc2));
 #pragma unroll
     for (int i = 0; i < 6; ++i) dps[i] = 0.f;
     // The sincos of the embedding is RE-computed below: hide the angles from CSE, otherwise the compiler keeps every
@@ -698,7 +793,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     for (int i = 0; i < 6; ++i) asm volatile("" : "+v"(pe.vh[i]), "+v"(pe.vl[i]));
 
     // ---- phase A: heads, colour layer, (feature layer,) mid2
-    T32 d_hf = zero32();
+    d_hf = zero32();
     if (FEAT) {           // d loss / d hf_s = w_s * (d loss / d fh of the sample's ray), through the ReLU
       const float wv = valid ? stg[F_SW + slot] : 0.0f;
 #pragma unroll
@@ -709,7 +804,6 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
           d_hf.t[tt][r] = ((hf_pos >> (4 * tt + r)) & 1u) ? wv * gv : 0.0f;
         }
     }
-    T32 d_hc, d_h4;
     float pa_[8];
     float pb_[8], pc_[8], pd_[8];       // head-weight gradient products, summed over the samples below (butterfly form)
 #pragma unroll
@@ -721,17 +815,22 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         const float hv = act.hc.t[tt][r];
         if (LAZY_H) {
           hW[0][s] = fmaf(da, act.h4.t[tt][r], hW[0][s]);
-          hW[1][s] = fmaf(dc0, hv, hW[1][s]);
-          hW[2][s] = fmaf(dc1, hv, hW[2][s]);
-          hW[3][s] = fmaf(dc2, hv, hW[3][s]);
+          if (!NC) {
+            hW[1][s] = fmaf(dc0, hv, hW[1][s]);
+            hW[2][s] = fmaf(dc1, hv, hW[2][s]);
+            hW[3][s] = fmaf(dc2, hv, hW[3][s]);
+          }
         } else {
           pa_[s] = da * act.h4.t[tt][r];
-          pb_[s] = dc0 * hv;
-          pc_[s] = dc1 * hv;
-          pd_[s] = dc2 * hv;
+          pb_[s] = NC ? 0.0f : dc0 * hv;
+          pc_[s] = NC ? 0.0f : dc1 * hv;
+          pd_[s] = NC ? 0.0f : dc2 * hv;
         }
-        const float dv = fmaf(sv[SV_WOC + 2 * H + row], dc2, fmaf(sv[SV_WOC + H + row], dc1, sv[SV_WOC + row] * dc0));
-        d_hc.t[tt][r] = hv > 0.0f ? dv : 0.0f;
+        if (NC) d_hc.t[tt][r] = 0.0f;
+        else {
+          const float dv = fmaf(sv[SV_WOC + 2 * H + row], dc2, fmaf(sv[SV_WOC + H + row], dc1, sv[SV_WOC + row] * dc0));
+          d_hc.t[tt][r] = hv > 0.0f ? dv : 0.0f;
+        }
         d_h4.t[tt][r] = sv[SV_WA + row] * da;
       }
     // round A staging (row maps: Lay)
@@ -740,11 +839,11 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
       gS1 += slot_sums16(pc_, pd_, c);
       asm volatile("" : "+v"(gS0), "+v"(gS1));
     }
-    st_T32(stg_lane, 0, act.h4);
+    if (!NC) st_T32(stg_lane, 0, act.h4);
     if (!FEAT) st_T32(stg_lane, LY::A_H3, act.h3);
     st_T32(stg_lane, LY::A_DHC, d_hc);
     if (FEAT) st_T32(stg_lane, LY::A_DHF, d_hf);
-    mma_t32<FAST>(d_h4, wt0, wt1, R_CL, d_hc);
+    if (!NC) mma_t32<FAST>(d_h4, wt0, wt1, R_CL, d_hc);
     if (FEAT) mma_t32<FAST>(d_h4, wt0, wt1, R_FL, d_hf);
     d_h4 = relu_mask32(d_h4, act.h4);
 #ifdef OBJ_LAZY_BIAS
@@ -766,7 +865,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     if (!FEAT) st_T32(stg_lane, LY::A_DH4, d_h4);
     // PE backward, x2 part (octaves 4, 5): a 16-row tile = two direction slots
 #pragma unroll
-    for (int T = 0; T < 3; ++T) {
+    for (int T = 0; T < (NC ? 0 : 3); ++T) {        // (NC: d_hc = 0, nothing reaches x2)
       f32x4 d_x = zero4();
       mma_t16<FAST>(d_x, wt0, wt1, R_CL + 32 + 16 * T, d_hc);
       if (FEAT) mma_t16<FAST>(d_x, wt0, wt1, R_FL + 32 + 16 * T, d_hf);
@@ -775,12 +874,25 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
       pe32_x2_pair_fb(pe, 2 * T + 1, g, d_x[2], d_x[3], dps[2 * T + 1], o2, o3);
       st_T16(stg_lane, 32 + 16 * T, f32x4{o0, o1, o2, o3});
     }
-    T32 d_h3 = zero32();
+    d_h3 = zero32();
     mma_t32<FAST>(d_h3, wt0, wt1, R_M2, d_h4);
     d_h3 = relu_mask32(d_h3, act.h3);
+    };      // phase_a
+    if (wave_dead) {
+      // nothing of this wave's samples enters any result: zeros to its columns of every operand of round A.  (Its
+      // activation columns could stay as they are, like the [h4 | x2] columns above; zeros keep the staging area free of
+      // anything an earlier tile left.)
+      st_zero<5>(stg_lane, 0);          // [h4 | x2]
+      st_zero<6>(stg_lane, 96);         // h3, d_hc, d_h4
+      d_hc = d_h4 = d_h3 = d_hf = zero32();    // (defined on every path: see the forward pass)
+#pragma unroll
+      for (int i = 0; i < 6; ++i) dps[i] = 0.f;
+    } else if (wave_nocol) phase_a(std::true_type{});
+    else phase_a(std::false_type{});
     PT(6);
     TILE_SYNC();
     PT(7);
+    phase_lane();
     if (FEAT) {
       // round A: colour tiles 0..4 (waves 0..4), feature tiles 0..2 (waves 5..7)
       const int dTr = (w < 5) ? LY::A_DHC : LY::A_DHF;
@@ -798,7 +910,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         const int aTr = (w < 4) ? 48 + 16 * t2 : LY::A_H3 + 16 * t2;
         wg_half<WGU>(accA2, lane_rd + dTr * STG_LD, lane_rd + aTr * STG_LD);
       }
-    } else if (w < 7) {
+    } else if (w < 7 && !(tile_nocol && w < 5) && !tile_dead) {     // (no ray of this object in the tile: d_hc is all zero)
       const int dTr = (w < 5) ? 128 : 160;
       const int aTr = (w < 5) ? 16 * w : 96 + 16 * (w - 5);
       wg_pair<WGU>(accA0, accA1, lane_rd + dTr * STG_LD, lane_rd + aTr * STG_LD);
@@ -806,10 +918,17 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     PT(8);
     TILE_SYNC();
     PT(9);
+    phase_lane();
     // ---- phase B: cat layer.  [h2 | x1] rows 0..127, d_h3pre rows 128..
+    T32 d_h2, d_h1;
+    if (wave_dead) {
+      st_zero<8>(stg_lane, 0);          // [h2 | x1]
+      st_zero<2>(stg_lane, 128);        // d_h3
+      d_h2 = d_h1 = zero32();
+    } else {
     st_T32(stg_lane, 0, act.h2);
     st_T32(stg_lane, 128, d_h3);
-    T32 d_h2 = zero32();
+    d_h2 = zero32();
     mma_t32<FAST>(d_h2, wt0, wt1, R_CAT, d_h3);
     d_h2 = relu_mask32(d_h2, act.h2);
 #ifdef OBJ_LAZY_BIAS
@@ -829,7 +948,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
       asm volatile("" : "+v"(gS2));
     }
 #endif
-    T32 d_h1 = zero32();
+    d_h1 = zero32();
     mma_t32<FAST>(d_h1, wt0, wt1, R_M1, d_h2);
     d_h1 = relu_mask32(d_h1, act.h1);
     // PE backward, x1 part (octaves 0..3): d x1 tile = cat^T d_h3 + in^T d_h1; a tile = one direction slot
@@ -847,21 +966,31 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
       dB[i][1] = fmaf(dps[i], pe.t[1], dB[i][1]);
       dB[i][2] = fmaf(dps[i], pe.t[2], dB[i][2]);
     }
+    }      // !wave_dead
     PT(10);
     PT(11);
     TILE_SYNC();
     PT(12);
-    wg_pair<WGU>(accB0, accB1, lane_rd + 128 * STG_LD, lane_rd + (16 * w) * STG_LD);
+    phase_lane();
+    if (!tile_dead) wg_pair<WGU>(accB0, accB1, lane_rd + 128 * STG_LD, lane_rd + (16 * w) * STG_LD);
     PT(13);
     TILE_SYNC();
+    phase_lane();
     // ---- phase C: in layer (x1 stays at rows 32..127) + mid1.  h1 rows 0.., d_h1pre 128.., d_h2pre 160..
     fetch_point(tile + tstep, slot, nx, ny, nz);
+    fetch_labels(tile + tstep, nlb0, nlb1);
+    if (wave_dead) {
+      st_zero<2>(stg_lane, 0);          // h1 (x1 stays: zeros since phase B)
+      st_zero<4>(stg_lane, 128);        // d_h1, d_h2
+    } else {
     st_T32(stg_lane, 0, act.h1);
     st_T32(stg_lane, 128, d_h1);
     if (!FEAT) st_T32(stg_lane, LY::C_DH2, d_h2);
+    }
     PT(14);
     TILE_SYNC();
     PT(15);
+    phase_lane();
     if (FEAT) {
       // round C: the six in-layer tiles; round C2: d_h2 over the d_h1 rows, the two mid1 tiles as eight quarters
       if (w < 6) wg_pair<WGU>(accC0, accC1, lane_rd + 128 * STG_LD, lane_rd + (32 + 16 * w) * STG_LD);
@@ -874,7 +1003,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
                  16 * (w & 1));
       // the next tile's forward pass writes its hidden-feature buffer into rows this round is reading
       TILE_SYNC();
-    } else {
+    } else if (!tile_dead) {
       const int dTr = (w < 6) ? 128 : 160;
       const int aTr = (w < 6) ? 32 + 16 * w : 16 * (w - 6);
       wg_pair<WGU>(accC0, accC1, lane_rd + dTr * STG_LD, lane_rd + aTr * STG_LD);
