@@ -39,10 +39,11 @@ using namespace objtrain;
 #define OBJ32_WG_UNROLL_FAST 16
 #endif
 
-// 1: the instantiations that skip masked-out rays re-derive their lane constants at every phase (phase_lane below);
-// 0 exists to time the kernel without it (variant libraries only; profiles/masked_rays.txt)
+// The instantiations that skip masked-out rays re-derive their lane constants (phase_lane below) at the phases whose bit
+// is set here: bit 0 the top of the tile, 1 compositing, 2 phase A, 3 round A, 4 phase B, 5 round B, 6 phase C, 7 round C.
+// 0x11 is the product; other masks exist to time the kernel (variant libraries only; profiles/live_path.txt).
 #ifndef OBJ32_PHASE_LANE
-#define OBJ32_PHASE_LANE 1
+#define OBJ32_PHASE_LANE 0x11
 #endif
 
 namespace {
@@ -250,8 +251,12 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
   const float n1 = (float)a.counts[2 * k], n2 = (float)a.counts[2 * k + 1];
   int bflag0, bflag1;
   batch_flags(a, bflag0, bflag1);
-  const float inv1 = bflag0 ? 0.0f : 1.0f / (n1 + 1e-10f);
-  const float inv2 = bflag1 ? 0.0f : 1.0f / (n2 + 1e-10f);
+  float inv1 = bflag0 ? 0.0f : 1.0f / (n1 + 1e-10f);
+  float inv2 = bflag1 ? 0.0f : 1.0f / (n2 + 1e-10f);
+  if (SKIP) {      // wave-uniform, but the division leaves them in vector registers, which the tile loop then kept in scratch
+    inv1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, inv1)));
+    inv2 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, inv2)));
+  }
 
   // per-lane LDS bases (objnerf_mlp32.h)
   const float* wf = (const float*)__builtin_assume_aligned(lds + 4 * g * WROW + out_pos(c), 8);
@@ -262,11 +267,13 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
   int slot = 16 * w + c;
   // The instantiations that leave masked-out work aside have more paths through a tile, and the allocator, at 256
   // registers, then keeps the lane-derived constants above in scratch and reloads them inside the tile loop.  They
-  // re-derive them at every phase from a copy of the lane id the compiler cannot see through: a few VALU instructions
-  // per phase, and only the ones a phase uses are live in it.
-  auto phase_lane = [&]() {
-    if (!SKIP || !(OBJ32_PHASE_LANE)) return;
-    asm volatile("" : "+v"(lane));
+  // re-derive them from the lane id, which v_mbcnt makes out of nothing (no register carries it across the tile; the
+  // asm keeps the compiler from hoisting it), and only the constants a phase uses are live in it.  Two sites are enough
+  // since the predicates are one scalar register (below): the top of the tile and phase B.  Every site costs 0.15 - 0.2 ms
+  // per step; none: 110 - 120 spilled registers and scratch reloads between the MFMAs again (profiles/live_path.txt).
+  auto phase_lane = [&](const int site) {
+    if (!SKIP || !(((OBJ32_PHASE_LANE) >> site) & 1)) return;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     c = lane & 15; g = lane >> 4;
     slot = 16 * w + c;
     wf = (const float*)__builtin_assume_aligned(lds + 4 * g * WROW + out_pos(c), 8);
@@ -351,7 +358,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
   PT_INIT();
   for (int tile = t0; tile < t1; tile += tstep) {
     asm volatile("" ::: "memory");   // keep the LDS weight reads inside the loop (no LICM into registers)
-    phase_lane();
+    phase_lane(0);
     // what this tile may leave out: wave_* for the 16 samples of this wave, tile_* for all of its rays (every wave
     // forms these from the same labels, so they agree).  A ray that does not exist counts as unknown.
     //   wave_dead   only unknown rays: no forward pass, no input gradients; zeros to the wave's columns of the staging rows
@@ -360,23 +367,37 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     //   tile_dead   every wave is dead and no weight-gradient round runs: the tile costs its barriers and the zero stores
     // Every barrier stays outside these branches.  (tile_dead as a `continue` at this point, and dead paths that leave
     // the registers that cross a phase undefined, both made the allocator spill inside the tile loop: 9.4 -> 14.9 ms.)
-    bool wave_dead = false, wave_nocol = false, tile_dead = false, tile_nocol = false;
+    // They cross the whole tile.  As booleans each would be a 64-bit lane mask in a scalar register pair; they are packed
+    // into the bits of ONE scalar register and read back, at every use, through a copy the compiler cannot see through, so
+    // that the tile carries one register and every use is a bit test.  (That relief is what took the kernel's last
+    // spilled accumulator out of the tile loop: 129 spilled scalar registers, three vector registers of spill lanes,
+    // before; 107 after.)
+    int pred_bits = 0;
     if (SKIP) {
       const unsigned long long known = __ballot(nlb0 != 2) | __ballot(nlb1 != 2);
       const unsigned long long own = __ballot(nlb0 == 1) | __ballot(nlb1 == 1);
-      tile_dead = known == 0ull;
-      tile_nocol = own == 0ull;
+      bool wd, wn;
       if (SS == 64) {                 // the wave's 16 samples belong to ray w >> 2 of the tile
-        wave_dead = !((known >> (w >> 2)) & 1ull);
-        wave_nocol = !((own >> (w >> 2)) & 1ull);
+        wd = !((known >> (w >> 2)) & 1ull);
+        wn = !((own >> (w >> 2)) & 1ull);
       } else {
         const int q_ = slot / S;      // < 128: the lane's ray
         const int l0 = __shfl(nlb0, q_ & 63, 64), l1 = __shfl(nlb1, q_ & 63, 64);
         const int mine = q_ < 64 ? l0 : l1;
-        wave_dead = __all(mine == 2);
-        wave_nocol = __all(mine != 1);
+        wd = __all(mine == 2);
+        wn = __all(mine != 1);
       }
+      pred_bits = __builtin_amdgcn_readfirstlane((wd ? 1 : 0) | (wn ? 2 : 0) | (known == 0ull ? 4 : 0) | (own == 0ull ? 8 : 0));
     }
+    auto pred = [&](const int bit) -> bool {
+      if (!SKIP) return false;
+      asm volatile("" : "+s"(pred_bits));
+      return (pred_bits >> bit) & 1;
+    };
+    auto wave_dead = [&]() { return pred(0); };
+    auto wave_nocol = [&]() { return pred(1); };
+    auto tile_dead = [&]() { return pred(2); };
+    auto tile_nocol = [&]() { return pred(3); };
     const int ray0 = tile * TR;
     // ---------------------------------------------------------------- 1. forward
     const int q = slot / S;
@@ -384,7 +405,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     const bool valid = (q < TR) && (ray < R);
     Pe32 pe;
     Acts act;
-    if (wave_dead) {
+    if (wave_dead()) {
       // no forward pass: finite placeholders (raw alpha 0, colour 0.5) for the compositing, which skips these rays too, or,
       // in a pass that a live ray shares, multiplies what it makes of them by the zero masks
       s_alpha[g * TS + slot] = (g == 0) ? 0.0f : 0.5f;
@@ -398,7 +419,9 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
       pe32_project(sv, g, nx, ny, nz, scale, pe);     // (nx, ny, nz) fetched during the previous tile's phase C
       PT(0);
       Emb32 e;                        // forward-only: the backward re-creates the embedding tile by tile
-      if (wave_nocol) embed32_x1(e, pe, g); else embed32(e, pe, g);
+      // (two branches on the same bit, not one around both calls: with the embedding and the network of an arm in ONE block
+      // the step was 0.1 ms slower -- 8.71 against 8.61 ms, profiles/live_path.txt)
+      if (wave_nocol()) embed32_x1(e, pe, g); else embed32(e, pe, g);
       PT(1);
       if (MASKS && a.emb_debug && valid) {     // test hook: this lane's share of its sample's embedding row
         float* er = a.emb_debug + (((long)k * R + ray) * S + (slot - q * S)) * (OBJ_E1 + OBJ_E2);
@@ -417,7 +440,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
             if (col >= 0) er[OBJ_E1 + col] = e.x2[T_][r_];
           }
       }
-      s_alpha[g * TS + slot] = wave_nocol ? mlp32_forward_density(wf, sv, g, e, act) : mlp32_forward<FEAT>(wf, sv, g, e, act);
+      s_alpha[g * TS + slot] = wave_nocol() ? mlp32_forward_density(wf, sv, g, e, act) : mlp32_forward<FEAT>(wf, sv, g, e, act);
     }
     if (MASKS && a.relu_masks) {      // test hook: ReLU branch bits of this lane's sample
       uint8_t* dst = a.relu_masks + (((long)k * R + (valid ? ray : 0)) * S + (slot - q * S)) * 24;
@@ -494,7 +517,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     } else if (FEAT && w * (64 / S) < TR) feat_inputs(w, 0, pf_uh, pf_beta, pf_ngv, pf_lab2);
     TILE_SYNC();
     PT(3);
-    phase_lane();
+    phase_lane(1);
     // ---------------------------------------------------------------- 2. composite + loss (loss.py:27-101)
     auto composite_passes = [&](const auto& sg) {
       const int rpp = 64 / S;                       // rays per wave pass
@@ -517,7 +540,9 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         const float occ = on ? sigmoid_acc(al) : 0.0f;               // render_rays.py:13
         const float fr = on ? (1.0f - occ) + 1e-10f : 1.0f;          // render_rays.py:38
         const float Pinc = sg.scan_mul(fr, pos);
-        float T = __shfl_up(Pinc, 1, 64);
+        // (SKIP: the same move as one DPP instruction -- __shfl_up works from the workitem id, which the tile loop of these
+        // instantiations would reload from scratch on the two compositing waves, the tile's serial section)
+        float T = SKIP ? dpp_mov<0x138>(1.0f, Pinc) : __shfl_up(Pinc, 1, 64);
         if (pos == 0) T = 1.0f;
         const float wgt = occ * T;                                   // render_rays.py:43
         const float D = sg.total_add(wgt * zz, pos);       // loss.py:31
@@ -766,11 +791,17 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         }
       }
     } else if ((OBJ32_ABL) & 1) { /* ablation: no compositing */
-    } else if (SS || rows_mode) composite_passes(seg_rows); else composite_passes(SegGeneric{S});
+    } else if (SKIP && SS == 64) composite_passes(SegRows::make(64, lane));   // (six lane masks less across the tile)
+    else if (SS || rows_mode) composite_passes(seg_rows); else composite_passes(SegGeneric{S});
     PT(4);
+    // A pass that leaves through the `continue` above has read only the label of its prefetched ray inputs.  Name all of
+    // them here, on every path: the wait for those loads then stands at this point, before the barrier, and not at whatever
+    // later instruction first reuses one of their registers -- that was phase C, behind the next tile's point fetch, whose
+    // HBM latency the in-order counter then put on every tile's critical path.
+    if (SKIP) asm volatile("" :: "v"(pf_zz), "v"(pf_gtd), "v"(pf_gr), "v"(pf_gg), "v"(pf_gb), "v"(pf_lab));
     TILE_SYNC();
     PT(5);
-    phase_lane();
+    phase_lane(2);
     // ---------------------------------------------------------------- 3. backward
     float dps[6];
     T32 d_hf, d_hc, d_h4, d_h3;
@@ -878,7 +909,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     mma_t32<FAST>(d_h3, wt0, wt1, R_M2, d_h4);
     d_h3 = relu_mask32(d_h3, act.h3);
     };      // phase_a
-    if (wave_dead) {
+    if (wave_dead()) {
       // nothing of this wave's samples enters any result: zeros to its columns of every operand of round A.  (Its
       // activation columns could stay as they are, like the [h4 | x2] columns above; zeros keep the staging area free of
       // anything an earlier tile left.)
@@ -887,12 +918,12 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
       d_hc = d_h4 = d_h3 = d_hf = zero32();    // (defined on every path: see the forward pass)
 #pragma unroll
       for (int i = 0; i < 6; ++i) dps[i] = 0.f;
-    } else if (wave_nocol) phase_a(std::true_type{});
+    } else if (wave_nocol()) phase_a(std::true_type{});
     else phase_a(std::false_type{});
     PT(6);
     TILE_SYNC();
     PT(7);
-    phase_lane();
+    phase_lane(3);
     if (FEAT) {
       // round A: colour tiles 0..4 (waves 0..4), feature tiles 0..2 (waves 5..7)
       const int dTr = (w < 5) ? LY::A_DHC : LY::A_DHF;
@@ -910,7 +941,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         const int aTr = (w < 4) ? 48 + 16 * t2 : LY::A_H3 + 16 * t2;
         wg_half<WGU>(accA2, lane_rd + dTr * STG_LD, lane_rd + aTr * STG_LD);
       }
-    } else if (w < 7 && !(tile_nocol && w < 5) && !tile_dead) {     // (no ray of this object in the tile: d_hc is all zero)
+    } else if (w < 7 && !(tile_nocol() && w < 5) && !tile_dead()) {     // (no ray of this object in the tile: d_hc is all zero)
       const int dTr = (w < 5) ? 128 : 160;
       const int aTr = (w < 5) ? 16 * w : 96 + 16 * (w - 5);
       wg_pair<WGU>(accA0, accA1, lane_rd + dTr * STG_LD, lane_rd + aTr * STG_LD);
@@ -918,10 +949,10 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     PT(8);
     TILE_SYNC();
     PT(9);
-    phase_lane();
+    phase_lane(4);
     // ---- phase B: cat layer.  [h2 | x1] rows 0..127, d_h3pre rows 128..
     T32 d_h2, d_h1;
-    if (wave_dead) {
+    if (wave_dead()) {
       st_zero<8>(stg_lane, 0);          // [h2 | x1]
       st_zero<2>(stg_lane, 128);        // d_h3
       d_h2 = d_h1 = zero32();
@@ -971,15 +1002,15 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     PT(11);
     TILE_SYNC();
     PT(12);
-    phase_lane();
-    if (!tile_dead) wg_pair<WGU>(accB0, accB1, lane_rd + 128 * STG_LD, lane_rd + (16 * w) * STG_LD);
+    phase_lane(5);
+    if (!tile_dead()) wg_pair<WGU>(accB0, accB1, lane_rd + 128 * STG_LD, lane_rd + (16 * w) * STG_LD);
     PT(13);
     TILE_SYNC();
-    phase_lane();
+    phase_lane(6);
     // ---- phase C: in layer (x1 stays at rows 32..127) + mid1.  h1 rows 0.., d_h1pre 128.., d_h2pre 160..
     fetch_point(tile + tstep, slot, nx, ny, nz);
     fetch_labels(tile + tstep, nlb0, nlb1);
-    if (wave_dead) {
+    if (wave_dead()) {
       st_zero<2>(stg_lane, 0);          // h1 (x1 stays: zeros since phase B)
       st_zero<4>(stg_lane, 128);        // d_h1, d_h2
     } else {
@@ -990,7 +1021,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     PT(14);
     TILE_SYNC();
     PT(15);
-    phase_lane();
+    phase_lane(7);
     if (FEAT) {
       // round C: the six in-layer tiles; round C2: d_h2 over the d_h1 rows, the two mid1 tiles as eight quarters
       if (w < 6) wg_pair<WGU>(accC0, accC1, lane_rd + 128 * STG_LD, lane_rd + (32 + 16 * w) * STG_LD);
@@ -1003,7 +1034,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
                  16 * (w & 1));
       // the next tile's forward pass writes its hidden-feature buffer into rows this round is reading
       TILE_SYNC();
-    } else if (!tile_dead) {
+    } else if (!tile_dead()) {
       const int dTr = (w < 6) ? 128 : 160;
       const int aTr = (w < 6) ? 32 + 16 * w : 16 * (w - 6);
       wg_pair<WGU>(accC0, accC1, lane_rd + dTr * STG_LD, lane_rd + aTr * STG_LD);
