@@ -922,6 +922,55 @@ int objnerf_mesh_cull_emit(int64_t V, int64_t F, int32_t rule, const uint8_t* ke
                            size_t ws_bytes, int64_t Vn, int64_t Fn, int32_t* new_of_old, int32_t* old_of_new,
                            int32_t* faces_out, int32_t* face_old, void* stream);
 
+/* A novel view of the whole map in one launch chain (objnerf_mapview.hip; openobj_amd/map_view.py):
+ * replaces the per-object loop of train.py:550-612 (`cfg.if_render`) -- one sceneObject.render_2D_syn (vmap.py:604-685)
+ * per object and the z-buffer merge of train.py:581-598 on the host.  Added under ABI 14: the five entries below are
+ * purely additive, so OBJNERF_ABI_VERSION stays 14.
+ *
+ * objnerf_view_rays_count / _emit (Trainer.sample_points_bbox, trainer.py:130-167, for every object at once): T_WC [4][4]
+ * row-major, dirs_C [P][3] the camera rays of the view with p = w * H + h (the transposed [W, H] image), boxes [K][16] =
+ * T_OC rows 0..2 [3][4] | extent / 2 [3] | unused, T_OC = inverse(T_WO) @ T_WC formed by the caller as
+ * sample_points_bbox forms it.  Every (pixel, box) runs the arithmetic of objnerf_box_rays (one device function); the
+ * hits of object k are segment k of a CSR in the caller's object order, ascending in p inside a segment (no atomics).
+ * An object with at most one hit gets an empty segment (trainer.py:164-165).  count: seg_off [K + 1] int64 on the
+ * device; ws: objnerf_view_rays_workspace_bytes(P, K), handed on to emit unchanged.  emit (same inputs; M = seg_off[K]
+ * as counted, M >= 2^32 is EINVAL: the merge keys hold an entry in 32 bits): pix [M] int32, dirs_W [M][3], near [M]
+ * (>= 0), far [M] (+ 0.2).
+ *
+ * objnerf_render_fwd_segmented: objnerf_render_fwd (fp32 mode, no feature hidden, no z) over the segments of every
+ * hidden-32, n_freqs == 6 object of the view in ONE launch of persistent workgroups.  params / scale: the stacked arena
+ * of those objects (row r at params + r * p_stride, scale[r]); origin [3]: the camera centre.  rows [n_rows][4] int64 on
+ * the device: seg_lo, seg_hi (the row's entries of the CSR), u_lo (the row of u its first ray reads; < 0: drawn inside
+ * the kernel under (seed, draw)), draw.  tiles [n_tiles][3] int32 on the device: arena row, first 16-ray group counted
+ * from seg_lo, number of groups; a tile belongs to one row, tiles of a row are adjacent.  Ray r = entry - seg_lo is the
+ * row of u and the Philox counter, as ray r of objnerf_render_fwd is: the outputs (CSR-aligned out_depth [M],
+ * out_opacity [M], out_rgb [M][3]) are bit-equal to a per-object objnerf_render_fwd on the same rays, whatever
+ * `workgroups` (0 = two per compute unit) is.  A row whose segment or draws would leave [0, M) / [0, u_rows) renders
+ * nothing.
+ *
+ * objnerf_view_merge: the merge of train.py:581-598 in closed form.  info [K][2] int32: background flag, the id written
+ * into the mask-id image.  An entry is offered iff !((depth < near) | (depth > far) | (opacity < 0.9)) and depth < 100;
+ * W(p) = the offered foreground entry of smallest depth (ties: the earliest object), depth(p) = its depth or 100; the
+ * painter of p is the last offered background entry behind W's object in the order with a smaller depth than W (without
+ * W: the last one), otherwise W.  best_fg [P] uint64 and best_bg [P] uint32: workspace, initialised here.  Outputs per
+ * pixel: out_rgb [P][3] uint8 (rgb * 255 truncated), out_maskid [P] int32 (0 = nothing painted), out_depth [P],
+ * out_winner [P] int32 (the painter's entry, -1 = none).  64-bit atomicMin / 32-bit atomicMax of integers only: two
+ * calls write the same bytes. */
+size_t objnerf_view_rays_workspace_bytes(int64_t P, int32_t K);
+int objnerf_view_rays_count(int64_t P, int32_t K, const float* T_WC, const float* boxes, const float* dirs_C, void* ws,
+                            size_t ws_bytes, int64_t* seg_off, void* stream);
+int objnerf_view_rays_emit(int64_t P, int32_t K, const float* T_WC, const float* boxes, const float* dirs_C, const void* ws,
+                           size_t ws_bytes, int64_t M, int32_t* pix, float* dirs_W, float* near, float* far, void* stream);
+int objnerf_render_fwd_segmented(const objnerf_net* net, int32_t n_rows, int64_t n_tiles, int32_t n_bins, int64_t M,
+                                 const float* params, int64_t p_stride, const float* scale, const float* origin,
+                                 const int64_t* rows, const int32_t* tiles, const float* dirs_W, const float* near,
+                                 const float* far, const float* u, int64_t u_rows, uint64_t seed, float* out_depth,
+                                 float* out_opacity, float* out_rgb, int32_t workgroups, void* stream);
+int objnerf_view_merge(int64_t P, int32_t K, int64_t M, const int64_t* seg_off, const int32_t* pix, const float* depth,
+                       const float* opacity, const float* rgb, const float* near, const float* far, const int32_t* info,
+                       int32_t any_background, uint64_t* best_fg, uint32_t* best_bg, uint8_t* out_rgb, int32_t* out_maskid,
+                       float* out_depth, int32_t* out_winner, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
 #include "objnerf_wg.h"
 #include "objnerf_generic.h"
 #include "objnerf_step_tail.h"
+#include "objnerf_boxray.h"
 
 namespace {
 
@@ -664,21 +665,12 @@ __global__ void box_rays_kernel(long P, const float* T_WC, const float* T_OC, co
                                 float* dirs_W, float* near_o, float* far_o, uint8_t* hit_o) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P) return;
-  const float d0 = dirs_C[i * 3], d1 = dirs_C[i * 3 + 1], d2 = dirs_C[i * 3 + 2];
-  float nr = -INFINITY, fr = INFINITY;
+  const BoxRay b = box_ray(T_WC, T_OC, half, dirs_C[i * 3], dirs_C[i * 3 + 1], dirs_C[i * 3 + 2]);   // objnerf_boxray.h
 #pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    // utils.py:324-336: R @ d, products accumulated left to right
-    dirs_W[i * 3 + r] = (T_WC[r * 4] * d0 + T_WC[r * 4 + 1] * d1) + T_WC[r * 4 + 2] * d2;
-    const float dr = (T_OC[r * 4] * d0 + T_OC[r * 4 + 1] * d1) + T_OC[r * 4 + 2] * d2;
-    const float o = T_OC[r * 4 + 3];
-    const float ta = (-half[r] - o) / dr, tb = (half[r] - o) / dr;       // utils.py:311-312
-    nr = fmaxf(nr, fminf(ta, tb));
-    fr = fminf(fr, fmaxf(ta, tb));
-  }
-  hit_o[i] = (nr <= fr) && (fr > 0.f);                                    // :317
-  near_o[i] = fmaxf(nr, 0.f);                                             // trainer.py:166
-  far_o[i] = fr + 0.2f;                                                   // :167
+  for (int r = 0; r < 3; ++r) dirs_W[i * 3 + r] = b.dw[r];
+  hit_o[i] = b.hit;
+  near_o[i] = b.near_;
+  far_o[i] = b.far_;
 }
 
 __global__ void box_points_kernel(long n, int n_bins, const float* origin, const float* dirs_W, const float* near_i,

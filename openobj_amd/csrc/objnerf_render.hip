@@ -9,20 +9,11 @@
 // in a register -- no scan, no shuffle -- and depth / opacity / colour / the 32-wide feature hidden accumulate per lane.
 // Nothing per sample ever leaves the registers; a ray costs 20 B of input and 16 + 128 B of output.  The 512-d head is
 // applied afterwards to the composited hidden of the rays that pass the masks (exact: the head is linear).
-#include "objnerf_mlp32.h"
-#include "objnerf_philox.h"
+#include "objnerf_render_body.h"
 #include "../../include/objnerf_hip.h"
 
 namespace {
 using namespace obj32n;
-
-struct RenderDev {
-  long n; int n_bins, G;
-  const float* params; const float* scale; const float* origin; const float* dirs_W; const float* near_; const float* far_;
-  const float* u; uint64_t seed; uint32_t draw;
-  float* depth; float* opacity; float* rgb; float* hfeat; float* z_out;
-  Layout L;
-};
 
 template <bool FEAT>
 __global__ __launch_bounds__(256) void render_fwd_kernel(const RenderDev a) {
@@ -38,60 +29,8 @@ __global__ __launch_bounds__(256) void render_fwd_kernel(const RenderDev a) {
   const int S = a.n_bins - 1;
   const long ngroups = (a.n + 15) / 16;                      // 16 rays per wave step
   const uint32_t st = objrng::S_BOX_U | (a.draw << 3);
-  for (long grp = (long)blockIdx.x * 4 + w; grp < ngroups; grp += (long)a.G * 4) {
-    asm volatile("" ::: "memory");   // keep the LDS weight reads inside the loop (no LICM into registers)
-    const long ray = grp * 16 + c;
-    const bool valid = ray < a.n;
-    const long r = valid ? ray : a.n - 1;
-    const float lo = a.near_[r], hi = a.far_[r];
-    const float dx = a.dirs_W[r * 3], dy = a.dirs_W[r * 3 + 1], dz = a.dirs_W[r * 3 + 2];
-    const float* ur = a.u ? a.u + r * a.n_bins : nullptr;
-    float ublk[4] = {0.f, 0.f, 0.f, 0.f};
-    auto draw_u = [&](const int s) {                          // the draw of bin s (injected, or Philox block s >> 2)
-      if (ur) return ur[s];
-      if ((s & 3) == 0 || s == 0) objrng::uniform4(a.seed, st, (uint32_t)(r >> 32), (uint32_t)r, (uint32_t)(s >> 2), ublk);
-      return ublk[s & 3];
-    };
-    float z0 = strat(lo, hi, 0, a.n_bins, draw_u(0));
-    float T = 1.0f;                                           // transmittance in front of the current sample
-    float aD = 0.f, aO = 0.f, aC = 0.f;
-    T32 aF = zero32();
-    for (int s = 0; s < S; ++s) {
-      const float z1 = strat(lo, hi, s + 1, a.n_bins, draw_u(s + 1));
-      const float z = 0.5f * (z1 + z0);                       // trainer.py:175
-      z0 = z1;
-      if (a.z_out && valid && g == 0) a.z_out[r * S + s] = z;
-      Pe32 pe;
-      pe32_project(sv, g, ox + dx * z, oy + dy * z, oz + dz * z, scale, pe);     // trainer.py:176, embedding.py:47-48
-      Emb32 e;
-      embed32(e, pe, g);
-      Acts act;
-      float alpha10, col;
-      mlp32_forward_all<FEAT>(wf, sv, g, e, act, alpha10, col);
-      const float occ = sigmoid_acc(alpha10);                 // render_rays.py:6-14
-      const float wgt = occ * T;                              // render_rays.py:32-54
-      T *= (1.0f - occ) + 1e-10f;
-      aD = fmaf(wgt, z, aD);                                  // render_rays.py:56-63
-      aO += wgt;
-      aC = fmaf(wgt, col, aC);
-      if (FEAT) {
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr) aF.t[tt][rr] = fmaf(wgt, act.hf.t[tt][rr], aF.t[tt][rr]);
-      }
-    }
-    if (valid) {
-      if (g == 0) { a.depth[ray] = aD; a.opacity[ray] = aO; }
-      else a.rgb[ray * 3 + g - 1] = aC;
-      if (FEAT) {
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-          *reinterpret_cast<float4*>(a.hfeat + ray * H + 16 * tt + 4 * g) =
-              make_float4(aF.t[tt][0], aF.t[tt][1], aF.t[tt][2], aF.t[tt][3]);
-      }
-    }
-  }
+  for (long grp = (long)blockIdx.x * 4 + w; grp < ngroups; grp += (long)a.G * 4)
+    render_group<FEAT>(a, sv, wf, scale, ox, oy, oz, S, st, c, g, grp);      // objnerf_render_body.h
 }
 
 }  // namespace

@@ -1868,3 +1868,162 @@ def mesh_compact(keep_v: torch.Tensor, faces: torch.Tensor, rule: str = "all", o
     check(lib().objnerf_mesh_cull_emit(V, F, r, kp, fp, _ptr(ws), nbytes, Vn, Fn, p["new_of_old"], p["old_of_new"],
                                        p["faces"], p["face_old"], _stream()), "objnerf_mesh_cull_emit")
     return res
+
+
+# ------------------------------------------------------------- a novel view of the whole map (objnerf_mapview.hip)
+# additive under ABI 14; map_view.MapView drives these
+VIEW_MAX_ENTRIES = 2 ** 32 - 1          # the merge keys hold an entry of the CSR in 32 bits
+VIEW_TILE_GROUPS = 4                    # 16-ray groups per tile of render_fwd_segmented: one per wave of a workgroup
+
+
+def _view_inputs(T_WC, boxes, dirs_C, name):
+    dirs_C, boxes = _req(dirs_C, torch.float32, f"{name}: dirs_C"), _req(boxes, torch.float32, f"{name}: boxes")
+    if dirs_C.dim() != 2 or dirs_C.shape[1] != 3 or dirs_C.shape[0] < 1 or boxes.dim() != 2 or boxes.shape[1] != 16 or \
+            boxes.shape[0] < 1:
+        raise _lib.ObjnerfError(f"{name}: dirs_C [P >= 1, 3], boxes [K >= 1, 16]")
+    T_WC = _req(T_WC, torch.float32, f"{name}: T_WC")
+    if tuple(T_WC.shape) != (4, 4) or T_WC.device != dirs_C.device or boxes.device != dirs_C.device:
+        raise _lib.ObjnerfError(f"{name}: T_WC [4, 4], on the device of dirs_C and boxes")
+    return T_WC, boxes, dirs_C
+
+
+def view_rays_count(T_WC: torch.Tensor, boxes: torch.Tensor, dirs_C: torch.Tensor):
+    """The camera rays dirs_C [P, 3] (p = w * H + h) of one view against K boxes at once.  boxes [K, 16]: T_OC rows 0..2 |
+    extent / 2 | unused (map_view.view_box_record).  -> (seg_off int64 [K + 1] on the device, the same as a list, the
+    workspace view_rays_emit needs); an object with at most one hit has an empty segment.  Synchronises once: seg_off is
+    read back, so that the outputs of M = seg[-1] entries can be allocated to their exact size."""
+    T_WC, boxes, dirs_C = _view_inputs(T_WC, boxes, dirs_C, "view_rays_count")
+    P, K, dev = int(dirs_C.shape[0]), int(boxes.shape[0]), dirs_C.device
+    nbytes = int(lib().objnerf_view_rays_workspace_bytes(P, K))
+    if nbytes == 0:
+        raise _lib.ObjnerfError(f"view_rays_count: P = {P}, K = {K} outside the supported range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    seg_off = torch.empty(K + 1, dtype=torch.int64, device=dev)
+    check(lib().objnerf_view_rays_count(P, K, _ptr(T_WC), _ptr(boxes), _ptr(dirs_C), _ptr(ws), nbytes, _ptr(seg_off),
+                                        _stream()), "objnerf_view_rays_count")
+    return seg_off, [int(x) for x in seg_off.tolist()], ws                  # the one host sync
+
+
+def view_rays_emit(T_WC: torch.Tensor, boxes: torch.Tensor, dirs_C: torch.Tensor, ws: torch.Tensor, M: int):
+    """After view_rays_count on the same inputs -> (pix int32 [M], dirs_W [M, 3], near [M], far [M]): object-major,
+    ascending in the pixel inside an object; per entry the numbers ops.box_rays gives that (pixel, box)."""
+    T_WC, boxes, dirs_C = _view_inputs(T_WC, boxes, dirs_C, "view_rays_emit")
+    M = int(M)
+    if M > VIEW_MAX_ENTRIES:
+        raise _lib.ObjnerfError(f"view_rays_emit: {M} (pixel, object) entries do not fit 32 bits")
+    dev = dirs_C.device
+    pix = torch.empty(M, dtype=torch.int32, device=dev)
+    dirs_W, near, far = torch.empty(M, 3, device=dev), torch.empty(M, device=dev), torch.empty(M, device=dev)
+    p = (lambda t: _ptr(t) if M else None)
+    check(lib().objnerf_view_rays_emit(int(dirs_C.shape[0]), int(boxes.shape[0]), _ptr(T_WC), _ptr(boxes), _ptr(dirs_C),
+                                       _ptr(ws), int(ws.numel()), M, p(pix), p(dirs_W), p(near), p(far), _stream()),
+          "objnerf_view_rays_emit")
+    return pix, dirs_W, near, far
+
+
+def render_tiles(rows, tile_groups: int = VIEW_TILE_GROUPS) -> np.ndarray:
+    """The work list of render_fwd_segmented.  rows: (arena row, rays of its segment) in the order to render.  -> int32
+    [T, 3]: arena row, first 16-ray group counted from the segment's start, groups (<= tile_groups).  Every group of
+    every segment is in exactly one tile, a tile belongs to one row, the tiles of a row are adjacent and ascending; an
+    empty segment has no tile."""
+    tile_groups = int(tile_groups)
+    if tile_groups < 1:
+        raise ValueError(f"render_tiles: tile_groups = {tile_groups}")
+    parts = []
+    for row, n in rows:
+        groups = (int(n) + 15) // 16
+        if groups <= 0:
+            continue
+        first = np.arange(0, groups, tile_groups, dtype=np.int64)
+        t = np.empty((first.shape[0], 3), np.int64)
+        t[:, 0], t[:, 1], t[:, 2] = int(row), first, np.minimum(tile_groups, groups - first)
+        parts.append(t)
+    if not parts:
+        return np.zeros((0, 3), np.int32)
+    tiles = np.concatenate(parts)
+    if tiles.max() >= 2 ** 31:
+        raise _lib.ObjnerfError("render_tiles: a tile field does not fit 32 bits")
+    return tiles.astype(np.int32)
+
+
+def render_fwd_segmented(arena: ParamArena, origin: torch.Tensor, dirs_W: torch.Tensor, near: torch.Tensor,
+                         far: torch.Tensor, rows, u: Optional[torch.Tensor] = None, n_bins: int = 150,
+                         seed: Optional[int] = None, out=None, _workgroups: int = 0):
+    """ops.render_fwd (fp32, no feature hidden) over the segments of several hidden-32 objects in ONE launch
+    (objnerf_render_fwd_segmented).  arena: the stacked arena of those objects; dirs_W [M, 3], near, far [M]: the CSR of
+    view_rays_emit; rows: per object to render (arena row, seg_lo, seg_hi, u_lo, draw) -- its entries of the CSR, the row
+    of u [*, n_bins] its first ray reads (None or < 0: drawn in the kernel under (seed, draw)), the Philox draw counter.
+    -> dict(depth [M], opacity [M], rgb [M, 3]) (`out`: write into these); entries outside the rows' segments are left
+    as they are.  Per entry bit-equal to ops.render_fwd on the object's own rays.  _workgroups: internal, the number of
+    persistent workgroups (0: two per compute unit)."""
+    if arena.net.hidden != 32:
+        raise ObjnerfError("render_fwd_segmented: a stacked arena of hidden-32 objects")
+    dirs_W = _req(dirs_W, torch.float32, "dirs_W")
+    near, far = _req(near, torch.float32, "near"), _req(far, torch.float32, "far")
+    dev, M = dirs_W.device, int(near.shape[0])
+    if tuple(dirs_W.shape) != (M, 3) or int(far.shape[0]) != M or M > VIEW_MAX_ENTRIES:
+        raise ObjnerfError("render_fwd_segmented: dirs_W [M, 3], near [M], far [M], M < 2^32")
+    u_rows = 0
+    if u is not None:
+        u = _req(u, torch.float32, "u")
+        if u.dim() != 2 or int(u.shape[1]) != int(n_bins):
+            raise ObjnerfError(f"render_fwd_segmented: u [*, {n_bins}], got {tuple(u.shape)}")
+        u_rows = int(u.shape[0])
+    table = np.zeros((arena.K, 4), np.int64)
+    table[:, 2] = -1
+    work = []
+    for row, lo, hi, u_lo, draw in rows:
+        row, lo, hi = int(row), int(lo), int(hi)
+        u_lo = -1 if (u_lo is None or u is None) else int(u_lo)
+        if not (0 <= row < arena.K) or not (0 <= lo <= hi <= M) or (u_lo >= 0 and u_lo + hi - lo > u_rows):
+            raise ObjnerfError(f"render_fwd_segmented: row {row} [{lo}, {hi}) u_lo {u_lo} outside the arena, the CSR or u")
+        table[row] = (lo, hi, u_lo, int(draw) & 0x1FFFFFFF)
+        work.append((row, hi - lo))
+    if len(set(r for r, _ in work)) != len(work):
+        raise ObjnerfError("render_fwd_segmented: an arena row is listed twice")
+    tiles = render_tiles(work)
+    if out is None:
+        out = {"depth": torch.empty(M, device=dev), "opacity": torch.empty(M, device=dev), "rgb": torch.empty(M, 3, device=dev)}
+    for k, shp in (("depth", (M,)), ("opacity", (M,)), ("rgb", (M, 3))):
+        if _req(out[k], torch.float32, f"out {k}") is not out[k] or tuple(out[k].shape) != shp or out[k].device != dev:
+            raise ObjnerfError(f"render_fwd_segmented: out[{k!r}] must be contiguous fp32 {list(shp)}")
+    if tiles.shape[0] == 0 or M == 0:
+        return out
+    origin = origin.to(dev, torch.float32).contiguous()
+    table_d, tiles_d = torch.from_numpy(table).to(dev), torch.from_numpy(tiles).to(dev)
+    net = arena.net.c()
+    check(lib().objnerf_render_fwd_segmented(C.byref(net), arena.K, int(tiles.shape[0]), int(n_bins), M, _ptr(arena.params),
+                                             arena.p_stride, _ptr(arena.scale), _ptr(origin), _ptr(table_d), _ptr(tiles_d),
+                                             _ptr(dirs_W), _ptr(near), _ptr(far), _ptr(u), u_rows, _seed_of(seed),
+                                             _ptr(out["depth"]), _ptr(out["opacity"]), _ptr(out["rgb"]), int(_workgroups),
+                                             _stream()), "objnerf_render_fwd_segmented")
+    return out
+
+
+def view_merge(seg_off: torch.Tensor, pix, depth, opacity, rgb, near, far, info: torch.Tensor, P: int,
+               any_background: Optional[bool] = None):
+    """The z-buffer merge of train.py:581-598 in closed form over the CSR of a view (objnerf_view_merge).  info [K, 2]
+    int32: background flag, the id written into the mask-id image.  -> dict(rgb uint8 [P, 3], maskid int32 [P] (0 =
+    nothing painted), depth [P] (100 = no foreground), winner int32 [P] (the painter's entry, -1 = none)).
+    any_background: whether info flags any object (None: read from info, which synchronises); False skips launch (b)."""
+    seg_off, info = _req(seg_off, torch.int64, "seg_off"), _req(info, torch.int32, "info")
+    K, dev, M, P = int(seg_off.shape[0]) - 1, seg_off.device, int(depth.shape[0]), int(P)
+    if tuple(info.shape) != (K, 2) or M > VIEW_MAX_ENTRIES:
+        raise ObjnerfError("view_merge: info [K, 2], M < 2^32")
+    pix = _req(pix, torch.int32, "pix")
+    depth, opacity, rgb = _req(depth, torch.float32, "depth"), _req(opacity, torch.float32, "opacity"), _req(rgb, torch.float32, "rgb")
+    near, far = _req(near, torch.float32, "near"), _req(far, torch.float32, "far")
+    if any(int(t.shape[0]) != M for t in (pix, opacity, rgb, near, far)) or tuple(rgb.shape) != (M, 3):
+        raise ObjnerfError("view_merge: pix, depth, opacity, near, far [M], rgb [M, 3]")
+    best_fg = torch.empty(P, dtype=torch.int64, device=dev)
+    best_bg = torch.empty(P, dtype=torch.int32, device=dev)
+    out = {"rgb": torch.empty(P, 3, dtype=torch.uint8, device=dev), "maskid": torch.empty(P, dtype=torch.int32, device=dev),
+           "depth": torch.empty(P, device=dev), "winner": torch.empty(P, dtype=torch.int32, device=dev)}
+    if any_background is None:
+        any_background = bool(info[:, 0].any())
+    p = (lambda t: _ptr(t) if M else None)
+    check(lib().objnerf_view_merge(P, K, M, _ptr(seg_off), p(pix), p(depth), p(opacity), p(rgb), p(near), p(far), _ptr(info),
+                                   1 if any_background else 0, _ptr(best_fg), _ptr(best_bg), _ptr(out["rgb"]),
+                                   _ptr(out["maskid"]), _ptr(out["depth"]), _ptr(out["winner"]), _stream()),
+          "objnerf_view_merge")
+    return out
