@@ -971,6 +971,47 @@ int objnerf_view_merge(int64_t P, int32_t K, int64_t M, const int64_t* seg_off, 
                        int32_t any_background, uint64_t* best_fg, uint32_t* best_bg, uint8_t* out_rgb, int32_t* out_maskid,
                        float* out_depth, int32_t* out_winner, void* stream);
 
+/* Part features and open-vocabulary queries in a map view (objnerf_mapview.hip; MapView.query / .features, DESIGN.md
+ * 4.24): sceneObject.render_2D_syn(render_part=True)'s render_partfeat (vmap.py:641-679) for the pixels of a merged view,
+ * without the dense [P][512] image.  Added under ABI 14: the entries below are purely additive.
+ *
+ * objnerf_render_fwd_segmented_feat: objnerf_render_fwd_segmented plus out_hfeat [M][32], the composited feature hidden of
+ * every rendered entry (CSR-aligned; the input of out_clip, model.py:100), bit-equal to objnerf_render_fwd's out_hfeat
+ * per object; the other outputs are bit-equal to objnerf_render_fwd_segmented's.
+ * objnerf_render_fwd_segmented_occupancy: the workgroups of that renderer (with_hfeat 0 / 1) the runtime places on one
+ * compute unit; diagnostic.
+ *
+ * objnerf_view_query: for every painted pixel p (e = winner [p], an entry of object k) the part feature
+ *   F = of_w_k . h_e + of_b_k * opacity [e]       (C channels; vmap.py:678: the linear head after compositing)
+ * and against Q unit-length queries [Q][C]: out_sim [Q][P] = (queries [q] . F) / max(|F|, 1e-8) (objnerf_project's cosine
+ * convention), out_label [P] = the first arg-max over q, out_best [P] = that maximum; any of the three may be NULL, all
+ * three NULL skips the pass (queries may then be NULL; Q is still checked).  A pixel nothing painted, or whose painter no
+ * head serves, gets NaN / -1.  With n_feat > 0: out_feat [n_feat][C] = F of pixel feat_pix [i] (int32), zeros for a pixel
+ * out of [0, P), unpainted or unserved.  heads [K] on the device and heads_host [K], the same records in host memory (the
+ * argument checks read these): per object of_w [C][H], of_b [C], hfeat = the composited hidden rows [n_rows][H] with row
+ * (entry - row0); of_w, of_b and hfeat 16-byte aligned; hfeat NULL = this object serves nothing.  H a multiple of 32,
+ * objects of different H in one call.  Every output location has one writer, the summation order is fixed by the MFMA
+ * sequence: two calls write the same bytes, whatever `workgroups` (0 = four per compute unit) is.
+ * EINVAL: Q < 1, Q > 16, M >= 2^32, an H that is no multiple of 32, a misaligned pointer.  ENOTSUP: an H other than 32,
+ * 64, 128, C not a multiple of 16 or above 1020.  M = 0: only the unpainted fill (and zero rows). */
+typedef struct objnerf_view_head_obj {
+  const float* of_w; const float* of_b; const float* hfeat;
+  int64_t row0, n_rows;
+  int32_t H, reserved;
+} objnerf_view_head_obj;
+int objnerf_render_fwd_segmented_feat(const objnerf_net* net, int32_t n_rows, int64_t n_tiles, int32_t n_bins, int64_t M,
+                                      const float* params, int64_t p_stride, const float* scale, const float* origin,
+                                      const int64_t* rows, const int32_t* tiles, const float* dirs_W, const float* near,
+                                      const float* far, const float* u, int64_t u_rows, uint64_t seed, float* out_depth,
+                                      float* out_opacity, float* out_rgb, float* out_hfeat, int32_t workgroups,
+                                      void* stream);
+int objnerf_render_fwd_segmented_occupancy(int32_t with_hfeat);
+int objnerf_view_query(int64_t P, int32_t K, int64_t M, int32_t C, int32_t Q, const int64_t* seg_off, const int32_t* pix,
+                       const float* opacity, const int32_t* winner, const objnerf_view_head_obj* heads,
+                       const objnerf_view_head_obj* heads_host, const float* queries, float* out_sim, int32_t* out_label,
+                       float* out_best, int64_t n_feat, const int32_t* feat_pix, float* out_feat, int32_t workgroups,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,11 @@ class MapPointsHead(C.Structure):      # ABI 14: objnerf_mappoints_head_obj
                 ("H", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ViewHead(C.Structure):           # ABI 14: objnerf_view_head_obj
+    _fields_ = [("of_w", C.c_void_p), ("of_b", C.c_void_p), ("hfeat", C.c_void_p), ("row0", C.c_int64),
+                ("n_rows", C.c_int64), ("H", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AffinityArgs(C.Structure):
     _fields_ = [("N", C.c_int32), ("F", C.c_int32), ("d_cap", C.c_int32), ("d_clip", C.c_int32),
                 ("w_geo", C.c_double), ("w_cap", C.c_double), ("w_clip", C.c_double), ("w_color", C.c_double),
@@ -342,6 +347,15 @@ SIGNATURES = {
     "objnerf_view_merge": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # part features and queries in a map view: additive, still ABI 14
+    "objnerf_render_fwd_segmented_feat": (C.c_int, [C.POINTER(Net), C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
+                                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "objnerf_render_fwd_segmented_occupancy": (C.c_int, [C.c_int32]),
+    "objnerf_view_query": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1948,14 +1948,16 @@ def render_tiles(rows, tile_groups: int = VIEW_TILE_GROUPS) -> np.ndarray:
 
 def render_fwd_segmented(arena: ParamArena, origin: torch.Tensor, dirs_W: torch.Tensor, near: torch.Tensor,
                          far: torch.Tensor, rows, u: Optional[torch.Tensor] = None, n_bins: int = 150,
-                         seed: Optional[int] = None, out=None, _workgroups: int = 0):
-    """ops.render_fwd (fp32, no feature hidden) over the segments of several hidden-32 objects in ONE launch
-    (objnerf_render_fwd_segmented).  arena: the stacked arena of those objects; dirs_W [M, 3], near, far [M]: the CSR of
+                         seed: Optional[int] = None, out=None, _workgroups: int = 0, want_hfeat: bool = False):
+    """ops.render_fwd (fp32, no feature hidden unless want_hfeat) over the segments of several hidden-32 objects in ONE
+    launch (objnerf_render_fwd_segmented).  arena: the stacked arena of those objects; dirs_W [M, 3], near, far [M]: the CSR of
     view_rays_emit; rows: per object to render (arena row, seg_lo, seg_hi, u_lo, draw) -- its entries of the CSR, the row
     of u [*, n_bins] its first ray reads (None or < 0: drawn in the kernel under (seed, draw)), the Philox draw counter.
     -> dict(depth [M], opacity [M], rgb [M, 3]) (`out`: write into these); entries outside the rows' segments are left
     as they are.  Per entry bit-equal to ops.render_fwd on the object's own rays.  _workgroups: internal, the number of
-    persistent workgroups (0: two per compute unit)."""
+    persistent workgroups (0: two per compute unit).  want_hfeat: also "hfeat" [M, 32], the composited feature hidden
+    (render_fwd's "vals") of every rendered entry, through objnerf_render_fwd_segmented_feat; the other three outputs
+    keep their bits."""
     if arena.net.hidden != 32:
         raise ObjnerfError("render_fwd_segmented: a stacked arena of hidden-32 objects")
     dirs_W = _req(dirs_W, torch.float32, "dirs_W")
@@ -1984,7 +1986,9 @@ def render_fwd_segmented(arena: ParamArena, origin: torch.Tensor, dirs_W: torch.
     tiles = render_tiles(work)
     if out is None:
         out = {"depth": torch.empty(M, device=dev), "opacity": torch.empty(M, device=dev), "rgb": torch.empty(M, 3, device=dev)}
-    for k, shp in (("depth", (M,)), ("opacity", (M,)), ("rgb", (M, 3))):
+    if want_hfeat and "hfeat" not in out:
+        out["hfeat"] = torch.empty(M, 32, device=dev)
+    for k, shp in (("depth", (M,)), ("opacity", (M,)), ("rgb", (M, 3))) + ((("hfeat", (M, 32)),) if want_hfeat else ()):
         if _req(out[k], torch.float32, f"out {k}") is not out[k] or tuple(out[k].shape) != shp or out[k].device != dev:
             raise ObjnerfError(f"render_fwd_segmented: out[{k!r}] must be contiguous fp32 {list(shp)}")
     if tiles.shape[0] == 0 or M == 0:
@@ -1992,6 +1996,14 @@ def render_fwd_segmented(arena: ParamArena, origin: torch.Tensor, dirs_W: torch.
     origin = origin.to(dev, torch.float32).contiguous()
     table_d, tiles_d = torch.from_numpy(table).to(dev), torch.from_numpy(tiles).to(dev)
     net = arena.net.c()
+    if want_hfeat:
+        check(lib().objnerf_render_fwd_segmented_feat(C.byref(net), arena.K, int(tiles.shape[0]), int(n_bins), M,
+                                                      _ptr(arena.params), arena.p_stride, _ptr(arena.scale), _ptr(origin),
+                                                      _ptr(table_d), _ptr(tiles_d), _ptr(dirs_W), _ptr(near), _ptr(far),
+                                                      _ptr(u), u_rows, _seed_of(seed), _ptr(out["depth"]),
+                                                      _ptr(out["opacity"]), _ptr(out["rgb"]), _ptr(out["hfeat"]),
+                                                      int(_workgroups), _stream()), "objnerf_render_fwd_segmented_feat")
+        return out
     check(lib().objnerf_render_fwd_segmented(C.byref(net), arena.K, int(tiles.shape[0]), int(n_bins), M, _ptr(arena.params),
                                              arena.p_stride, _ptr(arena.scale), _ptr(origin), _ptr(table_d), _ptr(tiles_d),
                                              _ptr(dirs_W), _ptr(near), _ptr(far), _ptr(u), u_rows, _seed_of(seed),
@@ -2026,4 +2038,73 @@ def view_merge(seg_off: torch.Tensor, pix, depth, opacity, rgb, near, far, info:
                                    1 if any_background else 0, _ptr(best_fg), _ptr(best_bg), _ptr(out["rgb"]),
                                    _ptr(out["maskid"]), _ptr(out["depth"]), _ptr(out["winner"]), _stream()),
           "objnerf_view_merge")
+    return out
+
+
+VIEW_QUERY_MAX = 16                     # queries per objnerf_view_query launch (one MFMA tile of dot products)
+
+
+def _view_heads(heads, C_: int, dev):
+    """heads: per object (of_w [C, H], of_b [C], hfeat [n_rows, H] | None, row0) -> (the ctypes array, its device copy)."""
+    arr = (_lib.ViewHead * len(heads))()
+    for k, (of_w, of_b, hfeat, row0) in enumerate(heads):
+        of_w, of_b = _req(of_w, torch.float32, f"heads[{k}] of_w"), _req(of_b, torch.float32, f"heads[{k}] of_b")
+        H = int(of_w.shape[1]) if of_w.dim() == 2 else 0
+        if of_w.dim() != 2 or int(of_w.shape[0]) != C_ or tuple(of_b.shape) != (C_,):
+            raise ObjnerfError(f"view_query: heads[{k}]: of_w [{C_}, H], of_b [{C_}]")
+        if hfeat is not None:
+            hfeat = _req(hfeat, torch.float32, f"heads[{k}] hfeat")
+            if hfeat.dim() != 2 or int(hfeat.shape[1]) != H:
+                raise ObjnerfError(f"view_query: heads[{k}]: hfeat [n_rows, {H}], got {tuple(hfeat.shape)}")
+        if of_w.device != dev or of_b.device != dev or (hfeat is not None and hfeat.device != dev):
+            raise ObjnerfError(f"view_query: heads[{k}] is not on {dev}")
+        heads[k] = (of_w, of_b, hfeat, row0)                     # (keeps a contiguous copy alive through the call)
+        arr[k] = _lib.ViewHead(_ptr(of_w), _ptr(of_b), _ptr(hfeat) if hfeat is not None and hfeat.numel() else None,
+                               int(row0), int(hfeat.shape[0]) if hfeat is not None else 0, H, 0)
+    return arr, torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+
+
+def view_query(seg_off: torch.Tensor, pix: torch.Tensor, opacity: torch.Tensor, winner: torch.Tensor, heads,
+               queries: Optional[torch.Tensor] = None, pixels: Optional[torch.Tensor] = None, want_sims: bool = True,
+               want_best: bool = True, _workgroups: int = 0) -> Dict[str, Optional[torch.Tensor]]:
+    """The part feature F = of_w . h + of_b * opacity of the entry that painted each pixel of a merged view, never stored
+    densely (objnerf_view_query).  seg_off [K + 1], pix [M], opacity [M]: the CSR of the view; winner int32 [P] from
+    view_merge; heads: per object (of_w [C, H], of_b [C], hfeat [n_rows, H] | None, row0) -- hfeat row (entry - row0) is
+    the composited feature hidden of that entry, None = the object serves nothing; H a multiple of 32, mixed in one call;
+    the three tensors 16-byte aligned.
+    queries [Q, C], 1 <= Q <= 16, unit length (the caller normalises) -> "sims" [Q, P] (want_sims), "label" int32 [P]
+    (the first arg-max), "best" [P] (want_best); NaN / -1 where nothing painted.
+    pixels int [n] (p = w * H + h) -> "feat" [n, C], the raw F; zeros for a pixel out of range or unpainted."""
+    seg_off, winner = _req(seg_off, torch.int64, "seg_off"), _req(winner.reshape(-1), torch.int32, "winner")
+    pix, opacity = _req(pix, torch.int32, "pix"), _req(opacity, torch.float32, "opacity")
+    K, dev, M, P = int(seg_off.shape[0]) - 1, seg_off.device, int(pix.shape[0]), int(winner.shape[0])
+    heads = list(heads)
+    if len(heads) != K or K < 1 or int(opacity.shape[0]) != M or M > VIEW_MAX_ENTRIES:
+        raise ObjnerfError("view_query: one head per object of seg_off [K + 1]; pix, opacity [M], M < 2^32")
+    if queries is None and pixels is None:
+        raise ObjnerfError("view_query: neither queries nor pixels")
+    Q, C_ = 1, int(heads[0][0].shape[0])
+    out = {"sims": None, "label": None, "best": None, "feat": None}
+    if queries is not None:
+        queries = _req(queries, torch.float32, "queries")
+        if queries.dim() != 2 or int(queries.shape[1]) != C_:
+            raise ObjnerfError(f"view_query: queries [Q, {C_}], got {tuple(queries.shape)}")
+        Q = int(queries.shape[0])               # (the library rejects Q outside 1 .. VIEW_QUERY_MAX)
+        out["label"] = torch.empty(P, dtype=torch.int32, device=dev)
+        out["sims"] = torch.empty(max(Q, 0), P, device=dev) if want_sims else None
+        out["best"] = torch.empty(P, device=dev) if want_best else None
+    n = 0
+    if pixels is not None:
+        if not pixels.is_cuda or pixels.dim() != 1 or pixels.dtype not in (torch.int32, torch.int64):
+            raise ObjnerfError("view_query: pixels: a flat int32 / int64 GPU tensor")
+        # (a pixel index outside int32 is outside [0, P) too: it maps to -1 and gets a zero row)
+        pixels = torch.where((pixels >= 0) & (pixels < P), pixels, torch.full_like(pixels, -1)).to(torch.int32).contiguous()
+        n = int(pixels.shape[0])
+        out["feat"] = torch.empty(n, C_, device=dev)
+    arr, table = _view_heads(heads, C_, dev)
+    p = (lambda t: _ptr(t) if M else None)
+    check(lib().objnerf_view_query(P, K, M, C_, Q, _ptr(seg_off), p(pix), p(opacity), _ptr(winner), _ptr(table),
+                                   C.addressof(arr), _ptr(queries), _ptr(out["sims"]), _ptr(out["label"]), _ptr(out["best"]),
+                                   n, _ptr(pixels) if n else None, _ptr(out["feat"]) if n else None, int(_workgroups),
+                                   _stream()), "objnerf_view_query")
     return out
