@@ -1012,6 +1012,31 @@ int objnerf_view_query(int64_t P, int32_t K, int64_t M, int32_t C, int32_t Q, co
                        float* out_best, int64_t n_feat, const int32_t* feat_pix, float* out_feat, int32_t workgroups,
                        void* stream);
 
+/* The compact exported map (objnerf_partrows.hip; openobj_amd/query.py).  Added under ABI 14: the two
+ * entries below are purely additive, so OBJNERF_ABI_VERSION stays 14.
+ *
+ * The unit part feature of a vertex, f^ = (W h + b) / max(|W h + b|, 1e-8) with h its feature hidden [H] and [W | b] its
+ * object's out_clip head, is linear in the row  r = [h s, s],  s = 1 / max(|W h + b|, 1e-8):  f^ = A r,  A = [W | b]
+ * ([C][H + 1], row-major).
+ *
+ * objnerf_part_rows: hfeat [V][hfeat_stride] (the first H floats of a row), of_w [C][H], of_b [C] -> rows
+ * [V][row_stride_out]: r in the first H + 1 floats, zeros in floats H + 1 .. min(H + 4, row_stride_out) - 1, anything
+ * beyond untouched.  W h + b runs on v_mfma_f32_16x16x4_f32 (the chain of objnerf_view_query), |.|^2 is summed in
+ * registers; the C-wide vector is never written.  |W h + b| = 0 gives s = 1e8 and a finite row (the dense export's
+ * f / |f| is NaN there).  row_stride_out >= H + 1, hfeat_stride >= H; 16-byte aligned pointers and strides that are
+ * multiples of 4 take the 128-bit path, anything else the scalar one (same values).
+ *
+ * objnerf_part_expand: out [n][C] = A rows[index[i]] (index int64 [n] on the device; NULL: n == V, row i), zeros for an
+ * index outside [0, V).  head [C][H + 1].
+ *
+ * Both: V = 0 (n = 0) is a no-op; every output location has one writer and the order of every sum is fixed: two calls
+ * write the same bytes.  ENOTSUP: H not a multiple of 32 in 32 .. 256, C not a multiple of 16 in 16 .. 1024.  EINVAL: a
+ * null pointer, a stride below the row width, n != V without an index. */
+int objnerf_part_rows(int64_t V, int32_t H, int32_t C, const float* hfeat, int64_t hfeat_stride, const float* of_w,
+                      const float* of_b, float* rows, int64_t row_stride_out, void* stream);
+int objnerf_part_expand(int64_t V, int32_t H, int32_t C, const float* rows, int64_t row_stride, const float* head,
+                        int64_t n, const int64_t* index, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

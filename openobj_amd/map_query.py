@@ -2,7 +2,10 @@
 
     python -m openobj_amd.map_query --logdir DIR --mode {rgb,class,instance,partpca,object,part}
         [--clip-query F.npy --sbert-query F.npy --part-query F.npy --top N --color-yaml PATH
-         --dataset Replica|Scannet --scene NAME] --out DIR
+         --dataset Replica|Scannet --scene NAME --compact] --out DIR
+
+--compact reads map_vis_compact.pkl.gz (python -m openobj_amd.map_vis --compact); without the flag the dense
+map_vis.pkl.gz is read if it is there, else the compact file.
 
 Writes one coloured obj_<id>.ply per visible object (uint8 colours round(c * 255)) and query.json (mode, the visible
 ids, the ranked object ids with their similarities, the top-k ids).  --dataset Replica hides the "ceiling" objects as
@@ -23,8 +26,13 @@ NEEDS = {"object": ("clip_query", "sbert_query"), "part": ("clip_query", "sbert_
          "class": ("color_yaml",)}
 
 
+DENSE_FILE, COMPACT_FILE = "map_vis.pkl.gz", "map_vis_compact.pkl.gz"        # (map_vis.py writes them)
+
+
 def _width(all_obj, key):
     for o in all_obj.values():
+        if key == "part_feat" and o.get("part_head") is not None:      # a compact map: the head's C
+            return int(np.shape(o["part_head"])[0])
         f = o.get(key)
         if f is not None and np.size(f):
             return int(np.shape(f)[-1])
@@ -44,6 +52,7 @@ def _parse(argv):
     ap.add_argument("--scene", default="room_0")
     ap.add_argument("--out", required=True)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--compact", action="store_true", help="read map_vis_compact.pkl.gz")
     a = ap.parse_args(argv)
     for k in NEEDS.get(a.mode, ()):
         v = getattr(a, k)
@@ -51,9 +60,13 @@ def _parse(argv):
             ap.error(f"--mode {a.mode} needs --{k.replace('_', '-')}")
         if not os.path.isfile(v):
             ap.error(f"--{k.replace('_', '-')}: no such file {v}")
-    path = os.path.join(a.logdir, "map_vis.pkl.gz")
+    path = os.path.join(a.logdir, COMPACT_FILE if a.compact else DENSE_FILE)
+    if not a.compact and not os.path.isfile(path) and os.path.isfile(os.path.join(a.logdir, COMPACT_FILE)):
+        path = os.path.join(a.logdir, COMPACT_FILE)
     if not os.path.isfile(path):
-        ap.error(f"{path} is missing: run python -m openobj_amd.map_vis --logdir {a.logdir} first")
+        ap.error(f"{path} is missing: run python -m openobj_amd.map_vis --logdir {a.logdir}"
+                 f"{' --compact' if a.compact else ''} first")
+    a.map_file = path
     with gzip.open(path, "rb") as fh:
         all_obj = pickle.load(fh)
     queries = {}

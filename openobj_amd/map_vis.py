@@ -1,7 +1,7 @@
 """Map export for the open-vocabulary viewer: visualization/gen_map_vis.py:82-146 over the checkpoints the mapper writes
 (mapping.py save_checkpoints: <logdir>/ckpt/<obj_id>/obj_<id>.pth).
 
-    python -m openobj_amd.map_vis --logdir DIR [--grid-dim 128] [--device cuda:0]
+    python -m openobj_amd.map_vis --logdir DIR [--grid-dim 128] [--device cuda:0] [--compact]
 
 For every object whose checkpoint carries a box: Trainer.meshing(box, obj_center, grid_dim, save_mesh, if_color,
 if_part) on the GPU, the part feature L2-normalised per vertex, and the reference's per-object dict (clip_feat,
@@ -9,7 +9,13 @@ caption_feat, class_id, mesh, color, part_feat) collected into <logdir>/map_vis.
 <logdir>/map_vis/obj_<id>.ply.  The boxes are the ones the mapper fitted to each object's keyframes before writing the
 checkpoint (sceneObject.get_bound, vmap.py:287-384; `python -m openobj_amd.mapping` does it for every checkpoint).
 Objects whose checkpoint carries no box (too few keyframe points to fit one, as in the reference) are skipped with a
-message, as are objects whose network meshes to nothing."""
+message, as are objects whose network meshes to nothing.
+
+--compact (export(..., compact=True)) writes <logdir>/map_vis_compact.pkl.gz instead: the same dict per object without
+part_feat and with part_rows [V, H+1] fp32 and part_head [C, H+1] fp32 -- the unit part feature of vertex v is
+part_head . part_rows[v]: 33 floats a vertex at hidden 32 instead of 512.  The 512-d feature is never
+formed: Trainer.meshing(part_compact=True).  A vertex whose feature is exactly zero gets a finite row (s = 1e8) there,
+where the dense export's f / |f| is NaN.  The .ply files are the same."""
 from __future__ import annotations
 
 import argparse
@@ -43,7 +49,12 @@ def load_object(ckpt_file: str, device: str):
     return t, ck
 
 
-def export(logdir: str, grid_dim: int = 128, device: str = "cuda:0", obj_center: float = 0.0) -> Optional[Dict]:
+COMPACT_FILE = "map_vis_compact.pkl.gz"
+DENSE_FILE = "map_vis.pkl.gz"
+
+
+def export(logdir: str, grid_dim: int = 128, device: str = "cuda:0", obj_center: float = 0.0,
+           compact: bool = False) -> Optional[Dict]:
     ckpt_dir = os.path.join(logdir, "ckpt")
     ids = sorted(int(d) for d in os.listdir(ckpt_dir) if os.path.isdir(os.path.join(ckpt_dir, d)) and d.isdigit())
     ply_dir = os.path.join(logdir, "map_vis")
@@ -60,24 +71,29 @@ def export(logdir: str, grid_dim: int = 128, device: str = "cuda:0", obj_center:
             print(f"obj {obj_id}: the checkpoint carries no box, skipped")
             continue
         res = t.meshing(box, torch.tensor(obj_center), grid_dim=grid_dim, save_pcd=False, save_mesh=True,
-                        if_color=True, if_part=True)
+                        if_color=True, if_part=True, part_compact=compact)
         if res is None or len(res) != 3 or res[1] is None:
             print(f"obj {obj_id}: no surface, skipped")
             continue
         _, mesh, part_feat = res
-        part_feat = part_feat.cpu().numpy()
-        part_feat = part_feat / np.linalg.norm(part_feat, axis=-1, keepdims=True)       # gen_map_vis.py:121
         all_obj[obj_id] = {
             "clip_feat": ck.get("clip_feat"),
             "caption_feat": ck.get("caption_feat"),
             "class_id": ck.get("semantic_id"),
             "mesh": mesh,
             "color": mesh.visual.vertex_colors,
-            "part_feat": part_feat,
         }
+        if compact:
+            rows, head = part_feat
+            all_obj[obj_id]["part_rows"] = np.ascontiguousarray(rows.cpu().numpy())
+            all_obj[obj_id]["part_head"] = np.ascontiguousarray(head.cpu().numpy())
+        else:
+            part_feat = part_feat.cpu().numpy()
+            part_feat = part_feat / np.linalg.norm(part_feat, axis=-1, keepdims=True)   # gen_map_vis.py:121
+            all_obj[obj_id]["part_feat"] = part_feat
         mesh.export(os.path.join(ply_dir, f"obj_{obj_id}.ply"))
         print(f"obj {obj_id}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces")
-    path = os.path.join(logdir, "map_vis.pkl.gz")
+    path = os.path.join(logdir, COMPACT_FILE if compact else DENSE_FILE)
     with gzip.open(path, "wb") as fh:
         pickle.dump(all_obj, fh)
     print(path)
@@ -89,8 +105,9 @@ def main(argv=None):
     ap.add_argument("--logdir", required=True)
     ap.add_argument("--grid-dim", type=int, default=128)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--compact", action="store_true", help="write map_vis_compact.pkl.gz (rows + head per object)")
     a = ap.parse_args(argv)
-    export(a.logdir, a.grid_dim, a.device)
+    export(a.logdir, a.grid_dim, a.device, compact=a.compact)
 
 
 if __name__ == "__main__":

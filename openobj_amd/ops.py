@@ -1305,6 +1305,54 @@ def vertex_colors(seg_off, mode, V: int, rgb: Optional[torch.Tensor] = None, fac
     return out
 
 
+PART_ROW_PAD = 4                        # row stride of part_rows' buffer = H + 4: rows stay 16-byte aligned
+
+
+def part_rows(hfeat: torch.Tensor, of_w: torch.Tensor, of_b: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """The compact rows of a vertex set (objnerf_part_rows): hfeat [V, H] fp32 (any row stride), of_w [C, H], of_b [C]
+    -> rows [V, H + 1] = [h s, s], s = 1 / max(|of_w h + of_b|, 1e-8): the unit part feature is [of_w | of_b] . row.
+    The result is a view of a [V, H + 4] buffer (`out`, if given, is that buffer): rows stay 16-byte aligned for
+    objnerf_project's float4 path; columns H + 1 .. H + 3 of the buffer are zero."""
+    V, H, rs = _rows(hfeat, "part_rows")
+    dev = hfeat.device
+    of_w, of_b = _req(of_w, torch.float32, "part_rows: of_w"), _req(of_b, torch.float32, "part_rows: of_b")
+    if of_w.dim() != 2 or int(of_w.shape[1]) != H or tuple(of_b.shape) != (int(of_w.shape[0]),):
+        raise ObjnerfError(f"part_rows: of_w [C, {H}], of_b [C], got {tuple(of_w.shape)}, {tuple(of_b.shape)}")
+    if of_w.device != dev or of_b.device != dev:
+        raise ObjnerfError(f"part_rows: the head is not on {dev}")
+    C_ = int(of_w.shape[0])
+    if out is None:
+        out = torch.empty(V, H + PART_ROW_PAD, device=dev)
+    elif (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (V, H + PART_ROW_PAD)
+          or not out.is_contiguous()):
+        raise ObjnerfError(f"part_rows: out must be a contiguous fp32 [{V}, {H + PART_ROW_PAD}] buffer on {dev}")
+    check(lib().objnerf_part_rows(V, H, C_, _ptr(hfeat) if V else None, rs, _ptr(of_w), _ptr(of_b),
+                                  _ptr(out) if V else None, H + PART_ROW_PAD, _stream()), "objnerf_part_rows")
+    return out[:, :H + 1]
+
+
+def part_expand(rows: torch.Tensor, head: torch.Tensor, index: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [n, C] = head . rows[index] (objnerf_part_expand): rows [V, H + 1] fp32 (any row stride), head [C, H + 1],
+    index int64 [n] on the device (None: every row in order); an index outside [0, V) gives a zero row."""
+    V, H1, rs = _rows(rows, "part_expand")
+    dev = rows.device
+    head = _req(head, torch.float32, "part_expand: head")
+    if head.dim() != 2 or int(head.shape[1]) != H1 or head.device != dev:
+        raise ObjnerfError(f"part_expand: head [C, {H1}] on {dev}, got {tuple(head.shape)} on {head.device}")
+    C_ = int(head.shape[0])
+    n = V
+    if index is not None:
+        if not index.is_cuda or index.device != dev or index.dim() != 1 or index.dtype != torch.int64:
+            raise ObjnerfError("part_expand: index: a flat int64 tensor on the rows' device")
+        index = index.contiguous()
+        n = int(index.shape[0])
+    out = torch.empty(n, C_, device=dev)
+    check(lib().objnerf_part_expand(V, H1 - 1, C_, _ptr(rows) if V else None, max(rs, H1), _ptr(head), n,
+                                    _ptr(index) if index is not None and n else None, _ptr(out) if n else None,
+                                    _stream()), "objnerf_part_expand")
+    return out
+
+
 def rainbow_lut() -> np.ndarray:
     """The colour kernel's "rainbow" table [256, 3] fp32 (objnerf_rainbow_lut, host only)."""
     out = np.empty((256, 3), np.float32)

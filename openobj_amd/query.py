@@ -17,6 +17,10 @@ Every colouring returns device colours [V_total, 3] fp32 in that packed order; M
   color_by_rgb / color_by_class / color_by_instance (:263-306)
   hidden_sets            the ceiling / "most" index lists and the axis-aligned boxes (:146-190)
 
+A compact map (map_vis.export(compact=True): part_rows [V, H + 1] and part_head [C, H + 1] per object instead of
+part_feat, the unit feature being part_head . part_rows[v]) is taken the same way and answers
+the same calls from the rows: the 512-d features are never packed.  MapQuery.features(ids) expands single rows.
+
 Departures from the reference: an object whose checkpoint carries no clip or caption feature
 is left out of the ranking (never a top-k object, coloured like a non-selected one) where the reference would raise;
 PCA takes the exact top three eigenvectors with sklearn 1.3.2's u-based sign rule (the reference's sklearn takes the
@@ -138,12 +142,92 @@ def pca_weights(mean: np.ndarray, scatter: np.ndarray, counts: Sequence[int], st
     return W, b
 
 
+def pca_weights_lowrank(mean_r: Sequence[np.ndarray], scatter_r: Sequence[np.ndarray], heads: Sequence[np.ndarray],
+                        counts: Sequence[int], stats: Optional[Dict] = None):
+    """pca_weights for features that are linear in stored rows, X = r A^T (A = heads[s] [C, K], K = H + 1), from the
+    moments of r alone (fp64): per segment, with m = mean_r[s] [K], S = scatter_r[s] [K, K] = sum (r - m)(r - m)^T,
+      std_c = sqrt(a_c^T S a_c / n)  (0 -> 1; a negative rounding residue counts as 0),     D = diag(std)
+      S / n = L L^T  from numpy.linalg.eigh of the K x K matrix (negative eigenvalues clamped to 0),
+      B = D^-1 A L  [C, K]: the correlation matrix of X is B B^T, whose non-zero spectrum is that of B^T B [K, K];
+      (lambda, V) the top three eigenpairs of B^T B,  U = B V / sqrt(lambda)  (unit eigenvectors of B B^T),
+      W = U / std,  P = A^T W [K, 3],  b = -(A m) . W [3]:   scores = X W - (A m) W = r P + b.
+    A component with lambda <= 1e-12 lambda_0 (or lambda_0 = 0) gets zero weights.  Sequences (the segments may have
+    different K) -> (P: list of [K_s, 3], b: [S, 3]); arrays [S, K], [S, K, K], [S, C, K] work as well and then P
+    stacks to [S, K, 3]."""
+    S = len(counts)
+    P, b = [], np.zeros((S, 3))
+    t0 = time.perf_counter()
+    for s in range(S):
+        A = np.asarray(heads[s], np.float64)
+        K = A.shape[1]
+        Ps = np.zeros((K, 3))
+        P.append(Ps)
+        n = int(counts[s])
+        if n == 0:
+            continue
+        Sn = np.asarray(scatter_r[s], np.float64) / n
+        m = np.asarray(mean_r[s], np.float64)
+        std = np.sqrt(np.maximum(np.einsum("ck,kl,cl->c", A, Sn, A), 0.0))
+        std[std == 0.0] = 1.0
+        w, E = np.linalg.eigh(Sn)
+        L = E * np.sqrt(np.maximum(w, 0.0))
+        B = (A @ L) / std[:, None]
+        lam, V = np.linalg.eigh(B.T @ B)
+        lam, V = lam[::-1], V[:, ::-1]
+        k = min(3, K)
+        keep = [j for j in range(k) if lam[0] > 0.0 and lam[j] > 1e-12 * lam[0]]
+        if not keep:
+            continue
+        W = (B @ V[:, keep]) / np.sqrt(lam[keep]) / std[:, None]
+        Ps[:, keep] = A.T @ W
+        b[s, keep] = -(A @ m) @ W
+    if stats is not None:
+        stats["eigh_s"] = time.perf_counter() - t0
+    if len({p.shape for p in P}) == 1 and S:
+        P = np.stack(P)
+    return P, b
+
+
+def compact_layout(all_obj: Dict):
+    """Host-only checks of a map dict -> None for a dense map (every object carries part_feat), else per object
+    (rows [V, H + 1] fp32, head [C, H + 1] fp32) of a compact one.  ValueError: the two kinds mixed, a head that does not
+    match its rows, heads of different C."""
+    kinds = {"part_rows" in o for o in all_obj.values()}
+    if len(kinds) > 1 or any("part_rows" in o and "part_feat" in o for o in all_obj.values()):
+        raise ValueError("MapQuery: the map mixes dense (part_feat) and compact (part_rows) objects")
+    if not kinds or kinds == {False}:
+        return None
+    out, Cs = [], set()
+    for k, o in all_obj.items():
+        if o.get("part_head") is None:
+            raise ValueError(f"MapQuery: object {k} carries part_rows without part_head")
+        rows, head = np.asarray(o["part_rows"], np.float32), np.asarray(o["part_head"], np.float32)
+        if rows.ndim != 2 or head.ndim != 2 or rows.shape[1] != head.shape[1] or rows.shape[1] < 2:
+            raise ValueError(f"MapQuery: object {k}: part_rows {rows.shape} does not match part_head {head.shape}")
+        Cs.add(head.shape[0])
+        out.append((rows, head))
+    if len(Cs) > 1:
+        raise ValueError(f"MapQuery: part heads of different widths {sorted(Cs)}")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ the device side
 class MapQuery:
+    """A dense map (part_feat per object) or a compact one (part_rows + part_head per object): the
+    compact map keeps rows [V, H + 1] with f^ = head . row per vertex, one buffer of row stride H + 4 per contiguous
+    run of objects of equal H, and answers every query from the rows -- a part query is the affine projection of the
+    rows on head^T q^, the PCA colouring needs the moments of the rows and a (H + 1)-wide eigenproblem per object."""
+    compact = None                  # the runs of a compact map (_init_compact); None: a dense map
+
     def __init__(self, all_obj: Dict, device="cuda:0", eps: float = 0.2, min_samples: int = 2):
         self.all_obj = all_obj
         self.keys = list(all_obj.keys())
         self.dev = torch.device(device)
+        layout = compact_layout(all_obj)
+        if layout is not None:
+            self._init_compact(layout)
+            self._init_objects(eps, min_samples)
+            return
         pf = [np.asarray(all_obj[k]["part_feat"]) for k in self.keys]
         widths = {p.shape[1] for p in pf if p.ndim == 2 and len(p)}
         if len(widths) > 1:
@@ -162,6 +246,44 @@ class MapQuery:
             self.part_feat[r0:r1].copy_(torch.from_numpy(np.ascontiguousarray(pf[s], np.float32)))
             c = np.asarray(all_obj[k]["color"], np.uint8).reshape(r1 - r0, -1)
             self.rgb[r0:r1, : c.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(c)))
+        self._init_objects(eps, min_samples)
+
+    def _init_compact(self, layout) -> None:
+        """layout: compact_layout's (rows, head) per object -> self.compact: one record per contiguous run of objects of
+        equal width (s0, s1: the objects; buf [V_run, H + 4] device, zero in the padding; seg: the run's own offsets)."""
+        self.D = int(layout[0][1].shape[0])
+        counts = [len(r) for r, _ in layout]
+        self.seg_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        self.V = int(self.seg_host[-1])
+        self.seg_off = torch.from_numpy(self.seg_host).to(self.dev)
+        self.part_feat = None
+        self.rgb = torch.empty(self.V, 4, dtype=torch.uint8, device=self.dev)
+        self.heads64 = [h.astype(np.float64) for _, h in layout]
+        self.heads = [torch.from_numpy(np.ascontiguousarray(h)).to(self.dev) for _, h in layout]
+        self.compact = []
+        s0 = 0
+        while s0 < self.S:
+            K = layout[s0][1].shape[1]
+            s1 = s0 + 1
+            while s1 < self.S and layout[s1][1].shape[1] == K:
+                s1 += 1
+            r0, r1 = int(self.seg_host[s0]), int(self.seg_host[s1])
+            buf = torch.zeros(r1 - r0, K - 1 + ops.PART_ROW_PAD, device=self.dev)
+            for s in range(s0, s1):
+                a, b = int(self.seg_host[s]) - r0, int(self.seg_host[s + 1]) - r0
+                if b > a:
+                    buf[a:b, :K].copy_(torch.from_numpy(np.ascontiguousarray(layout[s][0])))
+            self.compact.append({"s0": s0, "s1": s1, "K": K, "buf": buf,
+                                 "seg": torch.from_numpy(self.seg_host[s0:s1 + 1] - r0).to(self.dev)})
+            s0 = s1
+        for s, k in enumerate(self.keys):
+            r0, r1 = int(self.seg_host[s]), int(self.seg_host[s + 1])
+            if r1 > r0:
+                c = np.asarray(self.all_obj[k]["color"], np.uint8).reshape(r1 - r0, -1)
+                self.rgb[r0:r1, : c.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(c)))
+
+    def _init_objects(self, eps: float, min_samples: int) -> None:
+        all_obj = self.all_obj
         ranked, clip, cap = reduce_object_features(all_obj, eps, min_samples)
         self.ranked = ranked                     # positions (in the map's order) that take part in the ranking
         self.clip = torch.from_numpy(clip).to(self.dev)
@@ -239,6 +361,8 @@ class MapQuery:
         q = q.reshape(1, -1) if q.dim() == 1 else q
         if q.shape[1] != self.D:
             raise ValueError(f"part query: width {q.shape[1]} does not match the map's {self.D}")
+        if self.compact is not None:
+            return self._part_similarity_compact(q, objects)
         W = q.t().contiguous()
         if objects is None:
             return ops.segment_project(self.part_feat, self.seg_off, W, cosine=True)
@@ -262,7 +386,92 @@ class MapQuery:
         return self._colors(modes, factor=np.full(self.S, DARK), column=np.zeros(self.S, np.int32), proj=proj,
                             minmax=mm)
 
+    # -------------------------------------------------------------------------------------------- the compact map
+    def _columns(self, run, cols) -> torch.Tensor:
+        """cols: per object of the run [K, Q] fp64 -> [n, H + 4, Q] fp32 on the device (zero rows for the padding)."""
+        K, Q = run["K"], cols[0].shape[1]
+        W = np.zeros((len(cols), K - 1 + ops.PART_ROW_PAD, Q), np.float32)
+        for i, c in enumerate(cols):
+            W[i, :K] = c                                              # the one rounding of head^T q^
+        return torch.from_numpy(W).to(self.dev)
+
+    def _part_similarity_compact(self, q: torch.Tensor, objects):
+        qn = q.detach().cpu().numpy().astype(np.float64)
+        qn = qn / np.maximum(np.linalg.norm(qn, axis=1, keepdims=True), 1e-8)       # objnerf_project's convention
+        Q = qn.shape[0]
+        full = objects is None
+        out = torch.empty(self.V, Q, device=self.dev) if full else torch.full((self.V, Q), float("nan"), device=self.dev)
+        mm = torch.empty(self.S, Q, 2, device=self.dev) if full else torch.full((self.S, Q, 2), float("nan"),
+                                                                               device=self.dev)
+        for run in self.compact:
+            s0, s1 = run["s0"], run["s1"]
+            r0 = int(self.seg_host[s0])
+            if full:
+                W = self._columns(run, [self.heads64[s].T @ qn.T for s in range(s0, s1)])
+                _, m = ops.segment_project(run["buf"], run["seg"], W, out=out[r0:int(self.seg_host[s1])])
+                mm[s0:s1] = m
+                continue
+            for p in objects:
+                if not s0 <= p < s1:
+                    continue
+                a, b = int(self.seg_host[p]), int(self.seg_host[p + 1])
+                if b == a:                                            # an empty object: the projection's own answer
+                    mm[p, :, 0], mm[p, :, 1] = float("inf"), float("-inf")
+                    continue
+                W = self._columns(run, [self.heads64[p].T @ qn.T])
+                _, m = ops.segment_project(run["buf"][a - r0:b - r0], torch.tensor([0, b - a]), W, out=out[a:b])
+                mm[p] = m[0]
+        return out, mm
+
+    def _color_by_partfeat_compact(self, stats: Optional[Dict] = None) -> torch.Tensor:
+        proj = torch.empty(self.V, 3, device=self.dev)
+        mm = torch.empty(self.S, 3, 2, device=self.dev)
+        eigh_s = 0.0
+        for run in self.compact:
+            s0, s1, K = run["s0"], run["s1"], run["K"]
+            mean, scatter = ops.segment_moments(run["buf"], run["seg"])
+            st = {}
+            P, b = pca_weights_lowrank(mean[:, :K].cpu().numpy(), scatter[:, :K, :K].cpu().numpy(),
+                                       self.heads64[s0:s1], np.diff(self.seg_host[s0:s1 + 1]), st)
+            eigh_s += st["eigh_s"]
+            _, m = ops.segment_project(run["buf"], run["seg"], self._columns(run, list(P)),
+                                       torch.from_numpy(b).float(),
+                                       out=proj[int(self.seg_host[s0]):int(self.seg_host[s1])])
+            mm[s0:s1] = m
+        if stats is not None:
+            stats["eigh_s"] = eigh_s
+        return self._colors(np.full(self.S, _lib.COLOR_PCA, np.int32), proj=proj, minmax=mm)
+
+    def features(self, vertex_ids) -> torch.Tensor:
+        """The unit part features [n, D] of the vertices vertex_ids (packed map order); a zero row for an id outside
+        [0, V).  The dense map gathers its rows, the compact one expands them (ops.part_expand, per object hit)."""
+        ids = torch.as_tensor(vertex_ids, dtype=torch.int64).reshape(-1).to(self.dev)
+        n = int(ids.numel())
+        out = torch.zeros(n, max(self.D, 1), device=self.dev)
+        ok = (ids >= 0) & (ids < self.V)
+        if n == 0 or not bool(ok.any()):
+            return out
+        if self.compact is None:
+            out[ok] = self.part_feat[ids[ok]]
+            return out
+        seg = torch.bucketize(ids, self.seg_off[1:], right=True)          # the object of every valid id
+        for s in torch.unique(seg[ok]).tolist():
+            sel = torch.nonzero(ok & (seg == s)).reshape(-1)
+            run = next(r for r in self.compact if r["s0"] <= s < r["s1"])
+            a = int(self.seg_host[s]) - int(self.seg_host[run["s0"]])
+            rows = run["buf"][a:a + int(self.seg_host[s + 1] - self.seg_host[s]), :run["K"]]
+            out[sel] = ops.part_expand(rows, self.heads[s], ids[sel] - int(self.seg_host[s]))
+        return out
+
+    def store_bytes(self) -> int:
+        """Device bytes of the packed part features: V x D fp32 (dense), or the padded rows plus the heads (compact)."""
+        if self.compact is None:
+            return int(self.V) * int(self.D) * 4
+        return sum(r["buf"].numel() * 4 for r in self.compact) + sum(h.numel() * 4 for h in self.heads)
+
     def color_by_partfeat(self, stats: Optional[Dict] = None) -> torch.Tensor:
+        if self.compact is not None:
+            return self._color_by_partfeat_compact(stats)
         mean, scatter = ops.segment_moments(self.part_feat, self.seg_off)
         W, b = pca_weights(mean.cpu().numpy(), scatter.cpu().numpy(), np.diff(self.seg_host), stats)
         proj, mm = ops.segment_project(self.part_feat, self.seg_off, torch.from_numpy(W).float(),
@@ -289,4 +498,4 @@ class MapQuery:
 
 
 __all__ = ["MapQuery", "hidden_sets", "instance_palette", "class_colors", "load_color_yaml", "pca_weights",
-           "reduce_object_features", "top_positions"]
+           "pca_weights_lowrank", "compact_layout", "reduce_object_features", "top_positions"]

@@ -53,6 +53,30 @@ class Trainer:
             return None
         return (occ, color, clip)
 
+    def eval_points_compact(self, points, chunk_size=300000):
+        """points [N,3] -> (occupancy [N], color [N,3], rows [N, H+1], head [C, H+1]) or None: eval_points without the
+        C-wide feature.  rows = ops.part_rows of the feature hidden: head . rows[v] is the unit part feature of point v
+        (DESIGN.md 4.25)."""
+        self.arena.scale.fill_(float(self.obj_scale))
+        views = self.arena.views()
+        of_w, of_b = views[16][0].contiguous(), views[17][0].contiguous()
+        H = int(of_w.shape[1])
+        n = int(points.shape[0])
+        buf = torch.empty(n, H + ops.PART_ROW_PAD, device=self.device)
+        occ, color = [], []
+        with torch.no_grad():
+            for k in range(0, n, chunk_size):
+                pts = points[k:k + chunk_size].reshape(1, -1, 3).to(self.device).contiguous()
+                a, c, h, _ = ops.eval_points(self.arena, pts, want_hfeat=True)
+                occ.append(ops.occupancy(a[0]))
+                color.append(c[0])
+                ops.part_rows(h[0], of_w, of_b, out=buf[k:k + chunk_size])
+        occ, color = torch.cat(occ), torch.cat(color)
+        if occ.max() == 0:
+            print("no occ")
+            return None
+        return occ, color, buf[:, :H + 1], torch.cat([of_w, of_b[:, None]], dim=1)
+
     def sample_points_bbox(self, bbox, do_eval=True, draws=None):
         """Points inside a known oriented 3-D box along the rays self.T_WC_gt / self.dirs_C_gt
         (trainer.py:130-198).  bbox: anything with .center [3], .R [3,3], .extent [3] (the reference passes an
@@ -135,12 +159,15 @@ class Trainer:
                 color.append(c[0])
         return torch.cat(occ), torch.cat(color)
 
-    def meshing(self, bound, obj_center, grid_dim=256, save_pcd=True, save_mesh=True, if_color=False, if_part=False):
+    def meshing(self, bound, obj_center, grid_dim=256, save_pcd=True, save_mesh=True, if_color=False, if_part=False,
+                part_compact=False):
         """Trainer.meshing (trainer.py:46-103) with its return shapes: (None, None) when the grid is empty (:63-64),
         None when marching cubes or the vertex re-query fails (:81-84, :95-96), (pcd, None, None) on the save_pcd
         branch (its voxel_down_sample result is discarded there, :70-77), (None, mesh, partfeat) otherwise.
         bound: .center [3], .R [3,3], .extent [3] (an open3d OrientedBoundingBox in the reference).  mesh is a
-        mesh.TriMesh, pcd a mesh.PointCloud; partfeat the [V, 512] device feature of the vertices (if_part)."""
+        mesh.TriMesh, pcd a mesh.PointCloud; partfeat the [V, 512] device feature of the vertices (if_part), or with
+        part_compact the pair (rows [V, H+1], head [C, H+1]) of eval_points_compact: the same mesh and colours without
+        the 512-d feature."""
         occ_range = [-1., 1.]
         range_dist = occ_range[1] - occ_range[0]
         scene_scale_np = np.asarray(bound.extent) / (range_dist * self.bound_extent)        # :51
@@ -172,7 +199,13 @@ class Trainer:
             if if_color or if_part:
                 # the re-query does NOT subtract obj_center (:92), as in the reference
                 vertices_pts = torch.from_numpy(np.array(mesh.vertices)).float().to(self.device)
-                if if_part:
+                if if_part and part_compact:
+                    ret = self.eval_points_compact(vertices_pts)
+                    if ret is None:
+                        return None
+                    _, color, rows, head = ret
+                    partfeat = (rows, head)
+                elif if_part:
                     ret = self.eval_points(vertices_pts)
                     if ret is None:
                         return None

@@ -5,7 +5,14 @@
 At one object (100 k x 512) and at the native map (51 such objects): the projection at Q = 1 and 16 (cosine) against
 6.3 TB/s of HBM, the moments against the 157 TF fp32 MFMA peak (2 V D^2 flop, D(D+1)/2 columns pairs counted once:
 the kernel computes the upper tiles only), the host eigensolve, a whole part query and a whole PCA colouring end to
-end, and the baselines: F.cosine_similarity on the device, sklearn's StandardScaler + PCA(3) per object on the CPU."""
+end, and the baselines: F.cosine_similarity on the device, sklearn's StandardScaler + PCA(3) per object on the CPU.
+
+    python tools/query_bench.py --compact [--out profiles/query_compact_bench.txt] [--reps 20]
+
+The compact map at the native size: a synthetic feature hidden [51 x 100 k, 32] and one head per
+object -> ops.part_rows per object, the stored bytes, the part-query pass at Q = 1 and 16 and the PCA colouring end to
+end over the rows, and the same figures of the dense map of the very same features (ops.part_expand of the rows) from
+the same run."""
 import argparse
 import json
 import os
@@ -100,12 +107,85 @@ def one(S, n, D, reps, dev):
     return r
 
 
+def _bare_query(S, n, D, dev):
+    mq = query.MapQuery.__new__(query.MapQuery)
+    off = torch.arange(S + 1, dtype=torch.int64) * n
+    mq.all_obj, mq.keys, mq.dev, mq.D, mq.V = {}, list(range(S)), torch.device(dev), D, S * n
+    mq.seg_host = off.numpy()
+    mq.seg_off = off.to(dev)
+    mq.rgb = torch.zeros(S * n, 4, dtype=torch.uint8, device=dev)
+    mq.ranked = list(range(S))
+    return mq
+
+
+def compact(S, n, H, D, reps, dev):
+    g = torch.Generator(device=dev).manual_seed(0)
+    V = S * n
+    common = torch.randn(H, device=dev, generator=g)
+    h = (common + 0.5 * torch.randn(V, H, device=dev, generator=g)).abs()
+    heads = torch.randn(S, D, H + 1, device=dev, generator=g) * (2.0 / (D + H)) ** 0.5
+    buf = torch.zeros(V, H + ops.PART_ROW_PAD, device=dev)
+    f = torch.empty(V, D, device=dev)
+    w0, b0 = heads[0, :, :H].contiguous(), heads[0, :, H].contiguous()
+    r = {"S": S, "rows_per_object": n, "H": H, "D": D,
+         "part_rows_per_object_s": timed(lambda: ops.part_rows(h[:n], w0, b0, out=buf[:n]), reps)}
+    r["part_rows_per_object_hbm_fraction"] = n * (2 * H + 4) * 4 / r["part_rows_per_object_s"] / HBM
+    for s in range(S):
+        ops.part_rows(h[s * n:(s + 1) * n], heads[s, :, :H].contiguous(), heads[s, :, H].contiguous(),
+                      out=buf[s * n:(s + 1) * n])
+        f[s * n:(s + 1) * n] = ops.part_expand(buf[s * n:(s + 1) * n, :H + 1], heads[s])
+    del h
+    cm, dm = _bare_query(S, n, D, dev), _bare_query(S, n, D, dev)
+    dm.part_feat = f
+    cm.part_feat = None
+    cm.heads = [heads[s] for s in range(S)]
+    cm.heads64 = [heads[s].cpu().numpy().astype(np.float64) for s in range(S)]
+    cm.compact = [{"s0": 0, "s1": S, "K": H + 1, "buf": buf, "seg": cm.seg_off}]
+    r["store_bytes"] = {"compact": cm.store_bytes(), "dense": dm.store_bytes()}
+    r["store_ratio"] = dm.store_bytes() / cm.store_bytes()
+    for name, mq, row in (("dense", dm, D), ("compact", cm, H + ops.PART_ROW_PAD)):
+        for Q in (1, 16):
+            q = torch.randn(Q, D, device=dev, generator=g)
+            t = timed(lambda: mq.part_similarity(q), reps)
+            r[f"{name}_part_query_q{Q}_s"] = t
+            r[f"{name}_part_query_q{Q}_hbm_fraction"] = (V * row * 4 + V * Q * 4) / t / HBM
+
+        def pca():
+            mq.color_by_partfeat()
+            torch.cuda.synchronize()
+        r[f"{name}_pca_coloring_end_to_end_s"] = timed(pca, 2 if name == "dense" else reps)
+        st = {}
+        mq.color_by_partfeat(st)
+        r[f"{name}_pca_eigh_s"] = st["eigh_s"]
+    for Q in (1, 16):           # the device pass alone: the per-segment columns already formed and uploaded
+        W = cm._columns(cm.compact[0], [np.random.randn(H + 1, Q) for _ in range(S)])
+        t = timed(lambda: ops.segment_project(buf, cm.seg_off, W), reps)
+        r[f"compact_project_q{Q}_s"] = t
+        r[f"compact_project_q{Q}_hbm_fraction"] = (V * (H + ops.PART_ROW_PAD) * 4 + V * Q * 4) / t / HBM
+    for Q in (1, 16):
+        r[f"part_query_q{Q}_speedup"] = r[f"dense_part_query_q{Q}_s"] / r[f"compact_part_query_q{Q}_s"]
+    r["pca_coloring_speedup"] = r["dense_pca_coloring_end_to_end_s"] / r["compact_pca_coloring_end_to_end_s"]
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "query_bench.json"))
-    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=None)
+    ap.add_argument("--compact", action="store_true", help="the compact map against the dense one (DESIGN.md 4.25)")
     a = ap.parse_args()
     dev = "cuda:0"
+    if a.compact:
+        res = {"device": torch.cuda.get_device_name(0), "hbm_peak_Bps": HBM, "reps": a.reps or 20,
+               "native_map": compact(51, 100_000, 32, 512, a.reps or 20, dev)}
+        out = a.out or os.path.join(ROOT, "profiles", "query_compact_bench.txt")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as fh:
+            fh.write("python tools/query_bench.py --compact\n" + json.dumps(res, indent=1) + "\n")
+        print(json.dumps(res, indent=1))
+        return
+    a.out = a.out or os.path.join(ROOT, "profiles", "query_bench.json")
+    a.reps = a.reps or 10
     res = {"device": torch.cuda.get_device_name(0), "hbm_peak_Bps": HBM, "fp32_mfma_peak_flops": F32_MFMA,
            "one_object": one(1, 100_000, 512, a.reps, dev), "native_map": one(51, 100_000, 512, a.reps, dev)}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
