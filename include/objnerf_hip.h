@@ -1037,6 +1037,58 @@ int objnerf_part_rows(int64_t V, int32_t H, int32_t C, const float* hfeat, int64
 int objnerf_part_expand(int64_t V, int32_t H, int32_t C, const float* rows, int64_t row_stride, const float* head,
                         int64_t n, const int64_t* index, float* out, void* stream);
 
+/* Scoring a rendered map view against a frame of the sequence (objnerf_vieweval.hip; openobj_amd/map_view_eval.py,
+ * DESIGN.md 4.26); the reference writes the images (train.py:550-612) and compares nothing.  Added under ABI 14: the entry
+ * below is purely additive, so OBJNERF_ABI_VERSION stays 14.
+ *
+ * objnerf_view_compare: one launch per frame.  Every image is [W][H], w-major (p = w * H + h).
+ *   the rendered view: rgb_r u8 [W][H][3], depth_r f32, id_r i32, painted u8 [W][H] or NULL (= every pixel painted);
+ *   the frame:         rgb_g u8 [W][H][3], depth_g f32 (metres, 0 = invalid), id_g i32;
+ *   lut i32 [n_lut], G: an id i HAS ROW lut[i] iff 0 <= i < n_lut and 0 <= lut[i] < G; otherwise it has no row.
+ * Outputs, all ADDED TO and never cleared (the caller zeroes them once per sequence, or once per frame):
+ *   acc i64 [G + 1][9]: row r < G = the pixels whose id_g has row r, row G = every other pixel (column sums = the whole
+ *   image).  Columns:
+ *     0  pixels                              1  pixels with painted set
+ *     2  sum over the 3 channels of (rgb_r - rgb_g)^2           3  the same over painted pixels only
+ *     4  pixels with depth_g > 0             5  pixels with depth_g > 0 and depth_r < 100 (100: nothing wrote depth)
+ *     6  sum over the pixels of column 5 of (int64) floor(e * 2^20), e = min(fabsf(depth_r - depth_g), 2^22): ONE fp32
+ *        subtraction; the widening to fp64 and the scaling are exact (the clamp keeps an infinite depth_g defined)
+ *     7  interior pixels                     8  sum over interior pixels of q         (both: SSIM below)
+ *   conf i64 [G][G + 1] or NULL: for a pixel whose id_g has row r, column (row of id_r) is incremented, column G if id_r
+ *   has no row -- the table of map_points.confusion (rows = ground truth, last column = prediction outside).
+ *   ssim_map f32 [W][H] or NULL: per pixel the mean over the channels (`value` below, rounded to fp32), NaN outside the
+ *   interior.
+ *
+ * SSIM (Wang et al. 2004: 11 x 11 Gaussian window, sigma 1.5, K1 0.01, K2 0.03, L 255, population covariance, per
+ * channel), scored only where the whole window lies inside the image -- the INTERIOR 5 <= w < W - 5, 5 <= h < H - 5,
+ * empty when W < 11 or H < 11 -- and made exact by integer taps that sum to 2^16:
+ *     t = [67, 498, 2359, 7167, 13960, 17434, 13960, 7167, 2359, 498, 67]
+ * (rint(65536 g) with the centre raised by one).  With x the rendered and y the frame's channel (u8):
+ *   1-D pass:  sum t x, sum t y, sum t x^2, sum t y^2, sum t x y           (<= 65536 * 65025 < 2^32: uint32, exact)
+ *   2-D:       Mx, My, Mxx, Myy, Mxy = sum t (1-D sums) over the other axis (< 2^48: integer, exact)
+ * then ONE fixed sequence of fp64 operations, each rounded on its own (no contraction; C1 = 6.5025, C2 = 58.5225):
+ *   mx = Mx * 2^-32, my = My * 2^-32, exx = Mxx * 2^-32, eyy = Myy * 2^-32, exy = Mxy * 2^-32          (all exact)
+ *   mxmx = mx * mx,  mymy = my * my,  mxmy = mx * my
+ *   vx = exx - mxmx, vy = eyy - mymy, cv = exy - mxmy
+ *   a1 = (2 * mxmy) + C1,  a2 = (2 * cv) + C2,  b1 = (mxmx + mymy) + C1,  b2 = (vx + vy) + C2
+ *   s  = (a1 * a2) / (b1 * b2)
+ *   value = ((s_R + s_G) + s_B) / 3
+ *   q = (int64) floor(value * 2^32)
+ * Identical images give q = 2^32 exactly; an inverted image gives a negative q (floor rounds towards -inf).
+ *
+ * Every accumulated quantity is an integer: the tables do not depend on the order of summation, the grid (`workgroups`,
+ * 0 = the default) or the path -- with G <= OBJNERF_VIEW_EVAL_LDS_ROWS a workgroup reduces into an LDS copy of the
+ * tables and adds one 64-bit atomic per non-zero cell; above it, wave-aggregated global atomics.  Tiles are
+ * OBJNERF_VIEW_EVAL_TILE pixels square.  The inputs are only read.
+ * EINVAL: a null image, lut or acc, W or H < 1, W * H >= 2^31, G < 1 or > OBJNERF_VIEW_EVAL_MAX_ROWS, n_lut < 0. */
+#define OBJNERF_VIEW_EVAL_TILE 32
+#define OBJNERF_VIEW_EVAL_LDS_ROWS 64
+#define OBJNERF_VIEW_EVAL_MAX_ROWS 32767
+int objnerf_view_compare(int32_t W, int32_t H, const uint8_t* rgb_r, const float* depth_r, const int32_t* id_r,
+                         const uint8_t* painted, const uint8_t* rgb_g, const float* depth_g, const int32_t* id_g,
+                         const int32_t* lut, int32_t n_lut, int32_t G, int64_t* acc, int64_t* conf, float* ssim_map,
+                         int32_t workgroups, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

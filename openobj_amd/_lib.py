@@ -361,6 +361,10 @@ SIGNATURES = {
                                     C.c_void_p, C.c_int64, C.c_void_p]),
     "objnerf_part_expand": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    # scoring a rendered view against a frame (objnerf_vieweval.hip): additive, still ABI 14
+    "objnerf_view_compare": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

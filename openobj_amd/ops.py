@@ -2156,3 +2156,48 @@ def view_query(seg_off: torch.Tensor, pix: torch.Tensor, opacity: torch.Tensor, 
                                    n, _ptr(pixels) if n else None, _ptr(out["feat"]) if n else None, int(_workgroups),
                                    _stream()), "objnerf_view_query")
     return out
+
+
+VIEW_EVAL_TILE = 32                     # OBJNERF_VIEW_EVAL_TILE: objnerf_view_compare's tiles are this many pixels square
+VIEW_EVAL_LDS_ROWS = 64                 # OBJNERF_VIEW_EVAL_LDS_ROWS: up to this G the tables are reduced in LDS first
+VIEW_EVAL_MAX_ROWS = 32767
+VIEW_EVAL_COLS = 9
+
+
+def view_compare(rgb_r: torch.Tensor, depth_r: torch.Tensor, id_r: torch.Tensor, painted: Optional[torch.Tensor],
+                 rgb_g: torch.Tensor, depth_g: torch.Tensor, id_g: torch.Tensor, lut: torch.Tensor, G: int,
+                 acc: torch.Tensor, conf: Optional[torch.Tensor] = None, want_ssim_map: bool = False,
+                 _workgroups: int = 0) -> Optional[torch.Tensor]:
+    """One frame of a rendered view against the sequence's frame (objnerf_view_compare; the columns, the exact-integer SSIM
+    and the lut rule stand in include/objnerf_hip.h).  rgb_* uint8 [W, H, 3], depth_* fp32 [W, H], id_* int32 [W, H],
+    painted uint8 / bool [W, H] or None (every pixel painted); lut int32 [n_lut]: id -> row in [0, G), anything else = no
+    row.  acc int64 [G + 1, 9] and conf int64 [G, G + 1] (or None) are ADDED TO, never cleared.  -> ssim_map fp32 [W, H]
+    (NaN outside the interior) with want_ssim_map, else None.  The tables do not depend on _workgroups (0 = default)."""
+    rgb_r, rgb_g = _req(rgb_r, torch.uint8, "rgb_r"), _req(rgb_g, torch.uint8, "rgb_g")
+    if rgb_r.dim() != 3 or int(rgb_r.shape[2]) != 3 or rgb_g.shape != rgb_r.shape:
+        raise ObjnerfError(f"view_compare: rgb_r, rgb_g uint8 [W, H, 3], got {tuple(rgb_r.shape)}, {tuple(rgb_g.shape)}")
+    W, H, dev, G = int(rgb_r.shape[0]), int(rgb_r.shape[1]), rgb_r.device, int(G)
+    depth_r, depth_g = _req(depth_r, torch.float32, "depth_r"), _req(depth_g, torch.float32, "depth_g")
+    id_r, id_g, lut = _req(id_r, torch.int32, "id_r"), _req(id_g, torch.int32, "id_g"), _req(lut, torch.int32, "lut")
+    if painted is not None:
+        if painted.dtype == torch.bool:
+            painted = painted.contiguous().view(torch.uint8)
+        painted = _req(painted, torch.uint8, "painted")
+    for name, t in (("depth_r", depth_r), ("depth_g", depth_g), ("id_r", id_r), ("id_g", id_g), ("painted", painted)):
+        if t is not None and (tuple(t.shape) != (W, H) or t.device != dev):
+            raise ObjnerfError(f"view_compare: {name} [{W}, {H}] on {dev}, got {tuple(t.shape)} on {t.device}")
+    if W < 1 or H < 1 or W * H > 0x7fffffff or not 1 <= G <= VIEW_EVAL_MAX_ROWS or lut.dim() != 1 or lut.device != dev:
+        raise ObjnerfError("view_compare: W, H >= 1, W * H < 2^31, 1 <= G <= 32767, lut int32 [n_lut]")
+    # (the kernel adds into these in place: a copy made by .contiguous() would be lost, so they are checked, not fixed)
+    if not (acc.is_cuda and acc.dtype == torch.int64 and acc.is_contiguous() and tuple(acc.shape) == (G + 1, VIEW_EVAL_COLS)
+            and acc.device == dev):
+        raise ObjnerfError(f"view_compare: acc: a contiguous int64 [{G + 1}, {VIEW_EVAL_COLS}] on {dev}")
+    if conf is not None and not (conf.is_cuda and conf.dtype == torch.int64 and conf.is_contiguous()
+                                 and tuple(conf.shape) == (G, G + 1) and conf.device == dev):
+        raise ObjnerfError(f"view_compare: conf: a contiguous int64 [{G}, {G + 1}] on {dev}")
+    ssim_map = torch.empty(W, H, device=dev) if want_ssim_map else None
+    n_lut = int(lut.shape[0])
+    check(lib().objnerf_view_compare(W, H, _ptr(rgb_r), _ptr(depth_r), _ptr(id_r), _ptr(painted), _ptr(rgb_g), _ptr(depth_g),
+                                     _ptr(id_g), _ptr(lut) if n_lut else None, n_lut, G, _ptr(acc), _ptr(conf),
+                                     _ptr(ssim_map), int(_workgroups), _stream()), "objnerf_view_compare")
+    return ssim_map
