@@ -122,6 +122,36 @@ __device__ __forceinline__ void wg_quarter(f32x4& acc0, const float* dT, const f
   }
 }
 
+// wg_pair over ONE ray of a two-ray tile (S = 64; the other ray gives exact zeros: DESIGN.md 4.1.1), as 32 MFMAs instead of
+// 64 and with the SAME bits.  The fp32 MFMA adds its four k-slots to the accumulator one after the other, lane group 0
+// first, so wg_pair's sum runs over the samples in the order (step 0: 0, 32, 64, 96), (step 1: 1, 33, 65, 97), ...  With ray
+// 1 masked out the slots of groups 2, 3 add +-0 and the chain is 0, 32, 1, 33, 2, 34, ...: the same chain with four live
+// slots per MFMA is step j of lane group g = sample 32 (g & 1) + 2 j + (g >> 1), 16 steps.  (Ray 0 masked out: the same
+// from column 64.)  dT / aT point at &stg[(row0 + c) * LD + 64 h + 32 (g & 1)]: lane groups g and g + 2 read the SAME aligned
+// pair of columns (2 j, 2 j + 1) with one ds_read_b64 per step and operand, and take its first (`odd` false: g < 2) or second
+// element.  Reading the one dword a lane needs instead is a two-way bank conflict on every read: dword reads have 32
+// banks, where lane groups 0 and 1 (32 columns apart) collide; the 8-byte read has 64, the half wave 0..31 covers them
+// once and the half wave 32..63 repeats its addresses (profiles/ray_halves.txt, section 2).
+template <int UNR = 8>
+__device__ __forceinline__ void wg_pair_ray(f32x4& acc0, f32x4& acc1, const float* dT, const float* aT, const bool odd) {
+  if ((OBJ32_ABL) & 8) return;
+  dT = (const float*)__builtin_assume_aligned(dT, 8);
+  aT = (const float*)__builtin_assume_aligned(aT, 8);
+#pragma unroll UNR
+  for (int j = 0; j < 16; ++j) {
+    const f32x2 b2 = *reinterpret_cast<const f32x2*>(aT + 2 * j);
+    const f32x2 a02 = *reinterpret_cast<const f32x2*>(dT + 2 * j);
+    const f32x2 a12 = *reinterpret_cast<const f32x2*>(dT + 16 * STG_LD + 2 * j);
+    const float b = odd ? b2[1] : b2[0];
+    const float a0 = odd ? a02[1] : a02[0];
+    const float a1 = odd ? a12[1] : a12[0];
+    acc0 = OBJ_MFMA(a0, b, acc0);
+    OBJ32_PIN_MFMA();
+    acc1 = OBJ_MFMA(a1, b, acc1);
+    OBJ32_PIN_MFMA();
+  }
+}
+
 // one weight-gradient tile pair -> slab.  col: reference column of this lane's staged input row (>= 0), BIAS_COL
 // (-> b_off) or ZERO_COL (padding: nothing to write)
 __device__ __forceinline__ void wr_pair(float* slab, const f32x4& a0, const f32x4& a1, const int g, const int col,
@@ -208,6 +238,14 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
   // test-hook instantiation, whose outputs cover all rays and which is the control for that claim, and not (yet) with the
   // feature loss, whose instantiations are register-tight.
   constexpr bool SKIP = !FEAT && !MASKS;
+  // S = 64: a tile is two rays, and a weight-gradient round whose other ray is masked out runs over one ray alone, in half
+  // the MFMAs and to the same bits (wg_pair_ray above).  At any other S the tile's rays are spread over the lane groups in
+  // ways only other waves know: the per-tile rule stays there.
+  constexpr bool RAYS = SKIP && SS == 64;
+  // A dead wave's columns of the staging rows are its ray's, which no round of RAYS reads: it stores no zeros there (108
+  // ds_write_b32 per dead wave and tile: 0.05 ms per step, profiles/ray_halves.txt) and the columns keep what an earlier
+  // tile left.
+  constexpr bool DEAD_ZEROS = !RAYS;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
   int lane = tid & 63;
@@ -362,9 +400,12 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     // what this tile may leave out: wave_* for the 16 samples of this wave, tile_* for all of its rays (every wave
     // forms these from the same labels, so they agree).  A ray that does not exist counts as unknown.
     //   wave_dead   only unknown rays: no forward pass, no input gradients; zeros to the wave's columns of the staging rows
+    //               (not with RAYS, where no round reads them)
     //   wave_nocol  no ray of this object: no colour layer (forward, backward), no octaves 4, 5 of the encoding
     //   tile_nocol  round A runs its two mid2 tile pairs only
     //   tile_dead   every wave is dead and no weight-gradient round runs: the tile costs its barriers and the zero stores
+    //   rays_live(col)   RAYS only, instead of the two tile_*: which of the tile's two rays are known (col: are this
+    //               object's); a round runs over both (wg_pair), over one alone (wg_pair_ray) or not at all
     // Every barrier stays outside these branches.  (tile_dead as a `continue` at this point, and dead paths that leave
     // the registers that cross a phase undefined, both made the allocator spill inside the tile loop: 9.4 -> 14.9 ms.)
     // They cross the whole tile.  As booleans each would be a 64-bit lane mask in a scalar register pair; they are packed
@@ -377,9 +418,12 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
       const unsigned long long known = __ballot(nlb0 != 2) | __ballot(nlb1 != 2);
       const unsigned long long own = __ballot(nlb0 == 1) | __ballot(nlb1 == 1);
       bool wd, wn;
+      int rays = 0;                   // bits 4, 5 SET: ray 0, 1 of the tile is NOT known; bits 6, 7 set: it is NOT this object's
+                                      // (rays_live below reads them inverted: is known / is this object's, as DESIGN.md 4.1.1 words it)
       if (SS == 64) {                 // the wave's 16 samples belong to ray w >> 2 of the tile
         wd = !((known >> (w >> 2)) & 1ull);
         wn = !((own >> (w >> 2)) & 1ull);
+        rays = ((~(int)known & 3) << 4) | ((~(int)own & 3) << 6);
       } else {
         const int q_ = slot / S;      // < 128: the lane's ray
         const int l0 = __shfl(nlb0, q_ & 63, 64), l1 = __shfl(nlb1, q_ & 63, 64);
@@ -387,7 +431,7 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         wd = __all(mine == 2);
         wn = __all(mine != 1);
       }
-      pred_bits = __builtin_amdgcn_readfirstlane((wd ? 1 : 0) | (wn ? 2 : 0) | (known == 0ull ? 4 : 0) | (own == 0ull ? 8 : 0));
+      pred_bits = __builtin_amdgcn_readfirstlane((wd ? 1 : 0) | (wn ? 2 : 0) | (known == 0ull ? 4 : 0) | (own == 0ull ? 8 : 0) | rays);
     }
     auto pred = [&](const int bit) -> bool {
       if (!SKIP) return false;
@@ -398,6 +442,21 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     auto wave_nocol = [&]() { return pred(1); };
     auto tile_dead = [&]() { return pred(2); };
     auto tile_nocol = [&]() { return pred(3); };
+    // RAYS: bit h = ray h of the tile gives something other than exact zeros to the weight gradients (it is not label 2) /
+    // to the colour layer's (it is label 1).  tile_dead and tile_nocol are "neither ray"; the rounds below use these instead.
+    auto rays_live = [&](const bool col) -> int {
+      if (!RAYS) return 3;
+      asm volatile("" : "+s"(pred_bits));
+      return (~pred_bits >> (col ? 6 : 4)) & 3;
+    };
+    // one tile pair of a round over the rays `live` names: both, one (the same bits in half the MFMAs), none
+    auto wg_round = [&](f32x4& a0, f32x4& a1, const int live, const int dTr, const int aTr) {
+      if (live == 3) wg_pair<WGU>(a0, a1, lane_rd + dTr * STG_LD, lane_rd + aTr * STG_LD);
+      else if (live) {
+        const float* rp = lane_rd - 64 * (g >> 1) + (live == 2 ? 64 : 0);      // column 64 h + 32 (g & 1)
+        wg_pair_ray<WGU>(a0, a1, rp + dTr * STG_LD, rp + aTr * STG_LD, (g >> 1) != 0);
+      }
+    };
     const int ray0 = tile * TR;
     // ---------------------------------------------------------------- 1. forward
     const int q = slot / S;
@@ -913,8 +972,10 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
       // nothing of this wave's samples enters any result: zeros to its columns of every operand of round A.  (Its
       // activation columns could stay as they are, like the [h4 | x2] columns above; zeros keep the staging area free of
       // anything an earlier tile left.)
-      st_zero<5>(stg_lane, 0);          // [h4 | x2]
-      st_zero<6>(stg_lane, 96);         // h3, d_hc, d_h4
+      if (DEAD_ZEROS) {
+        st_zero<5>(stg_lane, 0);          // [h4 | x2]
+        st_zero<6>(stg_lane, 96);         // h3, d_hc, d_h4
+      }
       d_hc = d_h4 = d_h3 = d_hf = zero32();    // (defined on every path: see the forward pass)
 #pragma unroll
       for (int i = 0; i < 6; ++i) dps[i] = 0.f;
@@ -941,6 +1002,9 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         const int aTr = (w < 4) ? 48 + 16 * t2 : LY::A_H3 + 16 * t2;
         wg_half<WGU>(accA2, lane_rd + dTr * STG_LD, lane_rd + aTr * STG_LD);
       }
+    } else if (RAYS) {
+      // the colour pairs (waves 0..4) need a ray to be this object's, the mid2 pairs (5, 6) to be known
+      if (w < 7) wg_round(accA0, accA1, rays_live(w < 5), (w < 5) ? 128 : 160, (w < 5) ? 16 * w : 96 + 16 * (w - 5));
     } else if (w < 7 && !(tile_nocol() && w < 5) && !tile_dead()) {     // (no ray of this object in the tile: d_hc is all zero)
       const int dTr = (w < 5) ? 128 : 160;
       const int aTr = (w < 5) ? 16 * w : 96 + 16 * (w - 5);
@@ -953,8 +1017,10 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     // ---- phase B: cat layer.  [h2 | x1] rows 0..127, d_h3pre rows 128..
     T32 d_h2, d_h1;
     if (wave_dead()) {
-      st_zero<8>(stg_lane, 0);          // [h2 | x1]
-      st_zero<2>(stg_lane, 128);        // d_h3
+      if (DEAD_ZEROS) {
+        st_zero<8>(stg_lane, 0);          // [h2 | x1]
+        st_zero<2>(stg_lane, 128);        // d_h3
+      }
       d_h2 = d_h1 = zero32();
     } else {
     st_T32(stg_lane, 0, act.h2);
@@ -1003,7 +1069,8 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     TILE_SYNC();
     PT(12);
     phase_lane(5);
-    if (!tile_dead()) wg_pair<WGU>(accB0, accB1, lane_rd + 128 * STG_LD, lane_rd + (16 * w) * STG_LD);
+    if (RAYS) wg_round(accB0, accB1, rays_live(false), 128, 16 * w);
+    else if (!tile_dead()) wg_pair<WGU>(accB0, accB1, lane_rd + 128 * STG_LD, lane_rd + (16 * w) * STG_LD);
     PT(13);
     TILE_SYNC();
     phase_lane(6);
@@ -1011,8 +1078,10 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
     fetch_point(tile + tstep, slot, nx, ny, nz);
     fetch_labels(tile + tstep, nlb0, nlb1);
     if (wave_dead()) {
-      st_zero<2>(stg_lane, 0);          // h1 (x1 stays: zeros since phase B)
-      st_zero<4>(stg_lane, 128);        // d_h1, d_h2
+      if (DEAD_ZEROS) {
+        st_zero<2>(stg_lane, 0);          // h1 (x1 stays: this wave's zeros of phase B)
+        st_zero<4>(stg_lane, 128);        // d_h1, d_h2
+      }
     } else {
     st_T32(stg_lane, 0, act.h1);
     st_T32(stg_lane, 128, d_h1);
@@ -1034,6 +1103,8 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
                  16 * (w & 1));
       // the next tile's forward pass writes its hidden-feature buffer into rows this round is reading
       TILE_SYNC();
+    } else if (RAYS) {
+      wg_round(accC0, accC1, rays_live(false), (w < 6) ? 128 : 160, (w < 6) ? 32 + 16 * w : 16 * (w - 6));
     } else if (!tile_dead()) {
       const int dTr = (w < 6) ? 128 : 160;
       const int aTr = (w < 6) ? 32 + 16 * w : 16 * (w - 6);

@@ -5,7 +5,11 @@ restated on the host, and the time of the step under chosen label mixes (DESIGN.
 Host part (no GPU; tests/test_masked_rays.py holds it against a brute-force restatement):
 
   predicates(labels [K,R], S)   -> wave_dead / wave_nocol [K,NT,8], tile_dead / tile_nocol [K,NT]
-  expected_mfma(labels, S)      -> MFMA instructions (per wave) of one launch with and without the skips
+  expected_mfma(labels, S)      -> MFMA instructions (per wave) of one launch with and without the skips, weight-gradient
+                                   rounds left out per tile (the kernel's rule at S != 64)
+  expected_mfma_rays(labels, S) -> the kernel's count: at S = 64 the rounds are left out per ray (below)
+  wg_column(st, g)              -> staged sample column that weight-gradient MFMA step st reads in lane group g
+  wg_ray_column(j, g, h)        -> the same for step j of the 16 that run over ray h of a two-ray tile alone
 
 A tile is 128 sample slots = 128 // S rays (a slot behind the last ray of the tile, or behind ray R - 1, has no ray and
 counts as label 2); wave w of the eight holds slots 16 w .. 16 w + 15.
@@ -14,6 +18,14 @@ counts as label 2); wave w of the eight holds slots 16 w .. 16 w + 15.
   wave_nocol   every slot of the wave is label 0 or 2     no colour layer, forward or backward
   tile_nocol   every ray of the tile is label 0 or 2      round A runs only the two mid2 tile pairs
   tile_dead    every ray of the tile is label 2           the tile is skipped
+
+At S = 64 a tile is two rays (columns 0..63 and 64..127).  A tile pair is 32 steps x 2 accumulators; step st adds the
+samples of lane groups 0..3 (wg_column) to the accumulator one after the other.  Where only ray h of the tile has
+something to give, the other ray's slots add exact zeros, and the kernel runs the live slots alone, four to an MFMA, in the
+same order (wg_ray_column): 16 steps x 2, the same bits.  Per tile pair:
+
+  colour pairs (round A, waves 0..4)       32 MFMAs per ray that is label 1
+  mid2 pairs (waves 5, 6), rounds B, C     32 MFMAs per ray that is not label 2
 
 MFMAs per wave and tile, from the kernel's source (objnerf_mlp32.h mlp32_trunk, objnerf_train32.hip phases A / B and the
 weight-gradient rounds): forward 184 of which the colour layer 40, input gradients 192 of which 40, weight gradients
@@ -83,6 +95,36 @@ def expected_mfma(labels, S):
     return dict(full=int(full), with_skips=int(chain + rounds), ratio=float(chain + rounds) / float(full))
 
 
+def wg_column(st, g):
+    """Column (sample slot of the tile) of MFMA k-slot (step st of 32, lane group g of 4) in wg_pair / wg_half /
+    wg_quarter of objnerf_train32.hip."""
+    return 32 * g + st
+
+
+def wg_ray_column(j, g, h):
+    """Column of MFMA k-slot (step j of 16, lane group g) in wg_pair_ray over ray h of a two-ray tile."""
+    return 64 * h + 32 * (g & 1) + 2 * j + (g >> 1)
+
+
+def expected_mfma_rays(labels, S):
+    """expected_mfma with the weight-gradient rounds as the kernel runs them: 32 MFMAs per pair and contributing ray of the
+    tile at S = 64, per tile otherwise."""
+    if S != 64:
+        return expected_mfma(labels, S)
+    p = predicates(labels, S)
+    sl = slot_labels(labels, S)
+    K, NT, _ = sl.shape
+    ray = sl[:, :, ::S]                                    # [K, NT, 2]: the label of ray h of the tile (2: no such ray)
+    dead = p["wave_dead"]
+    nocol = p["wave_nocol"] & ~dead
+    per_wave = (~p["wave_nocol"]) * (FWD + DGRAD) + nocol * (FWD - FWD_COL + DGRAD - DGRAD_COL)
+    chain = per_wave.sum()                                 # (a dead tile has only dead waves)
+    half = PAIR // 2
+    rounds = (ray == 1).sum() * half * ROUND_A_COL + (ray != 2).sum() * half * (ROUND_A_MID2 + ROUND_B + ROUND_C)
+    full = K * NT * FULL_PER_TILE
+    return dict(full=int(full), with_skips=int(chain + rounds), ratio=float(chain + rounds) / float(full))
+
+
 MIXES = ("all1", "bench", "all0", "unknown45")
 
 
@@ -136,7 +178,7 @@ def main(argv=None):
             ev.append((e0, e1))
         torch.cuda.synchronize()
         ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
-        m = expected_mfma(lab, S)
+        m = expected_mfma_rays(lab, S)
         lines.append(dict(mix=name, step_ms_median=round(ms[len(ms) // 2], 4), step_ms_min=round(ms[0], 4),
                           step_ms_max=round(ms[-1], 4), mfma_ratio_expected=round(m["ratio"], 4),
                           status=int(ws.status.item())))
