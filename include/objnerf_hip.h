@@ -260,7 +260,7 @@ int objnerf_mlp_backward_ws(const objnerf_net* net, int32_t K, int64_t N, const 
                             size_t workspace_bytes, void* stream);
 
 /* d B [K][21][3] of UniDirsEmbed.B_layer.weight (embedding.py:36-38) from d_emb [K][N][129] and the inputs of
- * objnerf_embed; scratch: K * 64 floats.  (The reference differentiates neither the points nor the scale.) */
+ * objnerf_embed; scratch: K * 64 floats.  (d pts: objnerf_embed_bwd_pts, below.) */
 int objnerf_embed_bwd(const objnerf_net* net, int32_t K, int64_t N, const float* params, int64_t p_stride,
                       const float* scale, const float* pts, const float* d_emb, float* d_B, float* scratch,
                       void* stream);
@@ -1088,6 +1088,56 @@ int objnerf_view_compare(int32_t W, int32_t H, const uint8_t* rgb_r, const float
                          const uint8_t* painted, const uint8_t* rgb_g, const float* depth_g, const int32_t* id_g,
                          const int32_t* lut, int32_t n_lut, int32_t G, int64_t* acc, int64_t* conf, float* ssim_map,
                          int32_t workgroups, void* stream);
+
+/* Field gradients of the finished map: d alpha / d p, the nearest surface and the normal equations of a rigid alignment
+ * (objnerf_mapalign.hip; openobj_amd/map_points.py, openobj_amd/map_align.py).  The reference has no
+ * counterpart: it differentiates a network in its weights only.  Added under ABI 14: the entries below are purely
+ * additive, so OBJNERF_ABI_VERSION stays 14.
+ *
+ * objnerf_mappoints_grad: the arguments of objnerf_mappoints_eval without best, colour and hfeat.  For every pair of the
+ * hidden-32 objects (info as there) pair_alpha [M] = 10 * raw (model.py:88) and pair_grad [M][3] = d alpha / d p in world
+ * units (the 1 / scale of embedding.py:47 included).  One fused launch on the tile walk of objnerf_mappoints_eval: the
+ * density trunk forward, its four ReLU masks kept as bits, the chain backwards through the transposed weight reads.
+ * Octaves 4 and 5 feed colour only and take no part.  A pair's arithmetic does not depend on its tile, its place in the
+ * tile or the segment length: permuting the pairs permutes the outputs bit for bit.  ENOTSUP unless hidden = 32.
+ *
+ * objnerf_embed_bwd_pts: d_pts [K][N][3] of UniDirsEmbed.forward (embedding.py:46-55) from d_emb [K][N][129] and the
+ * inputs of objnerf_embed: all six octaves and the three linear entries, one thread per point, no atomics.  With
+ * objnerf_mlp_backward_ws it differentiates a network of any width in position (the layer-wise, slow path).
+ *
+ * objnerf_mapalign_select: d = alpha / max(|grad|, g_min) per pair, an estimate of the signed distance to the object's
+ * zero level set (positive inside); one 64-bit atomicMin per pair into best [N], WHICH THE CALLER FILLS WITH ALL ONES
+ * before the first select of a cloud.  Key: bits 62..31 the bits of |d| (a non-negative float's bit pattern is
+ * order-preserving), bits 30..0 the pair; equal |d| goes to the lower pair.  A minimum does not depend on arrival order.
+ * Launch it after every pair_alpha / pair_grad of the cloud is written.  g_min > 0.
+ * objnerf_mapalign_resolve: best -> per point out_obj [N] int32 (position in the list, -1 for a point in no box), optional
+ * out_pair [N] int32, out_d [N] (the signed d of the selected pair, +inf without one), out_alpha [N] and out_grad [N][3]
+ * (the selected pair's, 0 without one).  M = 0 is valid (pair_alpha / pair_grad may then be NULL).
+ *
+ * objnerf_mapalign_transform: out [N][3] = float32(R p + t) for pts [N][3] fp32, t_rows = a HOST array of 12 doubles, the
+ * rows of [R | t]; ((r0 x + r1 y) + r2 z) + t in fp64, every operation rounded on its own.
+ *
+ * objnerf_mapalign_accumulate: over the points with out_obj >= 0 and |d| <= tau, everything in fp64 from the fp32 values:
+ * den = max(|grad|, g_min), d = alpha / den, n = grad / den, J = [(q - pivot) x n, n] (q = pts [n]); out [29] (device) =
+ * the 21 upper entries of sum J J^T row by row, the 6 of sum J d, sum d^2, the inlier count.  pivot: a HOST array of 3.
+ * A workgroup owns 1024 consecutive points; its partial sums go to ws (objnerf_mapalign_workspace_bytes(N)) and a second
+ * launch adds them: the order of every sum depends on N alone, two calls write the same bytes.  Nothing is allocated. */
+int objnerf_mappoints_grad(const objnerf_net* net, int32_t K, int64_t N, int64_t M, const float* params, int64_t p_stride,
+                           const float* scale, const float* pts, const float* boxes, const int32_t* info,
+                           const int64_t* seg_off, const int32_t* pair_pt, float* pair_alpha, float* pair_grad,
+                           void* stream);
+int objnerf_embed_bwd_pts(const objnerf_net* net, int32_t K, int64_t N, const float* params, int64_t p_stride,
+                          const float* scale, const float* pts, const float* d_emb, float* d_pts, void* stream);
+int objnerf_mapalign_select(int64_t N, int64_t M, const int32_t* pair_pt, const float* pair_alpha, const float* pair_grad,
+                            float g_min, uint64_t* best, void* stream);
+int objnerf_mapalign_resolve(int64_t N, int32_t K, int64_t M, const uint64_t* best, const int64_t* seg_off,
+                             const float* pair_alpha, const float* pair_grad, float g_min, int32_t* out_obj,
+                             int32_t* out_pair, float* out_d, float* out_alpha, float* out_grad, void* stream);
+int objnerf_mapalign_transform(int64_t N, const float* pts, const double* t_rows, float* out, void* stream);
+size_t objnerf_mapalign_workspace_bytes(int64_t N);
+int objnerf_mapalign_accumulate(int64_t N, const float* pts, const int32_t* obj, const float* alpha, const float* grad,
+                                const double* pivot, double tau, double g_min, void* ws, size_t ws_bytes, double* out,
+                                void* stream);
 
 #ifdef __cplusplus
 }

@@ -365,6 +365,21 @@ SIGNATURES = {
     "objnerf_view_compare": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_void_p]),
+    # field gradients, nearest surface, rigid alignment (objnerf_mapalign.hip): additive, still ABI 14
+    "objnerf_mappoints_grad": (C.c_int, [C.POINTER(Net), C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "objnerf_embed_bwd_pts": (C.c_int, [C.POINTER(Net), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_mapalign_select": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                          C.c_void_p]),
+    "objnerf_mapalign_resolve": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_mapalign_transform": (C.c_int, [C.c_int64, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "objnerf_mapalign_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "objnerf_mapalign_accumulate": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_double), C.c_double, C.c_double, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

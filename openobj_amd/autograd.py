@@ -63,7 +63,7 @@ class MlpFunction(torch.autograd.Function):
 
 class EmbedFunction(torch.autograd.Function):
     """UniDirsEmbed.forward (embedding.py:46-55) of K stacked embeddings: pts [K,N,3] -> [K,N,129]; differentiable
-    w.r.t. B_layer.weight only (the reference never differentiates the sample positions)."""
+    w.r.t. B_layer.weight (objnerf_embed_bwd) and, when they require it, the sample positions (objnerf_embed_bwd_pts)."""
 
     @staticmethod
     def forward(ctx, arena, stacked, pts, B):
@@ -75,9 +75,9 @@ class EmbedFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_emb):
-        if ctx.needs_input_grad[2]:
-            raise NotImplementedError("gradient w.r.t. the sample positions is not part of the training path")
         _check_unmodified(ctx, "EmbedFunction")
         (pts,) = ctx.saved_tensors
-        d_B = ops.embed_backward(ctx.arena, pts, d_emb.contiguous())
-        return None, None, None, (d_B if ctx.stacked else d_B[0])
+        d_emb = d_emb.contiguous()
+        d_pts = ops.embed_backward_pts(ctx.arena, pts, d_emb) if ctx.needs_input_grad[2] else None
+        d_B = ops.embed_backward(ctx.arena, pts, d_emb)
+        return None, None, d_pts, (d_B if ctx.stacked else d_B[0])

@@ -20,6 +20,10 @@ Every object sees only the points inside its box (objnerf_mappoints.hip: count /
 evaluation of the hidden-32 objects, the wider background through objnerf_eval_points_ws, one 64-bit atomicMax per pair,
 and the 512-d head for the winners only) -- against K evaluations of the whole cloud with Trainer.eval_points.
 
+MapPoints.surface and label(want_normal=True) differentiate the map in position (objnerf_mapalign.hip):
+d alpha / d p of every candidate pair, the object whose surface is nearest to a point, the outward normal; map_align.py
+aligns a cloud to the map with them.
+
 The CLI writes labels.npz (obj, obj_id, class_id, alpha and, when asked for, color, part_feat), instances.ply and
 classes.ply (the cloud coloured per instance / per class with query.instance_palette) and, with --gt-class, eval.json
 (per-class IoU, mIoU, accuracy)."""
@@ -37,6 +41,8 @@ import torch
 from . import _lib, mesh, ops, query
 
 DEFAULT_PAIR_BUDGET = 1 << 30          # bytes of per-pair buffers label() keeps alive at once (it halves a chunk that needs more)
+DEFAULT_G_MIN = 1e-3                   # ASSUMED default: the floor of |d alpha / d p| (alpha units per metre) in d = alpha / |grad|
+FIELD_CHUNK = 1 << 18                  # pairs per round of the layer-wise gradient chain of a wide network
 
 
 @dataclass
@@ -63,6 +69,12 @@ def box_record(bbox, obj_center: float = 0.0) -> np.ndarray:
     rec[12:15] = e.astype(np.float32) * np.float32(0.5)
     rec[15] = np.float32(obj_center)
     return rec
+
+
+def outward_normal(grad: torch.Tensor) -> torch.Tensor:
+    """-grad / |grad| (alpha grows into the object), 0 where |grad| = 0."""
+    nrm = grad.norm(dim=-1, keepdim=True)
+    return torch.where(nrm > 0, -grad / nrm.clamp(min=1e-30), torch.zeros_like(grad))
 
 
 def confusion(pred_class: torch.Tensor, gt_class: torch.Tensor, n_classes: int, ignore: int = -1) -> torch.Tensor:
@@ -195,14 +207,40 @@ class MapPoints:
         return cls(objects, device=device, bg_ids=bg_ids, **kw)
 
     # ------------------------------------------------------------------------------------------------------------
-    def _pair_bytes(self, seg: List[int], want_color: bool, want_feat: bool) -> int:
+    def _pair_bytes(self, seg: List[int], want_color: bool, want_feat: bool, want_normal: bool = False) -> int:
         per = 8 + (12 if want_color else 0) + (128 if want_feat else 0)        # pair_pt, alpha | colour | hidden-32 rows
         total = seg[-1] * per
         for k in self.wide:
             total += ops.mappoints_wide_bytes(self.wide_arena[k], seg[k + 1] - seg[k], want_feat)
+        if want_normal:
+            total += self._field_bytes(seg) - 4 * seg[-1]                       # (pair_pt is counted above)
         return total
 
-    def _label_range(self, pts: torch.Tensor, out, lo: int, hi: int, want_color: bool, want_feat: bool, stats=None) -> None:
+    def _field_bytes(self, seg: List[int]) -> int:
+        """pair_pt, pair_alpha, pair_grad, and the layer-wise chain of the widest chunk of a wide segment."""
+        total = seg[-1] * 20
+        wide = [ops.field_grad_layerwise_bytes(self.wide_arena[k], seg[k + 1] - seg[k], FIELD_CHUNK) for k in self.wide]
+        return total + (max(wide) if wide else 0)
+
+    def _pair_field(self, p: torch.Tensor, seg_off: torch.Tensor, seg: List[int], pair_pt: torch.Tensor, stats=None):
+        """pair_alpha [M] and pair_grad [M, 3] = d alpha / d p of every candidate pair: the hidden-32 objects in one fused
+        launch (objnerf_mappoints_grad), a wider network (the hidden-128 background) through the layer-wise chain on its
+        contiguous segment -- the slow path, in chunks of FIELD_CHUNK pairs."""
+        dev, M = p.device, seg[-1]
+        pair_alpha, pair_grad = torch.empty(M, device=dev), torch.empty(M, 3, device=dev)
+        with _Pass(stats, "grad32_ms"):
+            if self.arena is not None and M:
+                ops.mappoints_grad(self.arena, p, self.boxes, self.info, seg_off, pair_pt, pair_alpha, pair_grad)
+        with _Pass(stats, "grad_wide_ms"):
+            for k in self.wide:
+                a, b = seg[k], seg[k + 1]
+                if b > a:
+                    gpts = ops.mappoints_gather(p, pair_pt[a:b], self.objects[k].obj_center)
+                    pair_alpha[a:b], pair_grad[a:b] = ops.field_grad_layerwise(self.wide_arena[k], gpts, FIELD_CHUNK)
+        return pair_alpha, pair_grad
+
+    def _label_range(self, pts: torch.Tensor, out, lo: int, hi: int, want_color: bool, want_feat: bool, stats=None,
+                     want_normal: bool = False) -> None:
         """Points [lo, hi): split in halves while the pair buffers would exceed the budget or the pairs the 31 bits of the
         keys (a point's result does not depend on which other points share its call)."""
         p = pts[lo:hi]
@@ -210,11 +248,11 @@ class MapPoints:
             seg_off, seg, ws = ops.mappoints_count(p, self.boxes)
         # decided on the counts alone, before anything of M entries exists: too many pairs for the keys, or for the budget
         if hi - lo > 1 and (seg[-1] > ops.MAPPOINTS_MAX_PAIRS or
-                            self._pair_bytes(seg, want_color, want_feat) > self.pair_budget_bytes):
+                            self._pair_bytes(seg, want_color, want_feat, want_normal) > self.pair_budget_bytes):
             del ws
             mid = (lo + hi) // 2
-            self._label_range(pts, out, lo, mid, want_color, want_feat, stats)
-            self._label_range(pts, out, mid, hi, want_color, want_feat, stats)
+            self._label_range(pts, out, lo, mid, want_color, want_feat, stats, want_normal)
+            self._label_range(pts, out, mid, hi, want_color, want_feat, stats, want_normal)
             return
         with _Pass(stats, "candidates_ms"):
             pair_pt = ops.mappoints_emit(p, self.boxes, ws, seg[-1])
@@ -241,9 +279,20 @@ class MapPoints:
         if self._keep_pairs:
             self._last_pairs = dict(seg=seg, pair_pt=pair_pt, pair_alpha=pair_alpha)
         with _Pass(stats, "resolve_ms"):
-            obj, alpha, _, color = ops.mappoints_resolve(best, seg_off, pair_color, M)
+            obj, alpha, win, color = ops.mappoints_resolve(best, seg_off, pair_color, M, want_pair=want_normal)
         out["obj"][lo:hi] = obj
         out["alpha"][lo:hi] = alpha
+        if want_normal:
+            # the winner's d alpha / d p: the gradients of every pair (their own alpha buffer: pair_alpha above stays as
+            # it is), read at the winning pair
+            grad = torch.zeros(n, 3, device=dev)
+            if M:
+                _, pair_grad = self._pair_field(p, seg_off, seg, pair_pt, stats)
+                if self._keep_pairs:
+                    self._last_pairs["pair_grad"] = pair_grad
+                    self._last_pairs["out_pair"] = win
+                grad = torch.where((win >= 0)[:, None], pair_grad[win.clamp(min=0).long()], grad)
+            out["grad"][lo:hi] = grad
         if want_color:
             out["color"][lo:hi] = color
         if want_feat and M:
@@ -258,14 +307,17 @@ class MapPoints:
                 ops.mappoints_head(best, seg_off, pair_pt, heads, self.feat_dim, out["part_feat"][lo:hi])
 
     def label(self, points, want_color: bool = False, want_feat: bool = False, normalise_feat: bool = False,
-              chunk: Optional[int] = None, stats: Optional[dict] = None):
+              chunk: Optional[int] = None, stats: Optional[dict] = None, want_normal: bool = False):
         """points [N, 3] -> dict of device tensors: obj int32 [N] (position in the object list, -1 unlabelled), obj_id and
         class_id int64 [N] (-1 unlabelled), alpha fp32 [N], color [N, 3] (want_color), part_feat [N, C] (want_feat; the raw
         out_clip output of the winner, L2-normalised per labelled point with normalise_feat, as map_vis does).
         chunk: points per call (None: the whole cloud); a call whose pair buffers would exceed pair_budget_bytes is halved
         until they fit.  Chunked and unchunked results are bit-equal.
         stats: DIAGNOSTIC, for tools/mappoints_bench.py -- a dict that receives the time of every pass (device events and a
-        synchronise per pass, which a normal call does not pay), the number of pairs and of calls."""
+        synchronise per pass, which a normal call does not pay), the number of pairs and of calls.
+        want_normal: two more outputs -- grad [N, 3], the winner's d alpha / d p, and normal [N, 3] = -grad / |grad| (outward:
+        alpha grows into the object; the sign of ops.marching_cubes); 0 for an unlabelled point or |grad| = 0.  Without the
+        flag the call issues exactly the launches it issued before the flag existed."""
         pts = torch.as_tensor(points)
         if pts.dim() != 2 or pts.shape[1] != 3:
             raise _lib.ObjnerfError(f"MapPoints.label: expected points [N, 3], got {tuple(pts.shape)}")
@@ -278,10 +330,14 @@ class MapPoints:
             out["color"] = torch.empty(N, 3, device=dev)
         if want_feat:
             out["part_feat"] = torch.zeros(N, self.feat_dim, device=dev)
+        if want_normal:
+            out["grad"] = torch.zeros(N, 3, device=dev)
         step = N if chunk is None else int(chunk)
         with torch.no_grad():
             for lo in range(0, N, max(step, 1)):
-                self._label_range(pts, out, lo, min(lo + step, N), want_color, want_feat, stats)
+                self._label_range(pts, out, lo, min(lo + step, N), want_color, want_feat, stats, want_normal)
+            if want_normal:
+                out["normal"] = outward_normal(out["grad"])
             o = out["obj"].long()
             lab = o >= 0
             out["obj_id"] = torch.where(lab, self.obj_ids[o.clamp(min=0)], torch.full_like(o, -1))
@@ -290,6 +346,65 @@ class MapPoints:
                 f = out["part_feat"]
                 nrm = f.norm(dim=-1, keepdim=True)
                 out["part_feat"] = torch.where(lab[:, None], f / nrm.clamp(min=1e-30), f)      # map_vis.py:69; unlabelled rows stay 0
+        return out
+
+    # ------------------------------------------------------------------------------------------------------------
+    def _surface_range(self, pts: torch.Tensor, out, lo: int, hi: int, g_min: float, stats=None) -> None:
+        """Points [lo, hi) of surface(): halved like _label_range while the pair buffers exceed the budget."""
+        p = pts[lo:hi]
+        with _Pass(stats, "candidates_ms"):
+            seg_off, seg, ws = ops.mappoints_count(p, self.boxes)
+        if hi - lo > 1 and (seg[-1] > ops.MAPPOINTS_MAX_PAIRS or self._field_bytes(seg) > self.pair_budget_bytes):
+            del ws
+            mid = (lo + hi) // 2
+            self._surface_range(pts, out, lo, mid, g_min, stats)
+            self._surface_range(pts, out, mid, hi, g_min, stats)
+            return
+        with _Pass(stats, "candidates_ms"):
+            pair_pt = ops.mappoints_emit(p, self.boxes, ws, seg[-1])
+        del ws
+        n, M = hi - lo, seg[-1]
+        if stats is not None:
+            stats["pairs"] = stats.get("pairs", 0) + M
+            stats["pairs32"] = stats.get("pairs32", 0) + sum(seg[k + 1] - seg[k] for k in range(self.K) if k not in self.wide_arena)
+            stats["calls"] = stats.get("calls", 0) + 1
+        pair_alpha, pair_grad = self._pair_field(p, seg_off, seg, pair_pt, stats)
+        best = torch.full((n,), -1, dtype=torch.int64, device=p.device)          # all ones: no pair yet
+        with _Pass(stats, "select_ms"):
+            ops.mapalign_select(n, pair_pt, pair_alpha, pair_grad, g_min, best)
+            obj, pair, d, alpha, grad = ops.mapalign_resolve(best, seg_off, pair_alpha, pair_grad, g_min,
+                                                             want_pair=self._keep_pairs)
+        if self._keep_pairs:
+            self._last_pairs = dict(seg=seg, pair_pt=pair_pt, pair_alpha=pair_alpha, pair_grad=pair_grad, out_pair=pair)
+        out["obj"][lo:hi] = obj
+        out["d"][lo:hi] = d
+        out["alpha"][lo:hi] = alpha
+        out["grad"][lo:hi] = grad
+
+    def surface(self, points, g_min: float = DEFAULT_G_MIN, chunk: Optional[int] = None, stats: Optional[dict] = None):
+        """points [N, 3] -> dict of device tensors: for every point the candidate object whose surface (the zero level set
+        of alpha) is nearest -- obj int32 [N] (position in the list) and obj_id int64 [N]; d [N], the signed distance
+        estimate alpha / max(|grad|, g_min) in metres, positive inside; normal [N, 3] = -grad / |grad| (outward); alpha [N]
+        and grad [N, 3] = d alpha / d p of that object.  A point in no box gets -1 / inf / 0.  The smallest |d| wins, equal
+        |d| goes to the object that comes first in the list.  g_min keeps d finite where the field is flat."""
+        pts = torch.as_tensor(points)
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise _lib.ObjnerfError(f"MapPoints.surface: expected points [N, 3], got {tuple(pts.shape)}")
+        if chunk is not None and int(chunk) < 1:
+            raise _lib.ObjnerfError(f"MapPoints.surface: chunk = {chunk}")
+        if not g_min > 0:
+            raise _lib.ObjnerfError(f"MapPoints.surface: g_min = {g_min}")
+        pts = pts.to(self.device, torch.float32).contiguous()
+        N, dev = int(pts.shape[0]), self.device
+        out = {"obj": torch.empty(N, dtype=torch.int32, device=dev), "d": torch.empty(N, device=dev),
+               "alpha": torch.empty(N, device=dev), "grad": torch.empty(N, 3, device=dev)}
+        step = N if chunk is None else int(chunk)
+        with torch.no_grad():
+            for lo in range(0, N, max(step, 1)):
+                self._surface_range(pts, out, lo, min(lo + step, N), float(g_min), stats)
+            o = out["obj"].long()
+            out["obj_id"] = torch.where(o >= 0, self.obj_ids[o.clamp(min=0)], torch.full_like(o, -1))
+            out["normal"] = outward_normal(out["grad"])
         return out
 
 

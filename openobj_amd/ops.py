@@ -1684,6 +1684,182 @@ def mappoints_head(best, seg_off, pair_pt, heads, feat_dim: int, out_feat) -> No
           "objnerf_mappoints_head")
 
 
+# --------------------------------------------------- field gradients, nearest surface, alignment (objnerf_mapalign.hip)
+MAPALIGN_SUMS = 29            # 21 upper entries of J J^T | 6 of J d | sum d^2 | inliers
+
+
+def _pair_shapes(what: str, pair_pt, pair_alpha, pair_grad) -> int:
+    M = int(pair_pt.shape[0])
+    if pair_pt.dim() != 1 or tuple(pair_alpha.shape) != (M,) or tuple(pair_grad.shape) != (M, 3):
+        raise _lib.ObjnerfError(f"{what}: pair_pt [M], pair_alpha [M], pair_grad [M, 3]; got {tuple(pair_pt.shape)}, "
+                                f"{tuple(pair_alpha.shape)}, {tuple(pair_grad.shape)}")
+    return M
+
+
+def mappoints_grad(arena: ParamArena, pts, boxes, info, seg_off, pair_pt, pair_alpha, pair_grad) -> None:
+    """The ragged fused field gradient of the hidden-32 objects: pair_alpha [M] = 10 * raw and pair_grad [M, 3] =
+    d alpha / d p (world units) for every pair of an object with info [k, 0] >= 0; other pairs are left alone."""
+    pts, boxes = _req(pts, torch.float32, "pts"), _req(boxes, torch.float32, "boxes")
+    info, seg_off = _req(info, torch.int32, "info"), _req(seg_off, torch.int64, "seg_off")
+    pair_pt = _req(pair_pt, torch.int32, "pair_pt")
+    for name, t in (("pair_alpha", pair_alpha), ("pair_grad", pair_grad)):
+        if _req(t, torch.float32, name) is not t:
+            raise _lib.ObjnerfError(f"mappoints_grad: {name} must be contiguous (it is written in place)")
+    K = int(boxes.shape[0])
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] < 1 or tuple(boxes.shape) != (K, 16) or K < 1 or \
+            tuple(info.shape) != (K, 2) or tuple(seg_off.shape) != (K + 1,):
+        raise _lib.ObjnerfError("mappoints_grad: pts [N >= 1, 3], boxes [K >= 1, 16], info [K, 2], seg_off [K + 1]")
+    M = _pair_shapes("mappoints_grad", pair_pt, pair_alpha, pair_grad)
+    net = arena.net.c()
+    check(lib().objnerf_mappoints_grad(C.byref(net), K, int(pts.shape[0]), M, _ptr(arena.params), arena.p_stride,
+                                       _ptr(arena.scale), _ptr(pts), _ptr(boxes), _ptr(info), _ptr(seg_off),
+                                       _ptr(pair_pt) if M else None, _ptr(pair_alpha) if M else None,
+                                       _ptr(pair_grad) if M else None, _stream()), "objnerf_mappoints_grad")
+
+
+def embed_backward_pts(arena: ParamArena, pts: torch.Tensor, d_emb: torch.Tensor) -> torch.Tensor:
+    """Backward of UniDirsEmbed.forward (embedding.py:46-55) w.r.t. the positions: pts [K, N, 3], d_emb [K, N, 129] ->
+    d_pts [K, N, 3]."""
+    pts = _req(pts, torch.float32, "pts")
+    if pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[0] != arena.K or pts.shape[1] < 1:
+        raise _lib.ObjnerfError(f"embed_backward_pts: pts [{arena.K}, N >= 1, 3], got {tuple(pts.shape)}")
+    K, N = int(pts.shape[0]), int(pts.shape[1])
+    E = 3 + N_DIRS * arena.net.n_freqs
+    if d_emb.numel() != K * N * E:
+        raise _lib.ObjnerfError(f"embed_backward_pts: d_emb [{K}, {N}, {E}], got {tuple(d_emb.shape)}")
+    d_emb = _req(d_emb.reshape(K, N, E), torch.float32, "d_emb")
+    d_pts = torch.empty(K, N, 3, device=pts.device)
+    net = arena.net.c()
+    check(lib().objnerf_embed_bwd_pts(C.byref(net), K, N, _ptr(arena.params), arena.p_stride, _ptr(arena.scale), _ptr(pts),
+                                      _ptr(d_emb), _ptr(d_pts), _stream()), "objnerf_embed_bwd_pts")
+    return d_pts
+
+
+def field_grad_layerwise(arena: ParamArena, pts: torch.Tensor, chunk: int = 1 << 18):
+    """alpha [N], d alpha / d p [N, 3] of ONE network of any width at pts [N, 3] (already relative to obj_center) through
+    the layer-wise chain objnerf_embed -> objnerf_mlp_forward_ws / objnerf_mlp_backward_ws (d_alpha = 1, d_color = 0) ->
+    objnerf_embed_bwd_pts, in chunks of `chunk` points.  The slow path: the hidden-32 objects of a map
+    go through mappoints_grad."""
+    pts = _req(pts, torch.float32, "pts")
+    if arena.K != 1 or pts.dim() != 2 or pts.shape[1] != 3:
+        raise _lib.ObjnerfError("field_grad_layerwise: one network, pts [N, 3]")
+    n, dev = int(pts.shape[0]), pts.device
+    alpha, grad = torch.empty(n, device=dev), torch.empty(n, 3, device=dev)
+    for lo in range(0, n, max(int(chunk), 1)):
+        p = pts[lo:lo + chunk].reshape(1, -1, 3)
+        m = int(p.shape[1])
+        emb = embed(arena, p)
+        a, _, _, _ = mlp_forward(arena, emb)
+        _, d_emb = mlp_backward(arena, emb, torch.ones(1, m, device=dev), torch.zeros(1, m, 3, device=dev))
+        alpha[lo:lo + m] = a[0]
+        grad[lo:lo + m] = embed_backward_pts(arena, p, d_emb)[0]
+    return alpha, grad
+
+
+def field_grad_layerwise_bytes(arena: ParamArena, n: int, chunk: int = 1 << 18) -> int:
+    """Device bytes field_grad_layerwise keeps alive for a segment of n pairs, beside the pair buffers."""
+    if n <= 0:
+        return 0
+    m = min(int(n), int(chunk))
+    net = arena.net.c()
+    ws = int(lib().objnerf_mlp_backward_workspace_bytes(C.byref(net), 1, m, 0)) + \
+        int(lib().objnerf_eval_workspace_bytes(C.byref(net), 1, m))
+    return ws + m * 4 * (3 + 2 * 129 + 1 + 3 + 1 + 3 + 3)         # (+ the weight-gradient arena: a constant, not per pair)
+
+
+def mappoints_gather(pts: torch.Tensor, seg_pt: torch.Tensor, obj_center: float) -> torch.Tensor:
+    """pts [seg_pt [i]] - obj_center for a contiguous slice of pair_pt -> [n, 3]."""
+    pts, seg_pt = _req(pts, torch.float32, "pts"), _req(seg_pt, torch.int32, "seg_pt")
+    n = int(seg_pt.shape[0])
+    out = torch.empty(n, 3, device=pts.device)
+    if n:
+        check(lib().objnerf_mappoints_gather(n, _ptr(seg_pt), _ptr(pts), float(obj_center), _ptr(out), _stream()),
+              "objnerf_mappoints_gather")
+    return out
+
+
+def mapalign_select(n_points: int, pair_pt, pair_alpha, pair_grad, g_min: float, best) -> None:
+    """One atomicMin per pair into best [N] (int64 storage of the unsigned keys, filled with -1 = all ones by the caller):
+    bits 62..31 the bits of |alpha / max(|grad|, g_min)|, bits 30..0 the pair."""
+    pair_pt = _req(pair_pt, torch.int32, "pair_pt")
+    pair_alpha, pair_grad = _req(pair_alpha, torch.float32, "pair_alpha"), _req(pair_grad, torch.float32, "pair_grad")
+    if _req(best, torch.int64, "best") is not best or tuple(best.shape) != (int(n_points),) or n_points < 1:
+        raise _lib.ObjnerfError("mapalign_select: best must be a contiguous int64 [N >= 1]")
+    if not g_min > 0:
+        raise _lib.ObjnerfError(f"mapalign_select: g_min = {g_min}")
+    M = _pair_shapes("mapalign_select", pair_pt, pair_alpha, pair_grad)
+    check(lib().objnerf_mapalign_select(int(n_points), M, _ptr(pair_pt) if M else None, _ptr(pair_alpha) if M else None,
+                                        _ptr(pair_grad) if M else None, float(g_min), _ptr(best), _stream()),
+          "objnerf_mapalign_select")
+
+
+def mapalign_key_encode(d_abs: np.ndarray, pair: np.ndarray) -> np.ndarray:
+    """The key objnerf_mapalign_select offers (host side, for tests and tools): uint64."""
+    bits = np.ascontiguousarray(np.abs(d_abs), np.float32).view(np.uint32).astype(np.uint64)
+    return (bits << np.uint64(31)) | np.asarray(pair, np.uint64)
+
+
+def mapalign_key_decode(key: np.ndarray):
+    """-> (|d| fp32, pair int64; -1 for the caller's fill)."""
+    key = np.asarray(key).astype(np.uint64)
+    free = (key >> np.uint64(63)) != 0
+    d = ((key >> np.uint64(31)) & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.float32)
+    pair = (key & np.uint64(0x7FFFFFFF)).astype(np.int64)
+    return np.where(free, np.float32(np.inf), d), np.where(free, -1, pair)
+
+
+def mapalign_resolve(best, seg_off, pair_alpha, pair_grad, g_min: float, want_pair: bool = False):
+    """best [N] -> (obj int32 [N] (-1: in no box), pair int32 [N] | None, d [N] (+inf), alpha [N], grad [N, 3] (0))."""
+    best, seg_off = _req(best, torch.int64, "best"), _req(seg_off, torch.int64, "seg_off")
+    pair_alpha, pair_grad = _req(pair_alpha, torch.float32, "pair_alpha"), _req(pair_grad, torch.float32, "pair_grad")
+    N, K, M, dev = int(best.shape[0]), int(seg_off.shape[0]) - 1, int(pair_alpha.shape[0]), best.device
+    if best.dim() != 1 or N < 1 or K < 1 or tuple(pair_grad.shape) != (M, 3):
+        raise _lib.ObjnerfError("mapalign_resolve: best [N >= 1], seg_off [K + 1], pair_alpha [M], pair_grad [M, 3]")
+    obj = torch.empty(N, dtype=torch.int32, device=dev)
+    pair = torch.empty(N, dtype=torch.int32, device=dev) if want_pair else None
+    d, alpha, grad = torch.empty(N, device=dev), torch.empty(N, device=dev), torch.empty(N, 3, device=dev)
+    check(lib().objnerf_mapalign_resolve(N, K, M, _ptr(best), _ptr(seg_off), _ptr(pair_alpha) if M else None,
+                                         _ptr(pair_grad) if M else None, float(g_min), _ptr(obj), _ptr(pair), _ptr(d),
+                                         _ptr(alpha), _ptr(grad), _stream()), "objnerf_mapalign_resolve")
+    return obj, pair, d, alpha, grad
+
+
+def mapalign_transform(pts: torch.Tensor, T) -> torch.Tensor:
+    """float32(R p + t) for pts [N, 3] fp32 and a 4 x 4 (or 3 x 4) host matrix T, formed in fp64 on the device."""
+    pts = _req(pts, torch.float32, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+        raise _lib.ObjnerfError(f"mapalign_transform: pts [N >= 1, 3], got {tuple(pts.shape)}")
+    rows = np.asarray(T, np.float64)[:3, :4].reshape(-1)
+    if rows.shape != (12,) or not np.isfinite(rows).all():
+        raise _lib.ObjnerfError("mapalign_transform: T must be a finite 4 x 4 matrix")
+    out = torch.empty_like(pts)
+    check(lib().objnerf_mapalign_transform(int(pts.shape[0]), _ptr(pts), (C.c_double * 12)(*rows.tolist()), _ptr(out),
+                                           _stream()), "objnerf_mapalign_transform")
+    return out
+
+
+def mapalign_accumulate(pts, obj, alpha, grad, pivot, tau: float, g_min: float, out=None) -> torch.Tensor:
+    """-> 29 doubles on the device: over the points with obj >= 0 and |d| <= tau the 21 upper entries of sum J J^T, the 6
+    of sum J d, sum d^2 and the inlier count; J = [(q - pivot) x n, n], everything in fp64 from the fp32 values.  The
+    order of every sum depends on N alone."""
+    pts, obj = _req(pts, torch.float32, "pts"), _req(obj, torch.int32, "obj")
+    alpha, grad = _req(alpha, torch.float32, "alpha"), _req(grad, torch.float32, "grad")
+    N, dev = int(pts.shape[0]), pts.device
+    if pts.dim() != 2 or pts.shape[1] != 3 or N < 1 or tuple(obj.shape) != (N,) or tuple(alpha.shape) != (N,) or \
+            tuple(grad.shape) != (N, 3):
+        raise _lib.ObjnerfError("mapalign_accumulate: pts [N >= 1, 3], obj [N], alpha [N], grad [N, 3]")
+    if not (g_min > 0 and tau >= 0):
+        raise _lib.ObjnerfError(f"mapalign_accumulate: tau = {tau}, g_min = {g_min}")
+    piv = (C.c_double * 3)(*[float(x) for x in pivot])
+    nbytes = int(lib().objnerf_mapalign_workspace_bytes(N))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(MAPALIGN_SUMS, dtype=torch.float64, device=dev)
+    check(lib().objnerf_mapalign_accumulate(N, _ptr(pts), _ptr(obj), _ptr(alpha), _ptr(grad), piv, float(tau), float(g_min),
+                                            _ptr(ws), nbytes, _ptr(out), _stream()), "objnerf_mapalign_accumulate")
+    return out
+
+
 # ------------------------------------------------------------------------- geometry evaluation (objnerf_mapeval.hip)
 NEAREST_CELL_FACTOR = 1.0       # cell side = this x the typical sample spacing (profiles/mapeval_bench.txt)
 _MESH_STATUS = ((1, "a face names a vertex outside [0, V)"), (2, "a face has a non-finite area"),

@@ -53,6 +53,26 @@ class Trainer:
             return None
         return (occ, color, clip)
 
+    def eval_grad(self, points, chunk_size=1 << 18):
+        """points [N,3] -> (alpha [N] = 10 * raw of model.py:88, grad [N,3] = d alpha / d points), on the device.  Hidden
+        32: the fused kernel of MapPoints (ops.mappoints_grad) over the trivial one-segment list; wider networks: the
+        layer-wise chain (ops.field_grad_layerwise) in chunks.  The reference has no counterpart."""
+        self.arena.scale.fill_(float(self.obj_scale))
+        pts = torch.as_tensor(points).reshape(-1, 3).to(self.device, torch.float32).contiguous()
+        n, dev = int(pts.shape[0]), pts.device
+        if n == 0:
+            return torch.empty(0, device=dev), torch.empty(0, 3, device=dev)
+        with torch.no_grad():
+            if self.hidden_feature_size != 32:
+                return ops.field_grad_layerwise(self.arena, pts, chunk_size)
+            boxes = torch.zeros(1, 16, device=dev)                 # never tested here: every point is a pair
+            info = torch.zeros(1, 2, dtype=torch.int32, device=dev)
+            seg_off = torch.tensor([0, n], dtype=torch.int64, device=dev)
+            pair_pt = torch.arange(n, dtype=torch.int32, device=dev)
+            alpha, grad = torch.empty(n, device=dev), torch.empty(n, 3, device=dev)
+            ops.mappoints_grad(self.arena, pts, boxes, info, seg_off, pair_pt, alpha, grad)
+        return alpha, grad
+
     def eval_points_compact(self, points, chunk_size=300000):
         """points [N,3] -> (occupancy [N], color [N,3], rows [N, H+1], head [C, H+1]) or None: eval_points without the
         C-wide feature.  rows = ops.part_rows of the feature hidden: head . rows[v] is the unit part feature of point v
