@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "objnerf_segments.h"       // seg_of: the segment of a row
 
 namespace {
 
@@ -12,16 +13,6 @@ constexpr int64_t CELL_MAX = (1ll << CELL_BITS) - 1;
 
 __device__ __forceinline__ int64_t cell_key(const int64_t x, const int64_t y, const int64_t z) {
   return (x << (2 * CELL_BITS)) | (y << CELL_BITS) | z;
-}
-
-// the segment of row i: the largest s with off[s] <= i (off[0] = 0 <= i < off[S]; empty segments are stepped over)
-__device__ __forceinline__ int seg_of(const int64_t* __restrict__ off, const int S, const int64_t i) {
-  int lo = 0, hi = S;
-  while (hi - lo > 1) {
-    const int m = (lo + hi) >> 1;
-    if (off[m] <= i) lo = m; else hi = m;
-  }
-  return lo;
 }
 
 __device__ __forceinline__ int64_t lower_bound(const int64_t* __restrict__ keys, int64_t lo, int64_t hi, const int64_t k) {

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <mutex>
 // Kernel attributes (the opt-in to more than 64 KB of dynamic LDS) belong to a device: set them once per device of
 // this process, thread-safely.  (Every lambda has its own type, hence every call site its own set of flags.)
@@ -13,6 +14,19 @@ inline void objnerf_once_per_device(F&& fn) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   std::call_once(flags[dev & 63], fn);
+}
+// The compute units of the CURRENT device, asked once per device (256 where the runtime does not say).  It sizes
+// grids, never a result: a kernel launched on it gives the same output on any number of workgroups.
+inline int objnerf_num_cu() {
+  static std::atomic<int> cached[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 256;
+  const int have = dev < 64 ? cached[dev].load(std::memory_order_relaxed) : 0;
+  if (have > 0) return have;
+  int n = 0;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 256;
+  if (dev < 64) cached[dev].store(n, std::memory_order_relaxed);
+  return n;
 }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -2,8 +2,8 @@
 // surface is nearest to a point, and the normal equations of a rigid alignment of a cloud to the map.
 // The reference has no counterpart: it never differentiates a network in position.
 //
-//   mp_grad_kernel        the walk of mp_eval_kernel (objnerf_mappoints.hip): a flat list of (object, 64-pair tile), one
-//       contiguous share per workgroup, stage_weights32 only where the object changes.  Per tile the density trunk runs
+//   mp_grad_kernel        over the candidate pairs of the hidden-32 objects (seg_walk, objnerf_segments.h), without the
+//       feature layer in the image.  Per tile the density trunk runs
 //       forward (mlp32_forward_density), the four ReLU masks are kept as 32 bits per lane, and the chain runs backwards
 //       through the transposed operand reads (mma_t32 / mma_t16): seed 10 w_alpha masked by h4 > 0, mid2^T, cat^T (d h2
 //       and the cat layer's d x1), mid1^T, in^T (added to d x1); pe32_x1_tile_fb leaves the projection gradient d p_j in
@@ -22,31 +22,19 @@
 //   accumulate_kernel / reduce_kernel   J = [(q - pivot) x n, n], n = grad / max(|grad|, g_min), in fp64: the 21 upper
 //       entries of J J^T, the 6 of J d, sum d^2 and the inlier count.  A workgroup owns 1024 consecutive points whatever
 //       the device; its partial sums go to the caller's workspace and one workgroup adds them in an order fixed by N.
-#include "objnerf_mlp32.h"
-#include "objnerf_wg.h"
-#include <atomic>
+#include "objnerf_segments.h"
 
 using namespace obj32;
 
 namespace {
 
-constexpr int MA_BOX = 16;            // floats per box record (objnerf_mappoints.hip)
 constexpr int MA_SUMS = 29;           // 21 + 6 + 1 + 1
 constexpr int MA_WG = 256;
 constexpr int MA_PER = 4;             // points per thread of accumulate_kernel
-constexpr unsigned long long MA_LOW = 0x7FFFFFFFull;
 
-struct MaGrad {
-  int K;
-  const float* params; long p_stride; const float* scale;
-  const float* pts; const float* boxes; const int32_t* info;
-  const int64_t* seg_off; const int32_t* pair_pt;
+struct MaGrad : SegWalkArgs {
   float* pair_alpha; float* pair_grad;
-  Layout L;
 };
-__device__ __forceinline__ long ma_tiles(const MaGrad& a, const int k) {
-  return a.info[2 * k] >= 0 ? (long)((a.seg_off[k + 1] - a.seg_off[k] + 63) >> 6) : 0L;
-}
 // the ReLU branch bits of one layer: bit 4 tt + r of the byte <-> feature 16 tt + 4 g + r
 __device__ __forceinline__ unsigned relu_bits(const T32& h) {
   unsigned b = 0;
@@ -65,41 +53,15 @@ __device__ __forceinline__ T32 mask_bits(const T32& d, const unsigned bits) {
   return o;
 }
 
-// 4 independent waves per workgroup, 16 pairs per wave per tile
 __global__ __launch_bounds__(256) void mp_grad_kernel(const MaGrad a) {
   using namespace obj32n;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, g = lane >> 4;
-  long T = 0;
-  for (int k = 0; k < a.K; ++k) T += ma_tiles(a, k);
-  const long t0 = T * (long)blockIdx.x / (long)gridDim.x, t1 = T * ((long)blockIdx.x + 1) / (long)gridDim.x;
-  if (t0 >= t1) return;                                 // (uniform over the workgroup)
-  int k = 0;
-  long kt0 = 0, kt1 = ma_tiles(a, 0);                   // object k owns tiles [kt0, kt1)
-  int staged = -1;
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   const float* sv = lds + sv_base(false);
   const float* wf = (const float*)__builtin_assume_aligned(lds + 4 * g * WROW + out_pos(c), 8);
   const float* wt0 = (const float*)__builtin_assume_aligned(lds + c * WROW + 8 * g + 4 * (g & 1), 16);
   const float* wt1 = (const float*)__builtin_assume_aligned(lds + c * WROW + 8 * g + 4 * (1 - (g & 1)), 16);
-  float scale = 1.0f, oc = 0.0f;
-  int64_t s0 = 0, s1 = 0;
-  for (long t = t0; t < t1; ++t) {
-    while (t >= kt1) { ++k; kt0 = kt1; kt1 += ma_tiles(a, k); }      // k < K: t < T
-    if (staged != k) {
-      __syncthreads();                                  // every wave is done with the image of the object before
-      const int row = a.info[2 * k];
-      stage_weights32(lds, a.params + (long)row * a.p_stride, a.L, false, tid, 256);
-      scale = a.scale[row];
-      oc = a.boxes[(long)k * MA_BOX + 15];
-      s0 = a.seg_off[k]; s1 = a.seg_off[k + 1];
-      staged = k;
-    }
-    asm volatile("" ::: "memory");   // keep the LDS weight reads inside the loop (no LICM into registers)
-    const int64_t m = s0 + (t - kt0) * 64 + 16 * w + c;
-    const bool valid = m < s1;
-    const int64_t n = a.pair_pt[valid ? m : s0];
+  seg_walk<false>(a, lds, [&](const int64_t m, const bool valid, const int64_t n, const float scale, const float oc, int) {
     const float* p = a.pts + n * 3;
     Pe32 pe;
     pe32_project(sv, g, p[0] - oc, p[1] - oc, p[2] - oc, scale, pe);
@@ -155,7 +117,7 @@ __global__ __launch_bounds__(256) void mp_grad_kernel(const MaGrad a) {
       if (g == 0) a.pair_alpha[m] = alpha;
       else a.pair_grad[m * 3 + g - 1] = ((g == 1) ? gt[0] : ((g == 2) ? gt[1] : gt[2])) / scale;      // embedding.py:47
     }
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------- embedding, d / d pts
@@ -207,14 +169,6 @@ __global__ void __launch_bounds__(256) select_kernel(const int64_t M, const int6
   const float d = fabsf(pair_alpha[m] / fmaxf(gn, g_min));
   atomicMin(best + n, ((unsigned long long)__float_as_uint(d) << 31) | (unsigned long long)m);
 }
-__device__ __forceinline__ int ma_seg_of(const int K, const int64_t* __restrict__ seg_off, const int64_t m) {
-  int lo = 0, hi = K;                                   // the k with seg_off[k] <= m < seg_off[k + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (seg_off[mid] <= m) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 __global__ void __launch_bounds__(256) select_resolve_kernel(const int64_t N, const int K, const int64_t M,
                                                              const unsigned long long* __restrict__ best,
                                                              const int64_t* __restrict__ seg_off,
@@ -226,7 +180,7 @@ __global__ void __launch_bounds__(256) select_resolve_kernel(const int64_t N, co
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   const unsigned long long key = best[n];
-  const int64_t m = (int64_t)(key & MA_LOW);
+  const int64_t m = (int64_t)(key & SEG_PAIR_LOW);
   const bool has = (key >> 63) == 0ull && m < M;        // the caller's fill (all ones) has bit 63 set
   float al = 0.f, gx = 0.f, gy = 0.f, gz = 0.f, d = INFINITY;
   if (has) {
@@ -235,7 +189,7 @@ __global__ void __launch_bounds__(256) select_resolve_kernel(const int64_t N, co
     const float gn = sqrtf((gx * gx + gy * gy) + gz * gz);
     d = al / fmaxf(gn, g_min);
   }
-  out_obj[n] = has ? ma_seg_of(K, seg_off, m) : -1;
+  out_obj[n] = has ? seg_of(seg_off, K, m) : -1;
   if (out_pair) out_pair[n] = has ? (int32_t)m : -1;
   out_d[n] = d;
   out_alpha[n] = al;
@@ -322,19 +276,6 @@ __global__ void __launch_bounds__(MA_WG) accumulate_reduce_kernel(const int64_t 
   wg_sums_store(s, red, out);
 }
 
-// the compute units of the CURRENT device (it sizes mp_grad_kernel's grid, never a result); cached per device
-std::atomic<int> g_ma_cu[64];
-int ma_num_cu() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 256;
-  const int cached = dev < 64 ? g_ma_cu[dev].load(std::memory_order_relaxed) : 0;
-  if (cached > 0) return cached;
-  int n = 0;
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 256;
-  if (dev < 64) g_ma_cu[dev].store(n, std::memory_order_relaxed);
-  return n;
-}
-bool ma_sizes_ok(const int64_t N, const int32_t K) { return N > 0 && N <= 0x7fffffff && K > 0 && K <= 65535; }
 int64_t ma_blocks(const int64_t N) { return cdiv(N, (int64_t)MA_WG * MA_PER); }
 
 }  // namespace
@@ -346,20 +287,13 @@ int objnerf_mappoints_grad(const objnerf_net* net, int32_t K, int64_t N, int64_t
                            const int64_t* seg_off, const int32_t* pair_pt, float* pair_alpha, float* pair_grad,
                            void* stream) {
   (void)hipGetLastError();
-  if (!net || !ma_sizes_ok(N, K) || M < 0 || M > 0x7fffffffLL || !params || !scale || !pts || !boxes || !info || !seg_off)
-    return OBJNERF_EINVAL;
-  if (net->hidden != 32 || net->n_freqs != 6) return OBJNERF_ENOTSUP;
-  if (M == 0) return OBJNERF_OK;
-  if (!pair_pt || !pair_alpha || !pair_grad) return OBJNERF_EINVAL;
   MaGrad d;
-  d.K = K; d.params = params; d.p_stride = (long)p_stride; d.scale = scale; d.pts = pts; d.boxes = boxes; d.info = info;
-  d.seg_off = seg_off; d.pair_pt = pair_pt; d.pair_alpha = pair_alpha; d.pair_grad = pair_grad;
-  d.L = make_layout(net->feat_dim);
+  const int rc = seg_walk_args(d, net, K, N, M, params, p_stride, scale, pts, boxes, info, seg_off, pair_pt);
+  if (rc != OBJNERF_OK || M == 0) return rc;
+  if (!pair_alpha || !pair_grad) return OBJNERF_EINVAL;
+  d.pair_alpha = pair_alpha; d.pair_grad = pair_grad;
   const size_t lds_bytes = (size_t)obj32n::img_floats(false) * 4;      // 60 KB: two workgroups a compute unit
-  int64_t G = 2 * (int64_t)ma_num_cu();
-  const int64_t t_max = M / 64 + K;
-  if (G > t_max) G = t_max;
-  hipLaunchKernelGGL(mp_grad_kernel, dim3((unsigned)G), dim3(256), lds_bytes, (hipStream_t)stream, d);
+  hipLaunchKernelGGL(mp_grad_kernel, seg_walk_grid(M, K), dim3(256), lds_bytes, (hipStream_t)stream, d);
   CHECK_LAUNCH();
   return OBJNERF_OK;
 }
@@ -394,7 +328,7 @@ int objnerf_mapalign_resolve(int64_t N, int32_t K, int64_t M, const uint64_t* be
                              const float* pair_alpha, const float* pair_grad, float g_min, int32_t* out_obj,
                              int32_t* out_pair, float* out_d, float* out_alpha, float* out_grad, void* stream) {
   (void)hipGetLastError();
-  if (!ma_sizes_ok(N, K) || M < 0 || M > 0x7fffffffLL || !best || !seg_off || !out_obj || !out_d || !out_alpha || !out_grad ||
+  if (!seg_sizes_ok(N, K) || M < 0 || M > 0x7fffffffLL || !best || !seg_off || !out_obj || !out_d || !out_alpha || !out_grad ||
       !(g_min > 0.0f))
     return OBJNERF_EINVAL;
   if (M > 0 && (!pair_alpha || !pair_grad)) return OBJNERF_EINVAL;

@@ -2,12 +2,11 @@
 // colour and part feature?  The 3-D counterpart of the z-buffer merge of train.py:550-612, over Trainer.eval_points
 // (trainer.py:105-128) restricted to each object's fitted box (the "bbox" of obj_<id>.pth, vmap.py:556-576).
 //
-//   box_count_kernel / wg_scan_kernel (objnerf_wg.h) / seg_off_kernel / box_emit_kernel
-//       candidate lists: point n is a candidate of object k iff |R_k^T (p_n - c_k)| <= extent_k / 2, component-wise, fp32.
-//       pair_pt [M] is object-major and ascending in the point index inside an object (prefixes run in thread order).
-//   mp_eval_kernel      the ragged fused evaluation of the hidden-32 objects: a flat list of (object, 64-pair tile), cut
-//       into one contiguous share per workgroup; a workgroup restages the weight image (stage_weights32) only where its
-//       share crosses into another object, gathers its points through pair_pt and runs the chain of objnerf_mlp32.h.
+//   objnerf_mappoints_count / _emit   the candidate CSR of objnerf_segments.h under the test InBox: point n is a candidate
+//       of object k iff |R_k^T (p_n - c_k)| <= extent_k / 2, component-wise, fp32.  pair_pt [M] is object-major and
+//       ascending in the point index inside an object.
+//   mp_eval_kernel      the ragged fused evaluation of the hidden-32 objects (seg_walk, objnerf_segments.h): a lane
+//       gathers its point through pair_pt and runs the chain of objnerf_mlp32.h.
 //   gather_kernel / merge_kernel   around objnerf_eval_points_ws for a wider network (the hidden-128 background): its
 //       segment of pair_pt is contiguous, so it is gathered, evaluated rectangularly and merged with the same keys.
 //   resolve_kernel      best [N] -> obj, alpha, the winning pair, the winner's colour.
@@ -25,141 +24,76 @@
 //
 // The arithmetic on a pair does not depend on where the pair sits: a sample is one column of the MFMA B operand and
 // every column goes through the same instructions (as in eval_kernel), the head sums h in one fixed order per row.
-#include "objnerf_mlp32.h"
-#include "objnerf_wg.h"
+#include "objnerf_segments.h"
 
 using namespace obj32;
 
 namespace {
 
-constexpr int MP_WG = 256;            // points / pairs per workgroup of the count and emit kernels
-constexpr int MP_SCAN_WG = 1024;
-constexpr int MP_BOX = 16;            // floats per box record: c [3] | R [3][3] row-major | extent / 2 [3] | obj_center
-constexpr unsigned long long MP_LOW = 0x7FFFFFFFull;
-
+// box record: c [3] | R [3][3] row-major | extent / 2 [3] | obj_center
 struct Box {
-  float c[3], R[9], h[3], oc;
+  float c[3], R[9], h[3];
 };
+// (the whole record at once, through a restrict pointer: the test's scalar loads then come in two rounds, not three)
 __device__ __forceinline__ Box load_box(const float* __restrict__ boxes, const int k) {
   Box b;
-  const float* p = boxes + (int64_t)k * MP_BOX;
+  const float* p = boxes + (int64_t)k * SEG_BOX_FLOATS;
 #pragma unroll
   for (int i = 0; i < 3; ++i) b.c[i] = p[i];
 #pragma unroll
   for (int i = 0; i < 9; ++i) b.R[i] = p[3 + i];
 #pragma unroll
   for (int i = 0; i < 3; ++i) b.h[i] = p[12 + i];
-  b.oc = p[15];
   return b;
 }
-// |R^T (p - c)| <= extent / 2 in every component
-__device__ __forceinline__ bool in_box(const Box& b, const float x, const float y, const float z) {
-  const float dx = x - b.c[0], dy = y - b.c[1], dz = z - b.c[2];
-  bool in = true;
+struct InBox {
+  const float* pts; const float* boxes; int32_t* pair_pt;
+  struct Payload {};
+  // |R^T (p - c)| <= extent / 2 in every component
+  __device__ __forceinline__ bool hit(const int k, const int64_t n, Payload&) const {
+    const Box b = load_box(boxes, k);
+    const float dx = pts[3 * n] - b.c[0], dy = pts[3 * n + 1] - b.c[1], dz = pts[3 * n + 2] - b.c[2];
+    bool in = true;
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const float l = fmaf(dz, b.R[6 + j], fmaf(dy, b.R[3 + j], dx * b.R[j]));
-    in = in && fabsf(l) <= b.h[j];
+    for (int j = 0; j < 3; ++j) {
+      const float l = fmaf(dz, b.R[6 + j], fmaf(dy, b.R[3 + j], dx * b.R[j]));
+      in = in && fabsf(l) <= b.h[j];
+    }
+    return in;
   }
-  return in;
-}
-
-// grid (nb, K): cnt [k][b] = the candidates of object k among the points of block b
-__global__ void __launch_bounds__(MP_WG) box_count_kernel(const int64_t N, const float* __restrict__ pts,
-                                                          const float* __restrict__ boxes, int64_t* __restrict__ cnt) {
-  const int k = blockIdx.y;
-  const Box b = load_box(boxes, k);
-  const int64_t n = (int64_t)blockIdx.x * MP_WG + threadIdx.x;
-  const bool in = n < N && in_box(b, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2]);
-  __shared__ int wcnt[MP_WG / 64];
-  int total;
-  wg_exclusive_flag<MP_WG>(in, wcnt, total);
-  if (threadIdx.x == 0) cnt[(int64_t)k * gridDim.x + blockIdx.x] = total;
-}
-// the scanned counts (cnt [K * nb] exclusive, cnt [K * nb] = M) -> seg_off [K + 1]
-__global__ void seg_off_kernel(const int K, const int64_t nb, const int64_t* __restrict__ cnt, int64_t* __restrict__ seg_off) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k <= K) seg_off[k] = cnt[(int64_t)k * nb];
-}
-__global__ void __launch_bounds__(MP_WG) box_emit_kernel(const int64_t N, const float* __restrict__ pts,
-                                                         const float* __restrict__ boxes, const int64_t* __restrict__ cnt,
-                                                         const int64_t M, int32_t* __restrict__ pair_pt) {
-  const int k = blockIdx.y;
-  const Box b = load_box(boxes, k);
-  const int64_t n = (int64_t)blockIdx.x * MP_WG + threadIdx.x;
-  const bool in = n < N && in_box(b, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2]);
-  __shared__ int wcnt[MP_WG / 64];
-  int total;
-  const int64_t pos = cnt[(int64_t)k * gridDim.x + blockIdx.x] + wg_exclusive_flag<MP_WG>(in, wcnt, total);
-  if (in && pos >= 0 && pos < M) pair_pt[pos] = (int32_t)n;
-}
+  __device__ __forceinline__ void store(const int64_t pos, const int64_t n, const Payload&) const { pair_pt[pos] = (int32_t)n; }
+};
 
 // ------------------------------------------------------------------------------------------------------------ keys
 __device__ __forceinline__ unsigned long long make_key(const float alpha, const bool fg, const int64_t m) {
   const unsigned u = __float_as_uint(alpha);
   const unsigned ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
   const unsigned long long top = (fg && alpha > 0.0f) ? 1ull : 0ull;
-  return (top << 63) | ((unsigned long long)ord << 31) | (MP_LOW - (unsigned long long)m);
+  return (top << 63) | ((unsigned long long)ord << 31) | (SEG_PAIR_LOW - (unsigned long long)m);
 }
 __device__ __forceinline__ float key_alpha(const unsigned long long key) {
   const unsigned ord = (unsigned)(key >> 31);
   return __uint_as_float((ord & 0x80000000u) ? (ord & 0x7FFFFFFFu) : ~ord);
 }
-__device__ __forceinline__ int64_t key_pair(const unsigned long long key) { return (int64_t)(MP_LOW - (key & MP_LOW)); }
+__device__ __forceinline__ int64_t key_pair(const unsigned long long key) { return (int64_t)(SEG_PAIR_LOW - (key & SEG_PAIR_LOW)); }
 // the pair that labels its point, or -1: the maximum, when it is occupied
 __device__ __forceinline__ int64_t key_winner(const unsigned long long key) {
   return (key != 0ull && key_alpha(key) > 0.0f) ? key_pair(key) : -1;
 }
 
 // ------------------------------------------------------------------------------------------- the ragged evaluation
-struct MpEval {
-  int K;
-  const float* params; long p_stride; const float* scale;
-  const float* pts; const float* boxes; const int32_t* info;      // info [K][2]: arena row (-1: not a hidden-32 object), background
-  const int64_t* seg_off; const int32_t* pair_pt;
+struct MpEval : SegWalkArgs {          // info's flag: the object is a background
   float* pair_alpha; float* pair_color; float* pair_hfeat;
   unsigned long long* best;
-  Layout L;
 };
-__device__ __forceinline__ long mp_tiles(const MpEval& a, const int k) {
-  return a.info[2 * k] >= 0 ? (long)((a.seg_off[k + 1] - a.seg_off[k] + 63) >> 6) : 0L;
-}
-// 4 independent waves per workgroup, 16 pairs per wave per tile (eval_kernel's form, objnerf_train.hip)
 template <bool FEAT>
 __global__ __launch_bounds__(256) void mp_eval_kernel(const MpEval a) {
   using namespace obj32n;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, g = lane >> 4;
-  long T = 0;
-  for (int k = 0; k < a.K; ++k) T += mp_tiles(a, k);
-  const long t0 = T * (long)blockIdx.x / (long)gridDim.x, t1 = T * ((long)blockIdx.x + 1) / (long)gridDim.x;
-  if (t0 >= t1) return;                                 // (uniform over the workgroup)
-  int k = 0;
-  long kt0 = 0, kt1 = mp_tiles(a, 0);                   // object k owns tiles [kt0, kt1)
-  int staged = -1;
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   const float* sv = lds + sv_base(FEAT);
   const float* wf = (const float*)__builtin_assume_aligned(lds + 4 * g * WROW + out_pos(c), 8);
-  float scale = 1.0f, oc = 0.0f;
-  bool fg = false;
-  int64_t s0 = 0, s1 = 0;
-  for (long t = t0; t < t1; ++t) {
-    while (t >= kt1) { ++k; kt0 = kt1; kt1 += mp_tiles(a, k); }      // k < K: t < T
-    if (staged != k) {
-      __syncthreads();                                  // every wave is done with the image of the object before
-      const int row = a.info[2 * k];
-      stage_weights32(lds, a.params + (long)row * a.p_stride, a.L, FEAT, tid, 256);
-      scale = a.scale[row];
-      oc = a.boxes[(long)k * MP_BOX + 15];
-      fg = a.info[2 * k + 1] == 0;
-      s0 = a.seg_off[k]; s1 = a.seg_off[k + 1];
-      staged = k;
-    }
-    asm volatile("" ::: "memory");   // keep the LDS weight reads inside the loop (no LICM into registers)
-    const int64_t m = s0 + (t - kt0) * 64 + 16 * w + c;
-    const bool valid = m < s1;
-    const int64_t n = a.pair_pt[valid ? m : s0];
+  seg_walk<FEAT>(a, lds, [&](const int64_t m, const bool valid, const int64_t n, const float scale, const float oc, const int bg) {
     const float* p = a.pts + n * 3;
     Pe32 pe;
     pe32_project(sv, g, p[0] - oc, p[1] - oc, p[2] - oc, scale, pe);
@@ -170,7 +104,7 @@ __global__ __launch_bounds__(256) void mp_eval_kernel(const MpEval a) {
     if (valid) {
       if (g == 0) {
         a.pair_alpha[m] = hout;
-        atomicMax(a.best + n, make_key(hout, fg, m));
+        atomicMax(a.best + n, make_key(hout, bg == 0, m));
       } else if (a.pair_color) {
         a.pair_color[m * 3 + g - 1] = hout;
       }
@@ -182,7 +116,7 @@ __global__ __launch_bounds__(256) void mp_eval_kernel(const MpEval a) {
         }
       }
     }
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------- a wide object's segment
@@ -202,14 +136,6 @@ __global__ void __launch_bounds__(256) merge_kernel(const int64_t n, const int64
 }
 
 // ---------------------------------------------------------------------------------------------------------- resolve
-__device__ __forceinline__ int seg_of(const int K, const int64_t* __restrict__ seg_off, const int64_t m) {
-  int lo = 0, hi = K;                                   // the k with seg_off[k] <= m < seg_off[k + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (seg_off[mid] <= m) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 __global__ void __launch_bounds__(256) resolve_kernel(const int64_t N, const int K, const unsigned long long* __restrict__ best,
                                                       const int64_t* __restrict__ seg_off, const float* __restrict__ pair_color,
                                                       int32_t* __restrict__ out_obj, float* __restrict__ out_alpha,
@@ -219,7 +145,7 @@ __global__ void __launch_bounds__(256) resolve_kernel(const int64_t N, const int
   const unsigned long long key = best[n];
   const int64_t m = key_winner(key);
   out_alpha[n] = key != 0ull ? key_alpha(key) : -INFINITY;
-  out_obj[n] = m >= 0 ? seg_of(K, seg_off, m) : -1;
+  out_obj[n] = m >= 0 ? seg_of(seg_off, K, m) : -1;
   if (out_pair) out_pair[n] = (int32_t)m;
   if (out_color) {
 #pragma unroll
@@ -232,29 +158,29 @@ __device__ __forceinline__ bool pair_wins(const int64_t m, const int64_t M, cons
                                           const unsigned long long* __restrict__ best) {
   return m < M && key_winner(best[pair_pt[m]]) == m;
 }
-__global__ void __launch_bounds__(MP_WG) win_count_kernel(const int64_t M, const int32_t* __restrict__ pair_pt,
+__global__ void __launch_bounds__(SEG_WG) win_count_kernel(const int64_t M, const int32_t* __restrict__ pair_pt,
                                                           const unsigned long long* __restrict__ best,
                                                           int64_t* __restrict__ cnt) {
-  const bool win = pair_wins((int64_t)blockIdx.x * MP_WG + threadIdx.x, M, pair_pt, best);
-  __shared__ int wcnt[MP_WG / 64];
+  const bool win = pair_wins((int64_t)blockIdx.x * SEG_WG + threadIdx.x, M, pair_pt, best);
+  __shared__ int wcnt[SEG_WG / 64];
   int total;
-  wg_exclusive_flag<MP_WG>(win, wcnt, total);
+  wg_exclusive_flag<SEG_WG>(win, wcnt, total);
   if (threadIdx.x == 0) cnt[blockIdx.x] = total;
 }
 // win [3][max_win]: the winning pairs in pair order (object-major), their points, their objects
-__global__ void __launch_bounds__(MP_WG) win_emit_kernel(const int64_t M, const int K, const int32_t* __restrict__ pair_pt,
+__global__ void __launch_bounds__(SEG_WG) win_emit_kernel(const int64_t M, const int K, const int32_t* __restrict__ pair_pt,
                                                          const unsigned long long* __restrict__ best,
                                                          const int64_t* __restrict__ seg_off, const int64_t* __restrict__ cnt,
                                                          const int64_t max_win, int32_t* __restrict__ win) {
-  const int64_t m = (int64_t)blockIdx.x * MP_WG + threadIdx.x;
+  const int64_t m = (int64_t)blockIdx.x * SEG_WG + threadIdx.x;
   const bool wins = pair_wins(m, M, pair_pt, best);
-  __shared__ int wcnt[MP_WG / 64];
+  __shared__ int wcnt[SEG_WG / 64];
   int total;
-  const int64_t pos = cnt[blockIdx.x] + wg_exclusive_flag<MP_WG>(wins, wcnt, total);
+  const int64_t pos = cnt[blockIdx.x] + wg_exclusive_flag<SEG_WG>(wins, wcnt, total);
   if (wins && pos >= 0 && pos < max_win) {
     win[pos] = (int32_t)m;
     win[max_win + pos] = pair_pt[m];
-    win[2 * max_win + pos] = seg_of(K, seg_off, m);
+    win[2 * max_win + pos] = seg_of(seg_off, K, m);
   }
 }
 
@@ -393,58 +319,29 @@ __global__ void __launch_bounds__(256, HW == 128 ? 1 : 2) head_kernel(const int 
   }
 }
 
-int g_mp_cu = 0;
-int mp_num_cu() {
-  if (g_mp_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    g_mp_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return g_mp_cu;
-}
-
-bool mp_sizes_ok(const int64_t N, const int32_t K) { return N > 0 && N <= 0x7fffffff && K > 0 && K <= 65535; }
-int64_t mp_blocks(const int64_t n) { return cdiv(n, MP_WG); }
 
 }  // namespace
 
 extern "C" {
 
-size_t objnerf_mappoints_workspace_bytes(int64_t N, int32_t K) {
-  if (!mp_sizes_ok(N, K)) return 0;
-  return align256(((size_t)K * (size_t)mp_blocks(N) + 1) * sizeof(int64_t));
-}
+size_t objnerf_mappoints_workspace_bytes(int64_t N, int32_t K) { return seg_csr_workspace_bytes(N, K); }
 
 int objnerf_mappoints_count(int64_t N, int32_t K, const float* pts, const float* boxes, void* ws, size_t ws_bytes,
                             int64_t* seg_off, void* stream) {
   (void)hipGetLastError();
-  if (!mp_sizes_ok(N, K) || !pts || !boxes || !ws || !seg_off) return OBJNERF_EINVAL;
-  if (ws_bytes < objnerf_mappoints_workspace_bytes(N, K)) return OBJNERF_EINVAL;
-  const int64_t nb = mp_blocks(N);
-  int64_t* cnt = (int64_t*)ws;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(box_count_kernel, dim3((unsigned)nb, (unsigned)K), dim3(MP_WG), 0, st, N, pts, boxes, cnt);
-  CHECK_LAUNCH();
-  hipLaunchKernelGGL((wg_scan_kernel<MP_SCAN_WG, 1, int64_t>), dim3(1), dim3(MP_SCAN_WG), 0, st, cnt, (int64_t)K * nb,
-                     cnt + (int64_t)K * nb);
-  CHECK_LAUNCH();
-  hipLaunchKernelGGL(seg_off_kernel, dim3((unsigned)cdiv(K + 1, 256)), dim3(256), 0, st, (int)K, nb, cnt, seg_off);
-  CHECK_LAUNCH();
-  return OBJNERF_OK;
+  if (!seg_sizes_ok(N, K) || !pts || !boxes || !ws || !seg_off) return OBJNERF_EINVAL;
+  if (ws_bytes < seg_csr_workspace_bytes(N, K)) return OBJNERF_EINVAL;
+  return seg_csr_count(N, K, InBox{pts, boxes, nullptr}, 1, ws, seg_off, (hipStream_t)stream);
 }
 
 int objnerf_mappoints_emit(int64_t N, int32_t K, const float* pts, const float* boxes, const void* ws, size_t ws_bytes,
                            int64_t M, int32_t* pair_pt, void* stream) {
   (void)hipGetLastError();
-  if (!mp_sizes_ok(N, K) || !pts || !boxes || !ws || M < 0 || M > 0x7fffffffLL) return OBJNERF_EINVAL;
-  if (ws_bytes < objnerf_mappoints_workspace_bytes(N, K)) return OBJNERF_EINVAL;
+  if (!seg_sizes_ok(N, K) || !pts || !boxes || !ws || M < 0 || M > 0x7fffffffLL) return OBJNERF_EINVAL;
+  if (ws_bytes < seg_csr_workspace_bytes(N, K)) return OBJNERF_EINVAL;
   if (M == 0) return OBJNERF_OK;
   if (!pair_pt) return OBJNERF_EINVAL;
-  hipLaunchKernelGGL(box_emit_kernel, dim3((unsigned)mp_blocks(N), (unsigned)K), dim3(MP_WG), 0, (hipStream_t)stream, N, pts,
-                     boxes, (const int64_t*)ws, M, pair_pt);
-  CHECK_LAUNCH();
-  return OBJNERF_OK;
+  return seg_csr_emit(N, K, InBox{pts, boxes, pair_pt}, ws, M, (hipStream_t)stream);
 }
 
 int objnerf_mappoints_eval(const objnerf_net* net, int32_t K, int64_t N, int64_t M, const float* params, int64_t p_stride,
@@ -452,28 +349,20 @@ int objnerf_mappoints_eval(const objnerf_net* net, int32_t K, int64_t N, int64_t
                            const int64_t* seg_off, const int32_t* pair_pt, float* pair_alpha, float* pair_color,
                            float* pair_hfeat, uint64_t* best, void* stream) {
   (void)hipGetLastError();
-  if (!net || !mp_sizes_ok(N, K) || M < 0 || M > 0x7fffffffLL || !params || !scale || !pts || !boxes || !info || !seg_off ||
-      !best)
-    return OBJNERF_EINVAL;
-  if (net->hidden != 32 || net->n_freqs != 6) return OBJNERF_ENOTSUP;
-  if (M == 0) return OBJNERF_OK;
-  if (!pair_pt || !pair_alpha) return OBJNERF_EINVAL;
+  if (!best) return OBJNERF_EINVAL;
   MpEval d;
-  d.K = K; d.params = params; d.p_stride = (long)p_stride; d.scale = scale; d.pts = pts; d.boxes = boxes; d.info = info;
-  d.seg_off = seg_off; d.pair_pt = pair_pt; d.pair_alpha = pair_alpha; d.pair_color = pair_color; d.pair_hfeat = pair_hfeat;
+  const int rc = seg_walk_args(d, net, K, N, M, params, p_stride, scale, pts, boxes, info, seg_off, pair_pt);
+  if (rc != OBJNERF_OK || M == 0) return rc;
+  if (!pair_alpha) return OBJNERF_EINVAL;
+  d.pair_alpha = pair_alpha; d.pair_color = pair_color; d.pair_hfeat = pair_hfeat;
   d.best = (unsigned long long*)best;
-  d.L = make_layout(net->feat_dim);
   const bool feat = pair_hfeat != nullptr;
   const size_t lds_bytes = (size_t)obj32n::img_floats(feat) * 4;
   objnerf_once_per_device([] {                          // the image with the feature layer exceeds the 64 KB default
     (void)hipFuncSetAttribute((const void*)mp_eval_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               obj32n::img_floats(true) * 4);
   });
-  // two workgroups a compute unit (the image is 60 / 73 KB), never more than the tiles there can be
-  int64_t G = 2 * (int64_t)mp_num_cu();
-  const int64_t t_max = M / 64 + K;
-  if (G > t_max) G = t_max;
-  const dim3 grid((unsigned)G), blk(256);
+  const dim3 grid = seg_walk_grid(M, K), blk(256);
   if (feat) hipLaunchKernelGGL((mp_eval_kernel<true>), grid, blk, lds_bytes, (hipStream_t)stream, d);
   else hipLaunchKernelGGL((mp_eval_kernel<false>), grid, blk, lds_bytes, (hipStream_t)stream, d);
   CHECK_LAUNCH();
@@ -507,7 +396,7 @@ int objnerf_mappoints_resolve(int64_t N, int32_t K, int64_t M, const uint64_t* b
                               const float* pair_color, int32_t* out_obj, float* out_alpha, int32_t* out_pair,
                               float* out_color, void* stream) {
   (void)hipGetLastError();
-  if (!mp_sizes_ok(N, K) || M < 0 || M > 0x7fffffffLL || !best || !seg_off || !out_obj || !out_alpha) return OBJNERF_EINVAL;
+  if (!seg_sizes_ok(N, K) || M < 0 || M > 0x7fffffffLL || !best || !seg_off || !out_obj || !out_alpha) return OBJNERF_EINVAL;
   // (without a pair nothing can win: every colour is 0 and pair_color, an empty buffer, is never read)
   if (out_color && !pair_color && M > 0) return OBJNERF_EINVAL;
   hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, N, (int)K,
@@ -518,29 +407,29 @@ int objnerf_mappoints_resolve(int64_t N, int32_t K, int64_t M, const uint64_t* b
 
 size_t objnerf_mappoints_head_workspace_bytes(int64_t M) {
   if (M <= 0 || M > 0x7fffffffLL) return 0;
-  return align256(((size_t)mp_blocks(M) + 1) * sizeof(int64_t));
+  return align256(((size_t)seg_blocks(M) + 1) * sizeof(int64_t));
 }
 
 int objnerf_mappoints_head(int32_t K, int32_t C, int64_t N, int64_t M, const uint64_t* best, const int64_t* seg_off,
                            const int32_t* pair_pt, const objnerf_mappoints_head_obj* heads, int32_t widths, void* ws,
                            size_t ws_bytes, int32_t* win_pair, float* out_feat, void* stream) {
   (void)hipGetLastError();
-  if (!mp_sizes_ok(N, K) || C <= 0 || M < 0 || M > 0x7fffffffLL || !best || !seg_off || !heads) return OBJNERF_EINVAL;
+  if (!seg_sizes_ok(N, K) || C <= 0 || M < 0 || M > 0x7fffffffLL || !best || !seg_off || !heads) return OBJNERF_EINVAL;
   if (M == 0) return OBJNERF_OK;
   if (!pair_pt || !ws || !win_pair || !out_feat || ws_bytes < objnerf_mappoints_head_workspace_bytes(M)) return OBJNERF_EINVAL;
-  const int64_t nb = mp_blocks(M);
+  const int64_t nb = seg_blocks(M);
   int64_t* cnt = (int64_t*)ws;
   hipStream_t st = (hipStream_t)stream;
   const unsigned long long* b = (const unsigned long long*)best;
-  hipLaunchKernelGGL(win_count_kernel, dim3((unsigned)nb), dim3(MP_WG), 0, st, M, pair_pt, b, cnt);
+  hipLaunchKernelGGL(win_count_kernel, dim3((unsigned)nb), dim3(SEG_WG), 0, st, M, pair_pt, b, cnt);
   CHECK_LAUNCH();
-  hipLaunchKernelGGL((wg_scan_kernel<MP_SCAN_WG, 1, int64_t>), dim3(1), dim3(MP_SCAN_WG), 0, st, cnt, nb, cnt + nb);
+  hipLaunchKernelGGL((wg_scan_kernel<SEG_SCAN_WG, 1, int64_t>), dim3(1), dim3(SEG_SCAN_WG), 0, st, cnt, nb, cnt + nb);
   CHECK_LAUNCH();
   const int64_t max_win = N < M ? N : M;                // a point has one winner at the most: win_pair holds 3 x min(N, M)
-  hipLaunchKernelGGL(win_emit_kernel, dim3((unsigned)nb), dim3(MP_WG), 0, st, M, (int)K, pair_pt, b, seg_off, cnt, max_win,
+  hipLaunchKernelGGL(win_emit_kernel, dim3((unsigned)nb), dim3(SEG_WG), 0, st, M, (int)K, pair_pt, b, seg_off, cnt, max_win,
                      win_pair);
   CHECK_LAUNCH();
-  int64_t G = 8 * (int64_t)mp_num_cu();
+  int64_t G = 8 * (int64_t)objnerf_num_cu();
   const int64_t t_max = cdiv(max_win, HD_TW);
   if (G > t_max) G = t_max;
   const int64_t* n_win = cnt + nb;

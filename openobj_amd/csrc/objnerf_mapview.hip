@@ -4,10 +4,9 @@
 //
 // 1. objnerf_view_rays_count / _emit: the candidate rays of ALL objects.  Pixel p = w * H + h of the transposed [W, H]
 //    image is tested against box k with box_ray (objnerf_boxray.h, the function objnerf_box_rays runs); the hits of an
-//    object become one segment of a CSR over the objects in the caller's (dict) order, ascending in p inside a segment
-//    (count / scan / emit of objnerf_wg.h: prefixes run in thread order, no atomics), which is the order of the
-//    nonzero() in render_2D_syn.  An object with at most one hit gets an EMPTY segment (trainer.py:164-165 of the
-//    reference drops it): view_drop_kernel zeroes its counts before the scan.
+//    object become one segment of the candidate CSR of objnerf_segments.h over the objects in the caller's (dict)
+//    order, ascending in p inside a segment, which is the order of the nonzero() in render_2D_syn.  An object with at
+//    most one hit gets an EMPTY segment (n_rays <= 1, trainer.py:164-165 of the reference drops it): min_keep = 2.
 // 2. objnerf_render_fwd_segmented: render_group (objnerf_render_body.h, the body objnerf_render_fwd runs) over the
 //    segments of every hidden-32 object in ONE launch.  The work list is tiles (arena row, first 16-ray group, groups);
 //    groups count from the segment's start, so ray r = entry - seg_lo is lane r & 15 of group r >> 4, the row of the
@@ -34,84 +33,34 @@
 //    for a pixel list, for the winners of stage 3 only; its banner stands ahead of its kernels below.
 #include "objnerf_render_body.h"
 #include "objnerf_boxray.h"
-#include "objnerf_wg.h"
+#include "objnerf_segments.h"
 
 namespace {
 using namespace obj32n;
 
-constexpr int MV_WG = 256;            // pixels / entries per workgroup of the count, emit and merge kernels
-constexpr int MV_SCAN_WG = 1024;
-constexpr int MV_BOX = 16;            // floats per box record: T_OC rows 0..2 [3][4] | extent / 2 [3] | unused
+constexpr int MV_WG = 256;            // pixels / entries per workgroup of the merge kernels
 constexpr unsigned long long MV_NO_FG = ((unsigned long long)0x42C80000u << 32) | 0xFFFFFFFFull;   // bits(100.0f), no entry
 
-bool mv_sizes_ok(const int64_t P, const int32_t K) { return P > 0 && P <= 0x7fffffff && K > 0 && K <= 65535; }
 int64_t mv_blocks(const int64_t n) { return cdiv(n, MV_WG); }
-int mv_num_cu() {
-  int dev = 0, cu = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-  return cu > 0 ? cu : 256;
-}
 
 // -------------------------------------------------------------------------------------------------- 1. candidate rays
-__device__ __forceinline__ BoxRay view_ray(const float* __restrict__ T_WC, const float* __restrict__ boxes, const int k,
-                                           const float* __restrict__ dirs_C, const int64_t p) {
-  const float* rec = boxes + (int64_t)k * MV_BOX;
-  return box_ray(T_WC, rec, rec + 12, dirs_C[3 * p], dirs_C[3 * p + 1], dirs_C[3 * p + 2]);
-}
-
-// grid (nb, K): cnt [k][b] = the hits of object k among the pixels of block b
-__global__ void __launch_bounds__(MV_WG) view_count_kernel(const int64_t P, const float* __restrict__ T_WC,
-                                                           const float* __restrict__ boxes,
-                                                           const float* __restrict__ dirs_C, int64_t* __restrict__ cnt) {
-  const int k = blockIdx.y;
-  const int64_t p = (int64_t)blockIdx.x * MV_WG + threadIdx.x;
-  const bool hit = p < P && view_ray(T_WC, boxes, k, dirs_C, p).hit;
-  __shared__ int wcnt[MV_WG / 64];
-  int total;
-  wg_exclusive_flag<MV_WG>(hit, wcnt, total);
-  if (threadIdx.x == 0) cnt[(int64_t)k * gridDim.x + blockIdx.x] = total;
-}
-// grid K: an object with at most one hit keeps none (n_rays <= 1, trainer.py:164-165 of the reference)
-__global__ void __launch_bounds__(MV_WG) view_drop_kernel(const int64_t nb, int64_t* __restrict__ cnt) {
-  int64_t* row = cnt + (int64_t)blockIdx.x * nb;
-  int v = 0;                                              // (a block counts at most MV_WG, all of them at most P < 2^31)
-  for (int64_t b = threadIdx.x; b < nb; b += MV_WG) v += (int)row[b];
-  __shared__ int wsum[MV_WG / 64];
-  const int total = wg_sum<MV_WG>(v, wsum);
-  if (total > 1) return;                                  // (uniform over the workgroup)
-  for (int64_t b = threadIdx.x; b < nb; b += MV_WG) row[b] = 0;
-}
-// the scanned counts (cnt [K * nb] exclusive, cnt [K * nb] = M) -> seg_off [K + 1]
-__global__ void view_seg_off_kernel(const int K, const int64_t nb, const int64_t* __restrict__ cnt,
-                                    int64_t* __restrict__ seg_off) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k <= K) seg_off[k] = cnt[(int64_t)k * nb];
-}
-__global__ void __launch_bounds__(MV_WG) view_emit_kernel(const int64_t P, const float* __restrict__ T_WC,
-                                                          const float* __restrict__ boxes,
-                                                          const float* __restrict__ dirs_C,
-                                                          const int64_t* __restrict__ cnt, const int64_t M,
-                                                          int32_t* __restrict__ pix, float* __restrict__ dirs_W,
-                                                          float* __restrict__ near_o, float* __restrict__ far_o) {
-  const int k = blockIdx.y;
-  const int64_t nb = gridDim.x;
-  const int64_t p = (int64_t)blockIdx.x * MV_WG + threadIdx.x;
-  BoxRay b;
-  b.hit = false;
-  if (p < P) b = view_ray(T_WC, boxes, k, dirs_C, p);
-  __shared__ int wcnt[MV_WG / 64];
-  int total;
-  const int64_t pos = cnt[(int64_t)k * nb + blockIdx.x] + wg_exclusive_flag<MV_WG>(b.hit, wcnt, total);
-  // the end of THIS object's segment: a dropped object (all counts zeroed) owns no slot, its hits go nowhere
-  const int64_t end = cnt[((int64_t)k + 1) * nb];
-  if (b.hit && pos >= 0 && pos < end && pos < M) {
+// box record: T_OC rows 0..2 [3][4] | extent / 2 [3] | unused
+struct ViewRay {
+  const float* T_WC; const float* boxes; const float* dirs_C;
+  int32_t* pix; float* dirs_W; float* near_o; float* far_o;
+  typedef BoxRay Payload;
+  __device__ __forceinline__ bool hit(const int k, const int64_t p, BoxRay& b) const {
+    const float* rec = boxes + (int64_t)k * SEG_BOX_FLOATS;
+    b = box_ray(T_WC, rec, rec + 12, dirs_C[3 * p], dirs_C[3 * p + 1], dirs_C[3 * p + 2]);
+    return b.hit;
+  }
+  __device__ __forceinline__ void store(const int64_t pos, const int64_t p, const BoxRay& b) const {
     pix[pos] = (int32_t)p;
     dirs_W[3 * pos] = b.dw[0]; dirs_W[3 * pos + 1] = b.dw[1]; dirs_W[3 * pos + 2] = b.dw[2];
     near_o[pos] = b.near_;
     far_o[pos] = b.far_;
   }
-}
+};
 
 // ---------------------------------------------------------------------------------------------- 2. segmented render
 struct SegRenderDev {
@@ -181,14 +130,6 @@ __global__ __launch_bounds__(256) void render_seg_kernel(const SegRenderDev a) {
 }
 
 // ------------------------------------------------------------------------------------------------------- 3. merge
-__device__ __forceinline__ int mv_seg_of(const int K, const int64_t* __restrict__ seg_off, const int64_t e) {
-  int lo = 0, hi = K;                                       // the k with seg_off[k] <= e < seg_off[k + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (seg_off[mid] <= e) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 // vmap.py:350 here (the masks of vmap.py:665,672) and the 100 the depth image starts from (train.py:566)
 __device__ __forceinline__ bool mv_offered(const float d, const float op, const float nr, const float fr) {
   return !((d < nr) | (d > fr) | (op < 0.9f)) && d < 100.0f;
@@ -212,7 +153,7 @@ template <bool BG>
 __global__ void __launch_bounds__(MV_WG) merge_entry_kernel(const MergeDev a) {
   const int64_t e = (int64_t)blockIdx.x * MV_WG + threadIdx.x;
   if (e >= a.M) return;
-  const int k = mv_seg_of(a.K, a.seg_off, e);
+  const int k = seg_of(a.seg_off, a.K, e);
   if ((a.info[2 * k] != 0) != BG) return;
   const int64_t p = a.pix[e];
   if (p < 0 || p >= a.P) return;
@@ -239,7 +180,7 @@ __global__ void __launch_bounds__(MV_WG) merge_out_kernel(const MergeDev a) {
   a.out_depth[p] = __uint_as_float((unsigned int)(key >> 32));
   a.out_winner[p] = (int32_t)e;
   const bool painted = e >= 0 && e < a.M;
-  a.out_maskid[p] = painted ? a.info[2 * mv_seg_of(a.K, a.seg_off, e) + 1] : 0;
+  a.out_maskid[p] = painted ? a.info[2 * seg_of(a.seg_off, a.K, e) + 1] : 0;
 #pragma unroll
   for (int j = 0; j < 3; ++j)
     a.out_rgb[3 * p + j] = painted ? (uint8_t)(int)(a.rgb[3 * e + j] * 255.0f) : (uint8_t)0;      // truncation
@@ -282,7 +223,7 @@ struct ViewQueryDev {
 __device__ __forceinline__ bool vq_width_built(const int H) { return H == 32 || H == 64 || H == 128; }
 // the object of entry e if its head serves e, else -1
 __device__ __forceinline__ int vq_server(const ViewQueryDev& a, const int64_t e) {
-  const int k = mv_seg_of(a.K, a.seg_off, e);
+  const int k = seg_of(a.seg_off, a.K, e);
   const objnerf_view_head_obj& h = a.heads[k];
   const int64_t rel = e - h.row0;
   return (h.of_w && h.of_b && h.hfeat && vq_width_built(h.H) && rel >= 0 && rel < h.n_rows) ? k : -1;
@@ -428,43 +369,25 @@ __global__ void __launch_bounds__(MV_WG) view_query_fill_kernel(const ViewQueryD
 
 extern "C" {
 
-size_t objnerf_view_rays_workspace_bytes(int64_t P, int32_t K) {
-  if (!mv_sizes_ok(P, K)) return 0;
-  return align256(((size_t)K * (size_t)mv_blocks(P) + 1) * sizeof(int64_t));
-}
+size_t objnerf_view_rays_workspace_bytes(int64_t P, int32_t K) { return seg_csr_workspace_bytes(P, K); }
 
 int objnerf_view_rays_count(int64_t P, int32_t K, const float* T_WC, const float* boxes, const float* dirs_C, void* ws,
                             size_t ws_bytes, int64_t* seg_off, void* stream) {
   (void)hipGetLastError();
-  if (!mv_sizes_ok(P, K) || !T_WC || !boxes || !dirs_C || !ws || !seg_off) return OBJNERF_EINVAL;
-  if (ws_bytes < objnerf_view_rays_workspace_bytes(P, K)) return OBJNERF_EINVAL;
-  const int64_t nb = mv_blocks(P);
-  int64_t* cnt = (int64_t*)ws;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(view_count_kernel, dim3((unsigned)nb, (unsigned)K), dim3(MV_WG), 0, st, P, T_WC, boxes, dirs_C, cnt);
-  CHECK_LAUNCH();
-  hipLaunchKernelGGL(view_drop_kernel, dim3((unsigned)K), dim3(MV_WG), 0, st, nb, cnt);
-  CHECK_LAUNCH();
-  hipLaunchKernelGGL((wg_scan_kernel<MV_SCAN_WG, 1, int64_t>), dim3(1), dim3(MV_SCAN_WG), 0, st, cnt, (int64_t)K * nb,
-                     cnt + (int64_t)K * nb);
-  CHECK_LAUNCH();
-  hipLaunchKernelGGL(view_seg_off_kernel, dim3((unsigned)cdiv(K + 1, 256)), dim3(256), 0, st, (int)K, nb,
-                     (const int64_t*)cnt, seg_off);
-  CHECK_LAUNCH();
-  return OBJNERF_OK;
+  if (!seg_sizes_ok(P, K) || !T_WC || !boxes || !dirs_C || !ws || !seg_off) return OBJNERF_EINVAL;
+  if (ws_bytes < seg_csr_workspace_bytes(P, K)) return OBJNERF_EINVAL;
+  return seg_csr_count(P, K, ViewRay{T_WC, boxes, dirs_C, nullptr, nullptr, nullptr, nullptr}, 2, ws, seg_off,
+                       (hipStream_t)stream);
 }
 
 int objnerf_view_rays_emit(int64_t P, int32_t K, const float* T_WC, const float* boxes, const float* dirs_C, const void* ws,
                            size_t ws_bytes, int64_t M, int32_t* pix, float* dirs_W, float* near, float* far, void* stream) {
   (void)hipGetLastError();
-  if (!mv_sizes_ok(P, K) || !T_WC || !boxes || !dirs_C || !ws || M < 0 || M >= (1LL << 32)) return OBJNERF_EINVAL;
-  if (ws_bytes < objnerf_view_rays_workspace_bytes(P, K)) return OBJNERF_EINVAL;
+  if (!seg_sizes_ok(P, K) || !T_WC || !boxes || !dirs_C || !ws || M < 0 || M >= (1LL << 32)) return OBJNERF_EINVAL;
+  if (ws_bytes < seg_csr_workspace_bytes(P, K)) return OBJNERF_EINVAL;
   if (M == 0) return OBJNERF_OK;
   if (!pix || !dirs_W || !near || !far) return OBJNERF_EINVAL;
-  hipLaunchKernelGGL(view_emit_kernel, dim3((unsigned)mv_blocks(P), (unsigned)K), dim3(MV_WG), 0, (hipStream_t)stream, P,
-                     T_WC, boxes, dirs_C, (const int64_t*)ws, M, pix, dirs_W, near, far);
-  CHECK_LAUNCH();
-  return OBJNERF_OK;
+  return seg_csr_emit(P, K, ViewRay{T_WC, boxes, dirs_C, pix, dirs_W, near, far}, ws, M, (hipStream_t)stream);
 }
 
 // both entries of the segmented renderer: out_hfeat selects the instantiation
@@ -488,7 +411,7 @@ static int render_fwd_segmented(const objnerf_net* net, int32_t n_rows, int64_t 
   d.depth = out_depth; d.opacity = out_opacity; d.rgb = out_rgb; d.hfeat = out_hfeat;
   d.L = make_layout(net->feat_dim);
   // two workgroups of 4 waves per CU (the image is 60 KB; 73 KB with the feature layer), never more than there are tiles
-  int64_t G = workgroups > 0 ? (int64_t)workgroups : 2 * (int64_t)mv_num_cu();
+  int64_t G = workgroups > 0 ? (int64_t)workgroups : 2 * (int64_t)objnerf_num_cu();
   if (G > n_tiles) G = n_tiles;
   if (out_hfeat) {
     // 73 KB of dynamic LDS is above the 64 KB a kernel gets without asking
@@ -544,7 +467,7 @@ int objnerf_view_merge(int64_t P, int32_t K, int64_t M, const int64_t* seg_off, 
                        int32_t any_background, uint64_t* best_fg, uint32_t* best_bg, uint8_t* out_rgb, int32_t* out_maskid,
                        float* out_depth, int32_t* out_winner, void* stream) {
   (void)hipGetLastError();
-  if (!mv_sizes_ok(P, K) || M < 0 || M >= (1LL << 32) || !seg_off || !info || !best_fg || !best_bg || !out_rgb ||
+  if (!seg_sizes_ok(P, K) || M < 0 || M >= (1LL << 32) || !seg_off || !info || !best_fg || !best_bg || !out_rgb ||
       !out_maskid || !out_depth || !out_winner)
     return OBJNERF_EINVAL;
   if (M > 0 && (!pix || !depth || !opacity || !rgb || !near || !far)) return OBJNERF_EINVAL;
@@ -575,7 +498,7 @@ int objnerf_view_query(int64_t P, int32_t K, int64_t M, int32_t C, int32_t Q, co
                        float* out_best, int64_t n_feat, const int32_t* feat_pix, float* out_feat, int32_t workgroups,
                        void* stream) {
   (void)hipGetLastError();
-  if (Q < 1 || Q > 16 || M < 0 || M >= (1LL << 32) || !mv_sizes_ok(P, K) || C <= 0 || n_feat < 0 || workgroups < 0)
+  if (Q < 1 || Q > 16 || M < 0 || M >= (1LL << 32) || !seg_sizes_ok(P, K) || C <= 0 || n_feat < 0 || workgroups < 0)
     return OBJNERF_EINVAL;
   if (!seg_off || !winner || !heads || !heads_host || (M > 0 && (!pix || !opacity))) return OBJNERF_EINVAL;
   const bool ask = out_sim || out_label || out_best;
@@ -596,7 +519,7 @@ int objnerf_view_query(int64_t P, int32_t K, int64_t M, int32_t C, int32_t Q, co
   hipStream_t st = (hipStream_t)stream;
   // four workgroups of 4 waves per CU (33 KB of LDS each at C = 512), never more waves than 16-item chunks
   auto grid = [&](const int64_t items) {
-    int64_t G = workgroups > 0 ? (int64_t)workgroups : 4 * (int64_t)mv_num_cu();
+    int64_t G = workgroups > 0 ? (int64_t)workgroups : 4 * (int64_t)objnerf_num_cu();
     const int64_t need = cdiv(cdiv(items, 16), 4);
     return dim3((unsigned)(G > need ? need : G));
   };

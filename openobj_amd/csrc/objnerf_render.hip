@@ -60,9 +60,7 @@ extern "C" int objnerf_render_fwd(const objnerf_net* net, int64_t n, int32_t n_b
   d.u = u; d.seed = seed; d.draw = draw;
   d.depth = out_depth; d.opacity = out_opacity; d.rgb = out_rgb; d.hfeat = out_hfeat; d.z_out = out_z;
   d.L = make_layout(net->feat_dim);
-  int dev = 0, cu = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
+  const int cu = objnerf_num_cu();
   const long ngroups = (n + 15) / 16;
   const bool feat = out_hfeat != nullptr;
   const size_t lds_bytes = (size_t)img_floats(feat) * 4;

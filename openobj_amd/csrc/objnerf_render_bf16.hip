@@ -183,9 +183,7 @@ int objnerf_render_fwd_bf16(const objnerf_net* net, int64_t n, int32_t n_bins, c
   d.u = u; d.seed = seed; d.draw = draw;
   d.depth = out_depth; d.opacity = out_opacity; d.rgb = out_rgb; d.hfeat = out_hfeat; d.z_out = out_z;
   d.L = make_layout(net->feat_dim);
-  int dev = 0, cu = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
+  const int cu = objnerf_num_cu();
   const long ngroups = (n + 15) / 16;
   long G = 2L * cu;                                           // two workgroups of 4 waves per CU
   if (G * 4 > ngroups) G = (ngroups + 3) / 4;

@@ -573,17 +573,6 @@ __global__ __launch_bounds__(256) void feat_finish_kernel(const float* params, l
   }
 }
 
-int g_num_cu = 0;
-int num_cu() {
-  if (g_num_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    g_num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return g_num_cu;
-}
-
 int eval_launch(const objnerf_net* net, int32_t K, int64_t N, const float* params, int64_t p_stride,
                 const float* scale, const float* pts, const float* emb, float* out_alpha, float* out_color,
                 float* out_hfeat, float* out_clip, void* stream) {
@@ -592,7 +581,7 @@ int eval_launch(const objnerf_net* net, int32_t K, int64_t N, const float* param
   d.alpha = out_alpha; d.color = out_color; d.hfeat = out_hfeat;
   d.L = make_layout(net->feat_dim);
   const long ntiles = (N + 63) / 64;
-  long G = (2L * num_cu()) / K;
+  long G = (2L * objnerf_num_cu()) / K;
   if (G < 1) G = 1;
   if (G > ntiles) G = ntiles;
   d.G = (int)G;
@@ -642,12 +631,12 @@ int64_t objnerf_param_layout(const objnerf_net* net, int64_t offsets[OBJNERF_N_T
 // in one round when K divides it well (K = 50 -> 5 x 50 = 250 of 256); otherwise (K = 100, 130, 300 ...) more,
 // shorter workgroups in several rounds come closer to K * NT / #CU tiles per compute unit.
 static int grid_cap(int K) {
-  const int g = num_cu() / (K > 0 ? K : 1);
+  const int g = objnerf_num_cu() / (K > 0 ? K : 1);
   return g > 32 ? g : 32;
 }
 static int train_grid(int K, int NT) {
   constexpr long TILE_EQUIV = 4;
-  const int cu = num_cu();
+  const int cu = objnerf_num_cu();
   int gmax = grid_cap(K);
   if (gmax > NT) gmax = NT;
   if (gmax < 1) gmax = 1;
@@ -668,7 +657,7 @@ static int train_grid(int K, int NT) {
 // kernel (22 us per tile).  The bf16 kernel stays on the strided grid: its segment costs ~10 of its 7-us tiles, and
 // wrapping its body in the segment loop alone cost 3.5 % (measured: 2.74 -> 2.83 ms strided, 2.79 flat).
 static void choose_flat(TrainDev& d, int K, const long TILE_EQUIV) {
-  const int cu = num_cu();
+  const int cu = objnerf_num_cu();
   const long T = (long)K * d.NT;
   if (T < cu) return;
   const long share = (T + cu - 1) / cu;
@@ -826,7 +815,7 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
         (void)hipFuncSetAttribute((const void*)feat_pre_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(((FEAT_PRE_MAXC / 16) * 2 * 64 * 4 + FEAT_PRE_MAXC) * sizeof(float)));
       });
-      int gpo = 2 * num_cu() / a->K;              // workgroups per object: one round of the chip at two per compute unit
+      int gpo = 2 * objnerf_num_cu() / a->K;              // workgroups per object: one round of the chip at two per compute unit
       if (gpo < 1) gpo = 1;
       if (gpo > (a->R + 127) / 128) gpo = (a->R + 127) / 128;
       hipLaunchKernelGGL(feat_pre_kernel, dim3(gpo, a->K), dim3(512), pre_lds, st, a->params, (long)a->p_stride,
@@ -844,7 +833,7 @@ int objnerf_train_step(const objnerf_net* net, const objnerf_train_args* a, void
     if (hipGetLastError() != hipSuccess) return OBJNERF_ELAUNCH;
     // 512-d head gradient from the per-ray (fh, O, a, c): two split-K GEMMs over the rays + a small finish
     const long nr = (long)a->K * a->R;
-    int gpo = 2 * num_cu() / a->K;                // ray chunks per object: one round of the chip at two workgroups per compute unit
+    int gpo = 2 * objnerf_num_cu() / a->K;                // ray chunks per object: one round of the chip at two workgroups per compute unit
     if (gpo < 1) gpo = 1;
     if (gpo > 16) gpo = 16;
     // the partials live in the room of X1 AND X2 (adjacent in the workspace, both unused on this route): 2 K R XCOLS floats.

@@ -25,6 +25,7 @@
 // (4.7 KB + 16.6 KB; with the staging 59 KB, two workgroups per compute unit).  Above that the lane of step 1 adds to
 // global memory directly (view_compare_kernel<false>): wave-aggregated global atomics, one per wave, key and column.
 // Every accumulated value is an integer, so both paths, every grid and every arrival order give the same tables.
+#include "objnerf_device.h"
 #include "objnerf_wg.h"
 
 namespace {
@@ -228,13 +229,6 @@ __global__ void __launch_bounds__(VE_WG) view_compare_kernel(const ViewCmp a) {
   }
 }
 
-int ve_num_cu() {
-  int dev = 0, cu = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-  return cu > 0 ? cu : 256;
-}
-
 }  // namespace
 
 extern "C" {
@@ -255,7 +249,7 @@ int objnerf_view_compare(int32_t W, int32_t H, const uint8_t* rgb_r, const float
   a.id_r = id_r; a.id_g = id_g; a.lut = lut;
   a.acc = (long long*)acc; a.conf = (long long*)conf; a.ssim_map = ssim_map;
   // two workgroups fit a compute unit (LDS); four per unit in the queue keep the tail short
-  int64_t grid = workgroups > 0 ? (int64_t)workgroups : 4 * (int64_t)ve_num_cu();
+  int64_t grid = workgroups > 0 ? (int64_t)workgroups : 4 * (int64_t)objnerf_num_cu();
   if (grid > a.n_tiles) grid = a.n_tiles;
   hipStream_t st = (hipStream_t)stream;
   if (G <= VE_ROWS) hipLaunchKernelGGL(view_compare_kernel<true>, dim3((unsigned)grid), dim3(VE_WG), 0, st, a);

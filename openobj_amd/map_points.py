@@ -131,6 +131,32 @@ class _Pass:
             self.stats[self.name] = self.stats.get(self.name, 0.0) + self.e0.elapsed_time(self.e1)
 
 
+def split_arenas(objects: Sequence[MapObject], stacked, dev):
+    """The networks of a map, copied to dev: -> (ONE arena of the hidden-32 objects whose trainer stacked() admits, or None;
+    row_of {k: its row there}; own {k: an arena of one row} for every other object)."""
+    small = [k for k, o in enumerate(objects) if stacked(o.trainer)]
+    row_of = {k: row for row, k in enumerate(small)}
+    shape = lambda t: ops.NetShape(int(t.hidden_feature_size), int(t.clip_point_feature_size), t.n_unidir_funcs + 1)
+    arena = None
+    if small:
+        arena = ops.ParamArena(len(small), shape(objects[small[0]].trainer), dev)
+        with torch.no_grad():
+            for row, k in enumerate(small):
+                t = objects[k].trainer
+                arena.params[row].copy_(t.arena.params[0].to(dev))
+                arena.scale[row] = float(t.obj_scale)
+        arena.version += 1
+    own = {}
+    for k, o in enumerate(objects):
+        if k not in row_of:
+            t = o.trainer
+            own[k] = ops.ParamArena(1, shape(t), dev)
+            with torch.no_grad():
+                own[k].params.copy_(t.arena.params.to(dev))
+                own[k].scale.fill_(float(t.obj_scale))
+    return arena, row_of, own
+
+
 class MapPoints:
     def __init__(self, objects: Sequence[MapObject], device=None, bg_ids: Iterable[int] = (0,),
                  pair_budget_bytes: int = DEFAULT_PAIR_BUDGET):
@@ -161,47 +187,20 @@ class MapPoints:
         self.class_ids = torch.tensor([-1 if o.class_id is None else int(o.class_id) for o in objects], dtype=torch.int64,
                                       device=dev)
         # the hidden-32 objects in ONE arena, wider ones (the background) each on its own
-        small = [k for k, o in enumerate(objects) if int(o.trainer.hidden_feature_size) == 32]
-        self.wide = [k for k in range(self.K) if k not in set(small)]
+        self.arena, row_of, self.wide_arena = split_arenas(objects, lambda t: int(t.hidden_feature_size) == 32, dev)
+        self.wide = sorted(self.wide_arena)
         info = np.full((self.K, 2), -1, np.int32)
         info[:, 1] = np.asarray(self.is_bg, np.int32)
-        self.arena = None
-        if small:
-            self.arena = ops.ParamArena(len(small), ops.NetShape(32, self.feat_dim, objects[small[0]].trainer.n_unidir_funcs + 1), dev)
-            with torch.no_grad():
-                for row, k in enumerate(small):
-                    t = objects[k].trainer
-                    self.arena.params[row].copy_(t.arena.params[0].to(dev))
-                    self.arena.scale[row] = float(t.obj_scale)
-                    info[k, 0] = row
-            self.arena.version += 1
-        self.wide_arena = {}
-        for k in self.wide:
-            t = objects[k].trainer
-            a = ops.ParamArena(1, ops.NetShape(int(t.hidden_feature_size), self.feat_dim, t.n_unidir_funcs + 1), dev)
-            with torch.no_grad():
-                a.params.copy_(t.arena.params.to(dev))
-                a.scale.fill_(float(t.obj_scale))
-            self.wide_arena[k] = a
+        for k, row in row_of.items():
+            info[k, 0] = row
         self.info_host = info
         self.info = torch.from_numpy(info).to(dev)
 
     @classmethod
     def from_logdir(cls, logdir: str, device="cuda:0", bg_ids: Iterable[int] = (0,), **kw) -> "MapPoints":
         from . import map_vis
-        ckpt_dir = os.path.join(logdir, "ckpt")
-        ids = sorted(int(d) for d in os.listdir(ckpt_dir) if os.path.isdir(os.path.join(ckpt_dir, d)) and d.isdigit())
         objects = []
-        for obj_id in ids:
-            f = os.path.join(ckpt_dir, str(obj_id), f"obj_{obj_id}.pth")
-            if not os.path.exists(f):
-                print("ckpt not exist ", f)
-                continue
-            t, ck = map_vis.load_object(f, device)
-            box = ck.get("bbox")
-            if box is None:
-                print(f"obj {obj_id}: the checkpoint carries no box, skipped")
-                continue
+        for obj_id, t, ck, box in map_vis.iter_checkpoints(logdir, device):
             sem = ck.get("semantic_id")
             objects.append(MapObject(t, box, obj_id=obj_id, class_id=-1 if sem is None else int(sem)))
         return cls(objects, device=device, bg_ids=bg_ids, **kw)

@@ -46,7 +46,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .map_points import MapObject, _Pass
+from .map_points import MapObject, _Pass, split_arenas
 from .render_view import ViewBuffers
 
 N_BINS = 150          # Trainer.sample_points_bbox(do_eval=True), trainer.py:145-146
@@ -95,28 +95,8 @@ class MapView:
             return int(t.hidden_feature_size) == 32 and int(t.n_unidir_funcs) + 1 == 6 and \
                 int(t.clip_point_feature_size) == self.feat_dim and not bool(getattr(t, "render_bf16", False))
 
-        small = [k for k, o in enumerate(objects) if fused(o.trainer)]
-        self.row_of = {k: row for row, k in enumerate(small)}
-        self.arena = None
-        if small:
-            self.arena = ops.ParamArena(len(small), ops.NetShape(32, self.feat_dim, 6), dev)
-            with torch.no_grad():
-                for row, k in enumerate(small):
-                    t = objects[k].trainer
-                    self.arena.params[row].copy_(t.arena.params[0].to(dev))
-                    self.arena.scale[row] = float(t.obj_scale)
-            self.arena.version += 1
-        self.own_arena, self.own_bf16 = {}, {}
-        for k, o in enumerate(objects):
-            if k in self.row_of:
-                continue
-            t = o.trainer
-            a = ops.ParamArena(1, ops.NetShape(int(t.hidden_feature_size), int(t.clip_point_feature_size),
-                                               t.n_unidir_funcs + 1), dev)
-            with torch.no_grad():
-                a.params.copy_(t.arena.params.to(dev))
-                a.scale.fill_(float(t.obj_scale))
-            self.own_arena[k], self.own_bf16[k] = a, bool(getattr(t, "render_bf16", False))
+        self.arena, self.row_of, self.own_arena = split_arenas(objects, fused, dev)
+        self.own_bf16 = {k: bool(getattr(objects[k].trainer, "render_bf16", False)) for k in self.own_arena}
         # out_clip of every object (of_w [C, H], of_b [C]) as tensors of their own: objnerf_view_query reads them with
         # 128-bit loads, which an arena offset does not promise
         self.heads = []
@@ -133,19 +113,8 @@ class MapView:
         """The checkpoints of <logdir>/ckpt in ascending id order (map_vis.load_object).  semantic_ids: write each
         object's semantic_id into the mask-id image where class_of does not name it."""
         from . import map_vis
-        ckpt_dir = os.path.join(logdir, "ckpt")
-        ids = sorted(int(d) for d in os.listdir(ckpt_dir) if os.path.isdir(os.path.join(ckpt_dir, d)) and d.isdigit())
         objects, class_of = [], dict(class_of or {})
-        for obj_id in ids:
-            f = os.path.join(ckpt_dir, str(obj_id), f"obj_{obj_id}.pth")
-            if not os.path.exists(f):
-                print("ckpt not exist ", f)
-                continue
-            t, ck = map_vis.load_object(f, device)
-            box = ck.get("bbox")
-            if box is None:
-                print(f"obj {obj_id}: the checkpoint carries no box, skipped")
-                continue
+        for obj_id, t, ck, box in map_vis.iter_checkpoints(logdir, device):
             sem = ck.get("semantic_id")
             if semantic_ids and sem is not None:
                 class_of.setdefault(obj_id, int(sem))

@@ -49,27 +49,37 @@ def load_object(ckpt_file: str, device: str):
     return t, ck
 
 
+def iter_checkpoints(logdir: str, device: str):
+    """The objects of <logdir>/ckpt/<id>/obj_<id>.pth in ascending id order that have a checkpoint with a box (the others
+    are skipped with a message) -> (obj_id, Trainer, checkpoint dict, box), one object loaded at a time."""
+    ckpt_dir = os.path.join(logdir, "ckpt")
+    ids = sorted(int(d) for d in os.listdir(ckpt_dir) if os.path.isdir(os.path.join(ckpt_dir, d)) and d.isdigit())
+
+    def load():             # (the directory is listed at the call, the objects are loaded as the caller iterates)
+        for obj_id in ids:
+            f = os.path.join(ckpt_dir, str(obj_id), f"obj_{obj_id}.pth")
+            if not os.path.exists(f):
+                print("ckpt not exist ", f)
+                continue
+            t, ck = load_object(f, device)
+            box = ck.get("bbox")
+            if box is None:
+                print(f"obj {obj_id}: the checkpoint carries no box, skipped")
+                continue
+            yield obj_id, t, ck, box
+    return load()
+
+
 COMPACT_FILE = "map_vis_compact.pkl.gz"
 DENSE_FILE = "map_vis.pkl.gz"
 
 
 def export(logdir: str, grid_dim: int = 128, device: str = "cuda:0", obj_center: float = 0.0,
            compact: bool = False) -> Optional[Dict]:
-    ckpt_dir = os.path.join(logdir, "ckpt")
-    ids = sorted(int(d) for d in os.listdir(ckpt_dir) if os.path.isdir(os.path.join(ckpt_dir, d)) and d.isdigit())
     ply_dir = os.path.join(logdir, "map_vis")
     os.makedirs(ply_dir, exist_ok=True)
     all_obj = {}
-    for obj_id in ids:
-        f = os.path.join(ckpt_dir, str(obj_id), f"obj_{obj_id}.pth")
-        if not os.path.exists(f):
-            print("ckpt not exist ", f)
-            continue
-        t, ck = load_object(f, device)
-        box = ck.get("bbox")
-        if box is None:
-            print(f"obj {obj_id}: the checkpoint carries no box, skipped")
-            continue
+    for obj_id, t, ck, box in iter_checkpoints(logdir, device):
         res = t.meshing(box, torch.tensor(obj_center), grid_dim=grid_dim, save_pcd=False, save_mesh=True,
                         if_color=True, if_part=True, part_compact=compact)
         if res is None or len(res) != 3 or res[1] is None:

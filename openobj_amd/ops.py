@@ -1571,6 +1571,26 @@ def mappoints_check_pairs(M: int) -> int:
     return int(M)
 
 
+def _csr_count(unit: str, what: str, n: int, K: int, *inputs):
+    """objnerf_<unit>_workspace_bytes / _count over n items and K boxes (objnerf_segments.h) -> (seg_off int64 [K + 1] on
+    the device, the same as a list, the workspace objnerf_<unit>_emit needs).  The one host sync: seg_off is read back."""
+    nbytes = int(getattr(lib(), f"objnerf_{unit}_workspace_bytes")(n, K))
+    if nbytes == 0:
+        raise _lib.ObjnerfError(f"{unit}_count: {what} = {n}, K = {K} outside the supported range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=inputs[0].device)
+    seg_off = torch.empty(K + 1, dtype=torch.int64, device=inputs[0].device)
+    check(getattr(lib(), f"objnerf_{unit}_count")(n, K, *[_ptr(t) for t in inputs], _ptr(ws), nbytes, _ptr(seg_off),
+                                                   _stream()), f"objnerf_{unit}_count")
+    return seg_off, [int(x) for x in seg_off.tolist()], ws
+
+
+def _csr_emit(unit: str, n: int, K: int, inputs, ws: torch.Tensor, M: int, outs):
+    """objnerf_<unit>_emit into outs (M entries each; no pointer is passed for an empty one)."""
+    check(getattr(lib(), f"objnerf_{unit}_emit")(n, K, *[_ptr(t) for t in inputs], _ptr(ws), int(ws.numel()), M,
+                                                  *[_ptr(o) if M else None for o in outs], _stream()), f"objnerf_{unit}_emit")
+    return outs
+
+
 def mappoints_count(pts: torch.Tensor, boxes: torch.Tensor):
     """pts [N, 3], boxes [K, 16] (centre | R row-major | extent / 2 | obj_center) -> (seg_off int64 [K + 1] on the device,
     the same as a list, the workspace mappoints_emit needs).  Synchronises once: seg_off is read back, so that the caller
@@ -1578,15 +1598,7 @@ def mappoints_count(pts: torch.Tensor, boxes: torch.Tensor):
     pts, boxes = _req(pts, torch.float32, "pts"), _req(boxes, torch.float32, "boxes")
     if pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] < 1 or boxes.dim() != 2 or boxes.shape[1] != 16 or boxes.shape[0] < 1:
         raise _lib.ObjnerfError("mappoints_count: pts [N >= 1, 3], boxes [K >= 1, 16]")
-    N, K, dev = int(pts.shape[0]), int(boxes.shape[0]), pts.device
-    nbytes = int(lib().objnerf_mappoints_workspace_bytes(N, K))
-    if nbytes == 0:
-        raise _lib.ObjnerfError(f"mappoints_count: N = {N}, K = {K} outside the supported range")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    seg_off = torch.empty(K + 1, dtype=torch.int64, device=dev)
-    check(lib().objnerf_mappoints_count(N, K, _ptr(pts), _ptr(boxes), _ptr(ws), nbytes, _ptr(seg_off), _stream()),
-          "objnerf_mappoints_count")
-    return seg_off, [int(x) for x in seg_off.tolist()], ws                  # the one host sync
+    return _csr_count("mappoints", "N", int(pts.shape[0]), int(boxes.shape[0]), pts, boxes)
 
 
 def mappoints_emit(pts: torch.Tensor, boxes: torch.Tensor, ws: torch.Tensor, M: int) -> torch.Tensor:
@@ -1594,10 +1606,8 @@ def mappoints_emit(pts: torch.Tensor, boxes: torch.Tensor, ws: torch.Tensor, M: 
     inside an object."""
     pts, boxes = _req(pts, torch.float32, "pts"), _req(boxes, torch.float32, "boxes")
     M = mappoints_check_pairs(M)
-    pair_pt = torch.empty(M, dtype=torch.int32, device=pts.device)
-    check(lib().objnerf_mappoints_emit(int(pts.shape[0]), int(boxes.shape[0]), _ptr(pts), _ptr(boxes), _ptr(ws),
-                                       int(ws.numel()), M, _ptr(pair_pt) if M else None, _stream()), "objnerf_mappoints_emit")
-    return pair_pt
+    return _csr_emit("mappoints", int(pts.shape[0]), int(boxes.shape[0]), (pts, boxes), ws, M,
+                     (torch.empty(M, dtype=torch.int32, device=pts.device),))[0]
 
 
 def mappoints_candidates(pts: torch.Tensor, boxes: torch.Tensor):
@@ -2117,15 +2127,7 @@ def view_rays_count(T_WC: torch.Tensor, boxes: torch.Tensor, dirs_C: torch.Tenso
     workspace view_rays_emit needs); an object with at most one hit has an empty segment.  Synchronises once: seg_off is
     read back, so that the outputs of M = seg[-1] entries can be allocated to their exact size."""
     T_WC, boxes, dirs_C = _view_inputs(T_WC, boxes, dirs_C, "view_rays_count")
-    P, K, dev = int(dirs_C.shape[0]), int(boxes.shape[0]), dirs_C.device
-    nbytes = int(lib().objnerf_view_rays_workspace_bytes(P, K))
-    if nbytes == 0:
-        raise _lib.ObjnerfError(f"view_rays_count: P = {P}, K = {K} outside the supported range")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    seg_off = torch.empty(K + 1, dtype=torch.int64, device=dev)
-    check(lib().objnerf_view_rays_count(P, K, _ptr(T_WC), _ptr(boxes), _ptr(dirs_C), _ptr(ws), nbytes, _ptr(seg_off),
-                                        _stream()), "objnerf_view_rays_count")
-    return seg_off, [int(x) for x in seg_off.tolist()], ws                  # the one host sync
+    return _csr_count("view_rays", "P", int(dirs_C.shape[0]), int(boxes.shape[0]), T_WC, boxes, dirs_C)
 
 
 def view_rays_emit(T_WC: torch.Tensor, boxes: torch.Tensor, dirs_C: torch.Tensor, ws: torch.Tensor, M: int):
@@ -2136,13 +2138,9 @@ def view_rays_emit(T_WC: torch.Tensor, boxes: torch.Tensor, dirs_C: torch.Tensor
     if M > VIEW_MAX_ENTRIES:
         raise _lib.ObjnerfError(f"view_rays_emit: {M} (pixel, object) entries do not fit 32 bits")
     dev = dirs_C.device
-    pix = torch.empty(M, dtype=torch.int32, device=dev)
-    dirs_W, near, far = torch.empty(M, 3, device=dev), torch.empty(M, device=dev), torch.empty(M, device=dev)
-    p = (lambda t: _ptr(t) if M else None)
-    check(lib().objnerf_view_rays_emit(int(dirs_C.shape[0]), int(boxes.shape[0]), _ptr(T_WC), _ptr(boxes), _ptr(dirs_C),
-                                       _ptr(ws), int(ws.numel()), M, p(pix), p(dirs_W), p(near), p(far), _stream()),
-          "objnerf_view_rays_emit")
-    return pix, dirs_W, near, far
+    return _csr_emit("view_rays", int(dirs_C.shape[0]), int(boxes.shape[0]), (T_WC, boxes, dirs_C), ws, M,
+                     (torch.empty(M, dtype=torch.int32, device=dev), torch.empty(M, 3, device=dev),
+                      torch.empty(M, device=dev), torch.empty(M, device=dev)))
 
 
 def render_tiles(rows, tile_groups: int = VIEW_TILE_GROUPS) -> np.ndarray:

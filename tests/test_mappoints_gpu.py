@@ -77,6 +77,17 @@ def test_candidate_lists_are_the_specification(dev, labelled):
     assert seg_off.dtype == torch.int64 and pair_pt.dtype == torch.int32
     assert torch.equal(cpu(seg_off), ref["seg_off"]) and seg == ref["seg_off"].tolist()
     assert torch.equal(cpu(pair_pt), ref["pair_pt"])
+    # the count blocks of 256 points below, at and above a boundary and across several, over [A, EMPTY, B]: the middle
+    # segment is empty, so the scan and the emit step over it.  Points drawn from the cloud with repetition (a candidate
+    # list does not care), the specification's mask gathered for them.
+    rs = np.random.RandomState(5)
+    for n in (255, 256, 257, 1025):
+        idx = rs.randint(0, len(ref["points"]), n)
+        cand = ref["cand"][:3, torch.from_numpy(idx)]
+        assert bool(cand[0].any()) and not bool(cand[1].any()) and bool(cand[2].any())
+        want_off, want_pt = U.candidate_lists(cand)
+        seg_off, seg, pair_pt = ops.mappoints_candidates(torch.from_numpy(ref["points"][idx]).to(dev), mp.boxes[:3].contiguous())
+        assert torch.equal(cpu(seg_off), want_off) and seg == want_off.tolist() and torch.equal(cpu(pair_pt), want_pt), n
 
 
 def test_candidate_lists_of_one_point(dev, labelled):
