@@ -1139,6 +1139,64 @@ int objnerf_mapalign_accumulate(int64_t N, const float* pts, const int32_t* obj,
                                 const double* pivot, double tau, double g_min, void* ws, size_t ws_bytes, double* out,
                                 void* stream);
 
+/* The mask front end: the image work of the reference's maskclustering/mask_gen.py between its four models
+ * (objnerf_maskprep.hip; openobj_amd/mask_prep.py).  Added under ABI 14: the entries below are purely
+ * additive, so OBJNERF_ABI_VERSION stays 14.  Painting the id image (mask_gen.py:289-295) is objnerf_part_index on the
+ * rank-permuted masks.  1 <= F <= 65535 frames, 1 <= H, W <= 32767 (a squared pixel distance fits 31 bits).
+ *
+ * objnerf_cc_label (split_mask's cv2.connectedComponentsWithStats, :168, for every mask of F frames at once):
+ * ids [F][H][W] int32 -> label [F][H][W] int32, 8-connectivity between pixels of EQUAL non-zero id; the label is the flat
+ * index y * W + x inside the frame of the component's first pixel in raster order, -1 where the id is 0.  Union-find over
+ * 32 x 32 tiles in LDS, a merge of the tile borders, a flatten: the root of a component is its smallest index whatever
+ * the order of the unions, so two calls write the same bytes.
+ *
+ * objnerf_cc_table: the components of every frame in raster order of their first pixel.  comp_off [F + 1] int64 (device),
+ * table [cap][8] int32 rows {first pixel, id, area, x0, y0, x1, y1, frame} (x0 / y0 the smallest column / row, x1 / y1
+ * the largest plus one: min_rect_bbox, :125-137), slot [F][H][W] int32 = the row of a component at its first pixel (-1
+ * elsewhere).  The order comes from count / scan / emit without atomics; area and box are integer atomics.  Rows past
+ * cap are not written: the caller compares comp_off [F] with cap and calls again with a larger one.
+ * ws: objnerf_cc_table_workspace_bytes(F, H, W).
+ *
+ * objnerf_cc_boundary: sel [rows] int32 maps a table row to a list s in [0, S) or -1.  boff [S + 1] int32 = the CSR
+ * offsets of the lists, bpix [bcap] uint32 = (y << 16) | x of the pixels of the selected components that have a
+ * 4-neighbour outside the component; cursor [S] int32 is scratch.  The order INSIDE a list is whatever the atomics give:
+ * only order-free reductions may read it.  Entries past bcap are dropped: bcap >= the selected components' areas holds all.
+ *
+ * objnerf_cc_gaps (closest_distance, :139-160, without its random tenth): pairs [P][2] int32 of lists -> d2 [P] int32,
+ * the exact minimum squared Euclidean distance between the two pixel sets (the closest pair lies on the boundaries).
+ * Brute force over LDS tiles of the second list, one atomicMin per workgroup; INT32_MAX for an empty list.
+ *
+ * objnerf_cc_relabel (:334-349): final_id [rows] int32 = the id each component ends with (0 = dropped) -> out_ids
+ * [F][H][W] int32 and stats [F][256][8] int32 rows in the table's layout (area, box of every final id; final ids lie in
+ * [0, 256), others are written as 0).
+ *
+ * objnerf_clip_crops (:495-516, CLIP's preprocessing of the padded crops): image [H][W][3] uint8, n crops.  PIL's two-pass
+ * integer bicubic resample (ImagingResample: horizontal first into a uint8 intermediate, clip8((2^21 + sum) >> 22) a pass)
+ * with the caller's coefficient tables, for the 224 x 224 pixels the centre crop keeps; then v / 255.0f, (x - mean) / std
+ * in fp32 -> out [n][3][224][224], channel c of the output = channel c of the image.
+ *   desc [n][8] int32  x0, y0 (the crop's origin in the image), w, h, row0, nrows (the crop rows the vertical pass reads:
+ *                      the intermediate's rows), hcopy, vcopy (>= 0: that pass is skipped, output column / row o is crop
+ *                      column / row hcopy + o / vcopy + o; -1: resample)
+ *   hb [n][224][2], hk [n][224][kh]   per kept output column: first crop column and count (<= kh), 22-bit coefficients
+ *   vb, vk (kv)                       the same for the kept output rows
+ *   tmp [n][tmp_rows][224][3] uint8   the intermediate, tmp_rows >= every nrows
+ * Every index is clamped into the image, the tables and tmp. */
+size_t objnerf_cc_table_workspace_bytes(int32_t F, int32_t H, int32_t W);
+int objnerf_cc_label(int32_t F, int32_t H, int32_t W, const int32_t* ids, int32_t* label, void* stream);
+int objnerf_cc_table(int32_t F, int32_t H, int32_t W, const int32_t* ids, const int32_t* label, void* ws, size_t ws_bytes,
+                     int64_t cap, int64_t* comp_off, int32_t* table, int32_t* slot, void* stream);
+int objnerf_cc_boundary(int32_t F, int32_t H, int32_t W, const int32_t* label, const int32_t* slot, const int32_t* sel,
+                        int64_t rows, int32_t S, int32_t* boff, int32_t* cursor, uint32_t* bpix, int64_t bcap,
+                        void* stream);
+int objnerf_cc_gaps(int32_t P, const int32_t* pairs, int32_t S, const int32_t* boff, const uint32_t* bpix, int64_t bcap,
+                    int32_t* d2, void* stream);
+int objnerf_cc_relabel(int32_t F, int32_t H, int32_t W, const int32_t* label, const int32_t* slot, const int32_t* final_id,
+                       int64_t rows, int32_t* out_ids, int32_t* stats, void* stream);
+#define OBJNERF_CLIP_SIDE 224
+int objnerf_clip_crops(int32_t n, int32_t H, int32_t W, const uint8_t* image, const int32_t* desc, int32_t kh,
+                       const int32_t* hb, const int32_t* hk, int32_t kv, const int32_t* vb, const int32_t* vk,
+                       int32_t tmp_rows, uint8_t* tmp, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -380,6 +380,20 @@ SIGNATURES = {
     "objnerf_mapalign_accumulate": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.POINTER(C.c_double), C.c_double, C.c_double, C.c_void_p, C.c_size_t,
                                               C.c_void_p, C.c_void_p]),
+    # the mask front end (objnerf_maskprep.hip): additive, still ABI 14
+    "objnerf_cc_table_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "objnerf_cc_label": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_cc_table": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_cc_boundary": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "objnerf_cc_gaps": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                  C.c_void_p]),
+    "objnerf_cc_relabel": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "objnerf_clip_crops": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,6 +1,8 @@
-// The object CSR of the map units, written once: seg_off [K + 1] over the K objects of a map, entries object-major and
-// ascending inside an object.  objnerf_mappoints.hip (candidate points), objnerf_mapview.hip (candidate
-// rays) and objnerf_mapalign.hip (field gradients over the candidate points) all work on it.
+// The segment CSR, written once: seg_off [K + 1] over K segments, entries segment-major and ascending inside a segment.
+// For the map units the segments are the K objects of a map: objnerf_mappoints.hip
+// (candidate points), objnerf_mapview.hip (candidate rays) and objnerf_mapalign.hip (field gradients over the candidate
+// points).  objnerf_maskprep.hip uses the candidate CSR alone, with the frames of a batch as segments:
+// the roots of the connected components in raster order.
 //
 //   seg_of                     the object of an entry.
 //   seg_csr_count / _emit      THE CANDIDATE CSR: count / scan / emit over the primitives of objnerf_wg.h, templated on a

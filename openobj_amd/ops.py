@@ -818,6 +818,108 @@ def part_dense(index: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------- the mask front end (objnerf_maskprep.hip)
+CC_ROW = 8          # ints per row of the component / final-id tables: first pixel, id, area, x0, y0, x1, y1, frame
+CC_MAX_SIDE = 32767
+CLIP_SIDE = 224
+
+
+def _id_images(ids: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    if ids.dim() != 3 or not 1 <= ids.shape[0] <= 65535 or not (1 <= ids.shape[1] <= CC_MAX_SIDE and
+                                                                1 <= ids.shape[2] <= CC_MAX_SIDE):
+        raise ObjnerfError(f"{what}: [F, H, W] with F <= 65535 and H, W <= {CC_MAX_SIDE} expected")
+    return int(ids.shape[0]), int(ids.shape[1]), int(ids.shape[2])
+
+
+def cc_label(ids: torch.Tensor) -> torch.Tensor:
+    """objnerf_cc_label: ids int32 [F, H, W] -> int32 [F, H, W], per pixel the flat index (in its frame) of the first pixel
+    of its 8-connected component of equal non-zero id, -1 where the id is 0."""
+    ids = _req(ids, torch.int32, "ids")
+    F, H, W = _id_images(ids, "cc_label")
+    label = torch.empty_like(ids)
+    check(lib().objnerf_cc_label(F, H, W, _ptr(ids), _ptr(label), _stream()), "objnerf_cc_label")
+    return label
+
+
+def cc_table(ids: torch.Tensor, label: torch.Tensor, cap: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """objnerf_cc_table -> (packed int64 [F + 1 + 4 * cap]: comp_off [F + 1], then the table's [cap, 8] int32 rows, so
+    that one copy brings both to the host; slot int32 [F, H, W])."""
+    ids, label = _req(ids, torch.int32, "ids"), _req(label, torch.int32, "label")
+    F, H, W = _id_images(ids, "cc_table")
+    if label.shape != ids.shape or label.device != ids.device or cap < 1:
+        raise ObjnerfError("cc_table: label must match ids; cap >= 1")
+    dev = ids.device
+    nbytes = int(lib().objnerf_cc_table_workspace_bytes(F, H, W))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    packed = torch.zeros(F + 1 + (CC_ROW // 2) * cap, dtype=torch.int64, device=dev)
+    slot = torch.empty_like(ids)
+    check(lib().objnerf_cc_table(F, H, W, _ptr(ids), _ptr(label), _ptr(ws), nbytes, int(cap), _ptr(packed),
+                                 packed.data_ptr() + 8 * (F + 1), _ptr(slot), _stream()), "objnerf_cc_table")
+    return packed, slot
+
+
+def cc_boundary(label: torch.Tensor, slot: torch.Tensor, sel: torch.Tensor, S: int, bcap: int):
+    """objnerf_cc_boundary: sel int32 [rows] (component row -> list in [0, S) or -1) -> (boff int32 [S + 1], bpix int32
+    [bcap] holding (y << 16) | x; unordered inside a list)."""
+    label, slot, sel = _req(label, torch.int32, "label"), _req(slot, torch.int32, "slot"), _req(sel, torch.int32, "sel")
+    F, H, W = _id_images(label, "cc_boundary")
+    if slot.shape != label.shape or sel.dim() != 1 or sel.numel() < 1 or S < 1 or bcap < 1:
+        raise ObjnerfError("cc_boundary: slot must match label; sel [rows], S >= 1, bcap >= 1")
+    dev = label.device
+    boff = torch.empty(S + 1, dtype=torch.int32, device=dev)
+    cursor = torch.empty(S, dtype=torch.int32, device=dev)
+    bpix = torch.empty(int(bcap), dtype=torch.int32, device=dev)
+    check(lib().objnerf_cc_boundary(F, H, W, _ptr(label), _ptr(slot), _ptr(sel), sel.numel(), int(S), _ptr(boff),
+                                    _ptr(cursor), _ptr(bpix), int(bcap), _stream()), "objnerf_cc_boundary")
+    return boff, bpix
+
+
+def cc_gaps(pairs: torch.Tensor, boff: torch.Tensor, bpix: torch.Tensor) -> torch.Tensor:
+    """objnerf_cc_gaps: pairs int32 [P, 2] of boundary lists -> int32 [P], the exact minimum squared distance."""
+    pairs, boff, bpix = _req(pairs, torch.int32, "pairs"), _req(boff, torch.int32, "boff"), _req(bpix, torch.int32, "bpix")
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1 or boff.numel() < 2:
+        raise ObjnerfError("cc_gaps: pairs [P, 2] with P >= 1 expected")
+    d2 = torch.empty(pairs.shape[0], dtype=torch.int32, device=pairs.device)
+    check(lib().objnerf_cc_gaps(pairs.shape[0], _ptr(pairs), boff.numel() - 1, _ptr(boff), _ptr(bpix), bpix.numel(),
+                                _ptr(d2), _stream()), "objnerf_cc_gaps")
+    return d2
+
+
+def cc_relabel(label: torch.Tensor, slot: torch.Tensor, final_id: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """objnerf_cc_relabel: final_id int32 [rows] per component -> (ids int32 [F, H, W], stats int32 [F, 256, 8])."""
+    label, slot = _req(label, torch.int32, "label"), _req(slot, torch.int32, "slot")
+    final_id = _req(final_id, torch.int32, "final_id")
+    F, H, W = _id_images(label, "cc_relabel")
+    if slot.shape != label.shape or final_id.dim() != 1 or final_id.numel() < 1:
+        raise ObjnerfError("cc_relabel: slot must match label; final_id [rows]")
+    out = torch.empty_like(label)
+    stats = torch.empty(F, 256, CC_ROW, dtype=torch.int32, device=label.device)
+    check(lib().objnerf_cc_relabel(F, H, W, _ptr(label), _ptr(slot), _ptr(final_id), final_id.numel(), _ptr(out),
+                                   _ptr(stats), _stream()), "objnerf_cc_relabel")
+    return out, stats
+
+
+def clip_crops(image: torch.Tensor, desc: torch.Tensor, hb: torch.Tensor, hk: torch.Tensor, vb: torch.Tensor,
+               vk: torch.Tensor, tmp_rows: int) -> torch.Tensor:
+    """objnerf_clip_crops: image uint8 [H, W, 3]; desc int32 [n, 8]; hb / vb int32 [n, 224, 2]; hk / vk int32
+    [n, 224, k] (include/objnerf_hip.h) -> fp32 [n, 3, 224, 224]."""
+    image = _req(image, torch.uint8, "image")
+    desc, hb, hk, vb, vk = (_req(t, torch.int32, nm) for t, nm in ((desc, "desc"), (hb, "hb"), (hk, "hk"), (vb, "vb"),
+                                                                    (vk, "vk")))
+    n = int(desc.shape[0])
+    if image.dim() != 3 or image.shape[2] != 3 or desc.shape != (n, 8) or n < 1 or hb.shape != (n, CLIP_SIDE, 2) or \
+            vb.shape != (n, CLIP_SIDE, 2) or hk.shape[:2] != (n, CLIP_SIDE) or vk.shape[:2] != (n, CLIP_SIDE) or \
+            hk.dim() != 3 or vk.dim() != 3 or tmp_rows < 1:
+        raise ObjnerfError("clip_crops: image [H, W, 3], desc [n, 8], bounds [n, 224, 2], coefficients [n, 224, k]")
+    dev = image.device
+    tmp = torch.empty(n, int(tmp_rows), CLIP_SIDE, 3, dtype=torch.uint8, device=dev)
+    out = torch.empty(n, 3, CLIP_SIDE, CLIP_SIDE, dtype=torch.float32, device=dev)
+    check(lib().objnerf_clip_crops(n, image.shape[0], image.shape[1], _ptr(image), _ptr(desc), hk.shape[2], _ptr(hb),
+                                   _ptr(hk), vk.shape[2], _ptr(vb), _ptr(vk), int(tmp_rows), _ptr(tmp), _ptr(out),
+                                   _stream()), "objnerf_clip_crops")
+    return out
+
+
 def _seed_of(seed):
     return (torch.initial_seed() if seed is None else int(seed)) & (2 ** 64 - 1)
 
