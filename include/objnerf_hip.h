@@ -1197,6 +1197,58 @@ int objnerf_clip_crops(int32_t n, int32_t H, int32_t W, const uint8_t* image, co
                        const int32_t* hb, const int32_t* hk, int32_t kv, const int32_t* vb, const int32_t* vk,
                        int32_t tmp_rows, uint8_t* tmp, float* out, void* stream);
 
+/* A navigation volume of the map (objnerf_mapvolume.hip; openobj_amd/map_volume.py).  Added under ABI 14:
+ * the entries below are purely additive, so OBJNERF_ABI_VERSION stays 14.  A grid of nx x ny x nz voxels, every axis in
+ * [1, 1024] and at most 2^31 - 1 voxels (EINVAL otherwise), idx = (z * ny + y) * nx + x; label [nz][ny][nx] int32, a voxel
+ * is OCCUPIED iff label >= 0.  All volume data is integer, every reduction a minimum over keys that no two candidates
+ * share: two calls write the same bytes.  Nothing is allocated.
+ *
+ * objnerf_volume_centres: out [nzs][ny][nx][3] fp32, the centres of the z-planes [z0, z0 + nzs): per component
+ * origin + (float(i) + 0.5f) * voxel, one fp32 multiply and one fp32 add.  origin: a HOST array of 3 floats.
+ *
+ * objnerf_volume_project: the axis (0 = x, 1 = y, 2 = z) collapsed to length 1: out = the label of the occupied voxel with
+ * the lowest index along the axis in every column, -1 for a column without one.
+ *
+ * objnerf_volume_clearance: dist2 [nz][ny][nx] int32 = the smallest dx^2 + dy^2 + dz^2 (voxel units) to an occupied voxel,
+ * site = the linear index of the occupied voxel at that distance, the LOWEST index among several; an occupied voxel has
+ * 0 and its own index; without an occupied voxel anywhere INT32_MAX and -1.  Three passes, x, y, z, each the
+ * lexicographic minimum of (partial dist2, site) over the line; tmp_dist2 / tmp_site: two more volumes, the middle pass's
+ * output (distinct from dist2 / site).
+ *
+ * objnerf_volume_reach_rounds: n_rounds relaxation rounds of the 26-connected path cost (weights 3 / 4 / 5 for a face /
+ * edge / corner move) through TRAVERSABLE voxels, label < 0 and dist2 >= r2.  cost [nz][ny][nx] uint32, 0xFFFFFFFF =
+ * not reached: the caller fills it, writes 0 at the start voxel and 1 at the start voxel's tile in active [2][T] int32
+ * (T = objnerf_volume_reach_tiles, tiles of 8 x 8 x 8, tile index (tz * nty + ty) * ntx + tx; all else 0) before round 0.
+ * Round round0 + r reads active [(round0 + r) & 1], clears what it read, flags in the other half the tiles whose halo it
+ * changed, and writes 1 to changed [r] (zeroed by the caller) iff it lowered a cost.  A round that lowers nothing is the
+ * last: every later one is empty.  No workgroup waits for another and every in-kernel loop is bounded by the tile size.
+ * The caller keeps 5 x (traversable voxels) below 2^32 - 6, so that no cost can wrap.
+ *
+ * objnerf_volume_goals: table [K] uint64, FILLED WITH ALL ONES by the caller; a traversable voxel u with a finite cost
+ * offers dist2 [u] << 32 | u to row label [site [u]]: the row's minimum is the reachable voxel that comes closest to the
+ * object, the lowest index among equals.
+ *
+ * objnerf_volume_paths: G goal voxels -> out [G][cap] int32, the voxels from the goal back to the start, and len [G]: the
+ * number of voxels, NEGATIVE when it exceeds cap (nothing is written past cap), 0 for a goal outside the grid, not
+ * traversable or not reached.  The predecessor of u is the first neighbour v in the order (dz, dy, dx) over {-1, 0, 1}^3,
+ * dz slowest, the centre left out, that lies in the grid, is traversable and has cost [v] + w(v, u) == cost [u]; at most
+ * cost [goal] / 3 + 1 steps. */
+int objnerf_volume_centres(int32_t nx, int32_t ny, int32_t nz, int32_t z0, int32_t nzs, const float* origin, float voxel,
+                           float* out, void* stream);
+int objnerf_volume_project(int32_t nx, int32_t ny, int32_t nz, int32_t axis, const int32_t* label, int32_t* out,
+                           void* stream);
+int objnerf_volume_clearance(int32_t nx, int32_t ny, int32_t nz, const int32_t* label, int32_t* dist2, int32_t* site,
+                             int32_t* tmp_dist2, int32_t* tmp_site, void* stream);
+int64_t objnerf_volume_reach_tiles(int32_t nx, int32_t ny, int32_t nz);
+int objnerf_volume_reach_rounds(int32_t nx, int32_t ny, int32_t nz, const int32_t* label, const int32_t* dist2, int32_t r2,
+                                uint32_t* cost, int32_t* active, int32_t round0, int32_t n_rounds, int32_t* changed,
+                                void* stream);
+int objnerf_volume_goals(int32_t nx, int32_t ny, int32_t nz, int32_t K, const int32_t* label, const int32_t* dist2,
+                         const int32_t* site, const uint32_t* cost, int32_t r2, uint64_t* table, void* stream);
+int objnerf_volume_paths(int32_t nx, int32_t ny, int32_t nz, const int32_t* label, const int32_t* dist2, int32_t r2,
+                         const uint32_t* cost, int32_t G, const int32_t* goals, int32_t cap, int32_t* out, int32_t* len,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2477,3 +2477,139 @@ def view_compare(rgb_r: torch.Tensor, depth_r: torch.Tensor, id_r: torch.Tensor,
                                      _ptr(id_g), _ptr(lut) if n_lut else None, n_lut, G, _ptr(acc), _ptr(conf),
                                      _ptr(ssim_map), int(_workgroups), _stream()), "objnerf_view_compare")
     return ssim_map
+
+
+# ---------------------------------------------------------------------------------------------------
+# a navigation volume of the map (objnerf_mapvolume.hip; map_volume.MapVolume drives these).  dims = (nx, ny, nz), volumes
+# are [nz, ny, nx]; cost is kept as int32 storage of the unsigned values (-1 = 0xFFFFFFFF, not reached)
+VOLUME_MAX_AXIS = 1024
+VOLUME_MAX_VOXELS = 2 ** 31 - 1
+VOLUME_ROUND_BATCH = 16
+
+
+def volume_check_dims(dims) -> Tuple[int, int, int]:
+    d = tuple(int(v) for v in dims)
+    if len(d) != 3 or min(d) < 1 or max(d) > VOLUME_MAX_AXIS or d[0] * d[1] * d[2] > VOLUME_MAX_VOXELS:
+        raise ObjnerfError(f"map volume: dims {d}: every axis in [1, {VOLUME_MAX_AXIS}], at most 2^31 - 1 voxels")
+    return d
+
+
+def _volume(t: torch.Tensor, dims, name: str) -> torch.Tensor:
+    t = _req(t, torch.int32, name)
+    if tuple(t.shape) != (dims[2], dims[1], dims[0]):
+        raise ObjnerfError(f"map volume: {name} [{dims[2]}, {dims[1]}, {dims[0]}], got {tuple(t.shape)}")
+    return t
+
+
+def volume_centres(dims, origin, voxel: float, z0: int, nzs: int, device) -> torch.Tensor:
+    """The fp32 centres [nzs * ny * nx, 3] of the z-planes [z0, z0 + nzs): origin + (float(i) + 0.5f) * voxel."""
+    nx, ny, nz = volume_check_dims(dims)
+    if not (0 <= z0 and 0 <= nzs and z0 + nzs <= nz) or not float(voxel) > 0:
+        raise ObjnerfError(f"volume_centres: planes [{z0}, {z0 + nzs}) of {nz}, voxel {voxel}")
+    out = torch.empty(nzs * ny * nx, 3, device=device)
+    org = (C.c_float * 3)(*[float(v) for v in origin])
+    check(lib().objnerf_volume_centres(nx, ny, nz, int(z0), int(nzs), org, float(voxel), _ptr(out) if nzs else None,
+                                       _stream()), "objnerf_volume_centres")
+    return out
+
+
+def volume_project(label: torch.Tensor, dims, axis: int) -> torch.Tensor:
+    """label [nz, ny, nx] -> the axis (0 = x, 1 = y, 2 = z) collapsed to length 1: the first occupied label of a column."""
+    nx, ny, nz = volume_check_dims(dims)
+    label = _volume(label, (nx, ny, nz), "label")
+    if axis not in (0, 1, 2):
+        raise ObjnerfError(f"volume_project: axis {axis}")
+    od = [nx, ny, nz]
+    od[axis] = 1
+    out = torch.empty(od[2], od[1], od[0], dtype=torch.int32, device=label.device)
+    check(lib().objnerf_volume_project(nx, ny, nz, int(axis), _ptr(label), _ptr(out), _stream()), "objnerf_volume_project")
+    return out
+
+
+def volume_clearance(label: torch.Tensor, dims):
+    """-> (dist2 int32 [nz, ny, nx], site int32 [nz, ny, nx]): the exact squared distance to the nearest occupied voxel and
+    its linear index (the lowest among equals); INT32_MAX / -1 without an occupied voxel."""
+    nx, ny, nz = volume_check_dims(dims)
+    label = _volume(label, (nx, ny, nz), "label")
+    d, s, td, ts = (torch.empty_like(label) for _ in range(4))
+    check(lib().objnerf_volume_clearance(nx, ny, nz, _ptr(label), _ptr(d), _ptr(s), _ptr(td), _ptr(ts), _stream()),
+          "objnerf_volume_clearance")
+    return d, s
+
+
+def volume_round_cap(traversable: int) -> int:
+    """The hard cap of reach's round loop.  After round r every voxel whose shortest path crosses fewer than r tile borders
+    is final (DESIGN.md 4.29); a shortest path is simple, so it crosses fewer borders than there are traversable voxels;
+    one more round finds nothing to lower."""
+    return int(traversable) + 2
+
+
+def volume_reach(label: torch.Tensor, dist2: torch.Tensor, dims, r2: int, start_voxel: int, stats: Optional[dict] = None,
+                 batch: int = VOLUME_ROUND_BATCH) -> torch.Tensor:
+    """cost int32 storage [nz, ny, nx] of the unsigned path costs from start_voxel (a traversable voxel: the caller checks).
+    Rounds go out in batches; the changed words are read back once per batch.  stats receives rounds / batches."""
+    nx, ny, nz = volume_check_dims(dims)
+    label, dist2 = _volume(label, (nx, ny, nz), "label"), _volume(dist2, (nx, ny, nz), "dist2")
+    dev, n, r2 = label.device, nx * ny * nz, int(r2)
+    if not 0 <= int(start_voxel) < n or not 0 <= r2 <= 0x7fffffff or batch < 1:
+        raise ObjnerfError(f"volume_reach: start voxel {start_voxel} of {n}, r2 = {r2}, batch = {batch}")
+    trav = int(((label < 0) & (dist2 >= r2)).sum())
+    if 5 * trav >= 2 ** 32 - 6:
+        raise ObjnerfError(f"volume_reach: {trav} traversable voxels: a path cost may not fit 32 bits")
+    T = int(lib().objnerf_volume_reach_tiles(nx, ny, nz))
+    cost = torch.full((nz, ny, nx), -1, dtype=torch.int32, device=dev)
+    active = torch.zeros(2, T, dtype=torch.int32, device=dev)
+    sx, sy, sz = start_voxel % nx, (start_voxel // nx) % ny, start_voxel // (nx * ny)
+    ntx, nty = (nx + 7) // 8, (ny + 7) // 8
+    cost.view(-1)[start_voxel] = 0
+    active[0, ((sz // 8) * nty + sy // 8) * ntx + sx // 8] = 1
+    changed = torch.empty(batch, dtype=torch.int32, device=dev)
+    cap, rounds, batches = volume_round_cap(trav), 0, 0
+    while True:
+        changed.zero_()
+        check(lib().objnerf_volume_reach_rounds(nx, ny, nz, _ptr(label), _ptr(dist2), r2, _ptr(cost), _ptr(active), rounds,
+                                                batch, _ptr(changed), _stream()), "objnerf_volume_reach_rounds")
+        ch = changed.tolist()                   # the one read-back of the batch
+        batches += 1
+        if 0 in ch:                             # a round that lowered nothing: it and every later one were empty
+            rounds += ch.index(0) + 1
+            break
+        rounds += batch
+        if rounds > cap:
+            raise ObjnerfError(f"volume_reach: not settled after {rounds} rounds (the cap of this grid is {cap})")
+    if stats is not None:
+        stats["rounds"], stats["batches"], stats["round_cap"], stats["traversable"] = rounds, batches, cap, trav
+    return cost
+
+
+def volume_goals(label, dist2, site, cost, dims, r2: int, K: int) -> torch.Tensor:
+    """-> table int64 [K] (storage of the unsigned keys dist2 << 32 | voxel; -1 = all ones: no goal)."""
+    nx, ny, nz = volume_check_dims(dims)
+    label, dist2, site, cost = (_volume(t, (nx, ny, nz), nm) for t, nm in ((label, "label"), (dist2, "dist2"),
+                                                                          (site, "site"), (cost, "cost")))
+    if K < 1:
+        raise ObjnerfError(f"volume_goals: K = {K}")
+    table = torch.full((int(K),), -1, dtype=torch.int64, device=label.device)
+    check(lib().objnerf_volume_goals(nx, ny, nz, int(K), _ptr(label), _ptr(dist2), _ptr(site), _ptr(cost), int(r2),
+                                     _ptr(table), _stream()), "objnerf_volume_goals")
+    return table
+
+
+def volume_paths(label, dist2, cost, dims, r2: int, goals: torch.Tensor, cap: int, out: Optional[torch.Tensor] = None):
+    """goals int32 [G] -> (out int32 [G, cap] (or the caller's contiguous buffer of at least G * cap words), len int32 [G]:
+    negative where the path has more than cap voxels)."""
+    nx, ny, nz = volume_check_dims(dims)
+    label, dist2, cost = (_volume(t, (nx, ny, nz), nm) for t, nm in ((label, "label"), (dist2, "dist2"), (cost, "cost")))
+    goals = _req(goals, torch.int32, "goals").reshape(-1)
+    G, cap = int(goals.shape[0]), int(cap)
+    if cap < 0 or G * max(cap, 1) > 0x7fffffff:
+        raise ObjnerfError(f"volume_paths: cap = {cap}, G = {G}")
+    if out is None:
+        out = torch.full((G, cap), -1, dtype=torch.int32, device=label.device)
+    elif not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= G * cap):
+        raise ObjnerfError(f"volume_paths: out: a contiguous int32 buffer of at least {G * cap} words")
+    ln = torch.zeros(G, dtype=torch.int32, device=label.device)
+    check(lib().objnerf_volume_paths(nx, ny, nz, _ptr(label), _ptr(dist2), int(r2), _ptr(cost), G, _ptr(goals) if G else None,
+                                     cap, _ptr(out) if cap and G else None, _ptr(ln) if G else None, _stream()),
+          "objnerf_volume_paths")
+    return out, ln
