@@ -1249,6 +1249,66 @@ int objnerf_volume_paths(int32_t nx, int32_t ny, int32_t nz, const int32_t* labe
                          const uint32_t* cost, int32_t G, const int32_t* goals, int32_t cap, int32_t* out, int32_t* len,
                          void* stream);
 
+/* Part regions: the connected surface patches of a part query on the map's meshes, with pose (objnerf_mapregions.hip;
+ * openobj_amd/map_regions.py).  Added under ABI 14: the entries below are purely additive, so
+ * OBJNERF_ABI_VERSION stays 14.  The whole map in one call: S objects, verts fp64 [V][3] in packed map order with
+ * vert_off [S + 1] int64, faces int32 [F][3] of PACKED vertex ids with face_off [S + 1] int64 (face f belongs to the
+ * object whose range holds f), sims fp32 [V][Q] and a column q, thr fp32 [S].  1 <= V <= 2^31 - 1, 0 <= F <= 2^31 - 1,
+ * 1 <= S <= 65535, 1 <= Q <= 16, 0 <= q < Q; EINVAL otherwise, for a null pointer and for a short workspace, before any
+ * launch.  Nothing is allocated.  status: one int32 the caller zeroes; bits are OR-ed in.
+ *
+ * SELECTION: vertex v of object s is selected iff sims[v][q] >= thr[s], one fp32 compare: a NaN on either side selects
+ * nothing.  CONNECTION: two selected vertices are connected iff some face names both.  A face that names a vertex
+ * outside [0, V) raises status bit 0, one that names a vertex outside its own object's range raises bit 1; either joins
+ * nothing, contributes nothing, and nothing is read through its ids.  A face with a repeated vertex or zero area is
+ * legal: it joins its vertices and adds zero area.
+ *
+ * objnerf_regions_label: root [V] int32 = the smallest packed index of the vertex's region, -1 for a vertex that is not
+ * selected (union-find whose parent is always a smaller index, one thread per face, then a flatten: the result does not
+ * depend on the order of the unions).  The roots are compacted per object in ascending vertex order by count / scan /
+ * emit without atomics: reg_off [S + 1] int64 (device; R = reg_off [S] is the number of regions) and label [V] int32 =
+ * the row of the vertex's region, -1 where not selected.  vmax: the largest vertex count of an object (1 <= vmax <= V),
+ * the extent of the compaction's grid: a vertex past vmax inside its object is never found as a root.
+ * ws: objnerf_regions_workspace_bytes(V, F, S) (0: sizes out of range).
+ *
+ * objnerf_regions_table: table int64 [R][OBJNERF_REGION_ROW], every entry the result of integer atomics (or a function of
+ * such entries), so any schedule gives the same bytes.  Columns:
+ *    0 root   1 object   2 vertices   3 faces   4 area_q   5..7 first moments   8..10 normal   11..13 box minimum
+ *   14..16 box maximum   17 peak   18..20 centroid   21..26 second moments xx, xy, xz, yy, yz, zz
+ *   27..29 residual first moments   30..31 zero
+ * box: per axis the minimum / maximum of key(fp32(coordinate)), key(x) = bits ^ 0xFFFFFFFF for a set sign bit, else
+ * bits | 0x80000000 (unsigned order = float order).  peak: the maximum of key(sim) << 32 | (~v & 0xFFFFFFFF) as an
+ * unsigned 64-bit number: the selected vertex of the highest similarity, the smallest index among equals.
+ * A face contributes iff all three of its vertices are selected (they are then in one region).  With a = the first
+ * vertex of the face's object (the anchor), A, B, C its vertices, every fp64 operation rounded on its own:
+ *    dA = A - a, dB = B - a, dC = C - a
+ *    c = (dB - dA) x (dC - dA)              each component u_j w_k - u_k w_j: two products, one difference
+ *    area = 0.5 sqrt((cx cx + cy cy) + cz cz)
+ *    s = (dA + dB) + dC
+ *    area_q           += q44(area)
+ *    first moment j   += q44((area s_j) / 3)
+ *    normal j         += q44(0.5 c_j)
+ * q44(x) = llrint(x 2^44) (nearest, ties to even); a NaN, an infinity or |x 2^44| >= 2^62 counts as 0 and raises status
+ * bit 2.  centroid j (the bits of an fp64, relative to the anchor) = double(first moment j) / double(area_q), 0.0 when
+ * area_q <= 0.  Then, with e_i = d_i - centroid (i = A, B, C) and t = (e_A + e_B) + e_C,
+ *    second moment jk += q44((area (((e_Aj e_Ak + e_Bj e_Bk) + e_Cj e_Ck) + t_j t_k)) / 12)
+ *    residual j       += q44((area t_j) / 3)
+ * The second moment is the exact integral of (x - centroid)_j (x - centroid)_k over the triangle before rounding.  The
+ * residual is the first moment about the centroid column: what the roundings of pass A and of the division left over.
+ * A reader refines the centroid to anchor + centroid + residual / area_q; its error is then one rounding of 2^-45 per
+ * face divided by the area, however far the region lies from the anchor.
+ * Inside a wave, runs of neighbouring lanes with the same row are folded by a segmented scan and the last lane of a run
+ * issues the atomics. */
+#define OBJNERF_REGION_ROW 32
+size_t objnerf_regions_workspace_bytes(int64_t V, int64_t F, int32_t S);
+int objnerf_regions_label(int64_t V, int64_t F, int32_t S, int64_t vmax, int32_t Q, int32_t q, const int64_t* vert_off,
+                          const int64_t* face_off, const int32_t* faces, const float* sims, const float* thr, void* ws,
+                          size_t ws_bytes, int32_t* root, int32_t* label, int64_t* reg_off, int32_t* status, void* stream);
+int objnerf_regions_table(int64_t V, int64_t F, int32_t S, int32_t Q, int32_t q, const int64_t* vert_off,
+                          const int64_t* face_off, const double* verts, const int32_t* faces, const float* sims,
+                          const int32_t* root, const int32_t* label, int64_t R, int64_t* table, int32_t* status,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,25 +28,7 @@ constexpr int CC_RUN = 8;                  // consecutive pixels of a row per th
 constexpr int CC_MAX_SIDE = 32767;
 constexpr int CC_FINAL_IDS = 256;
 
-// ------------------------------------------------------------------------------------------------------ union-find
-// L[a] <= a always, and only ever decreases: every loop below ends, and a stale read is still an ancestor.
-__device__ __forceinline__ int uf_find(const volatile int* L, int a) {
-  int p;
-  while ((p = L[a]) != a) a = p;
-  return a;
-}
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-  for (;;) {
-    a = uf_find(L, a);
-    b = uf_find(L, b);
-    if (a == b) return;
-    if (a > b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(&L[b], a);           // b was a root: hang it under a, unless somebody got there first
-    if (old == b) return;
-    b = old;
-  }
-}
-
+// (uf_find / uf_union, the union-find whose parent is always a smaller index: objnerf_wg.h)
 // grid (tiles in x, tiles in y, F)
 __global__ __launch_bounds__(CC_WG) void cc_local_kernel(const int H, const int W, const int32_t* __restrict__ ids,
                                                          int32_t* __restrict__ label) {

@@ -101,6 +101,25 @@ __device__ __forceinline__ int wg_sum(int v, int* lds) {
   return total;
 }
 
+// ------------------------------------------------------------------------------------------------------ union-find
+// L[a] <= a always, and only ever decreases: every loop below ends, and a stale read is still an ancestor.
+__device__ __forceinline__ int uf_find(const volatile int* L, int a) {
+  int p;
+  while ((p = L[a]) != a) a = p;
+  return a;
+}
+__device__ __forceinline__ void uf_union(int* L, int a, int b) {
+  for (;;) {
+    a = uf_find(L, a);
+    b = uf_find(L, b);
+    if (a == b) return;
+    if (a > b) { const int t = a; a = b; b = t; }
+    const int old = atomicMin(&L[b], a);           // b was a root: hang it under a, unless somebody got there first
+    if (old == b) return;
+    b = old;
+  }
+}
+
 // ------------------------------------------------------------------- over an array in global memory, by one workgroup
 // out[i][c] = in[0][c] + .. + in[i - 1][c] for i < n, total[c] = the sum of all n (in every thread), over NCH
 // interleaved channels.  Tiles of WG x WG_SCAN_ITEMS elements; a wave owns 64 x WG_SCAN_ITEMS neighbours and takes

@@ -2,7 +2,8 @@
 
     python -m openobj_amd.map_query --logdir DIR --mode {rgb,class,instance,partpca,object,part}
         [--clip-query F.npy --sbert-query F.npy --part-query F.npy --top N --color-yaml PATH
-         --dataset Replica|Scannet --scene NAME --compact] --out DIR
+         --dataset Replica|Scannet --scene NAME --compact
+         --regions [--region-frac F | --region-min-cos C] [--region-min-area A]] --out DIR
 
 --compact reads map_vis_compact.pkl.gz (python -m openobj_amd.map_vis --compact); without the flag the dense
 map_vis.pkl.gz is read if it is there, else the compact file.
@@ -10,6 +11,11 @@ map_vis.pkl.gz is read if it is there, else the compact file.
 Writes one coloured obj_<id>.ply per visible object (uint8 colours round(c * 255)) and query.json (mode, the visible
 ids, the ranked object ids with their similarities, the top-k ids).  --dataset Replica hides the "ceiling" objects as
 the reference's viewer does by default (vis_interaction.py:181-184); without --dataset every object is written.
+--mode part --regions also writes regions.json (one record per connected patch of the part query on the top objects:
+vertices, faces, area, centroid, normal, axes, extent, box, peak; MapQuery.part_regions) and
+obj_<id>_regions.ply per top object (a palette colour per region, darkened RGB elsewhere).  --region-frac F (default
+0.75, an assumed value) keeps the vertices at or above F of the object's own similarity range, --region-min-cos C
+those with a cosine >= C; --region-min-area A [m^2] drops smaller regions.  Without --regions every file is as before.
 Every argument, query file and query width is checked before the device is touched."""
 from __future__ import annotations
 
@@ -53,7 +59,24 @@ def _parse(argv):
     ap.add_argument("--out", required=True)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--compact", action="store_true", help="read map_vis_compact.pkl.gz")
+    ap.add_argument("--regions", action="store_true", help="--mode part: also write regions.json and obj_<id>_regions.ply")
+    ap.add_argument("--region-frac", type=float, default=None)
+    ap.add_argument("--region-min-cos", type=float, default=None)
+    ap.add_argument("--region-min-area", type=float, default=None)
     a = ap.parse_args(argv)
+    given = [n for n in ("region_frac", "region_min_cos", "region_min_area") if getattr(a, n) is not None]
+    if a.regions and a.mode != "part":
+        ap.error("--regions needs --mode part")
+    if given and not a.regions:
+        ap.error(f"--{given[0].replace('_', '-')} needs --regions")
+    if a.region_frac is not None and a.region_min_cos is not None:
+        ap.error("--region-frac and --region-min-cos exclude each other")
+    if a.region_frac is not None and not 0.0 <= a.region_frac <= 1.0:
+        ap.error(f"--region-frac {a.region_frac} outside [0, 1]")
+    if a.region_min_cos is not None and not -1.0 <= a.region_min_cos <= 1.0:
+        ap.error(f"--region-min-cos {a.region_min_cos} outside [-1, 1]")
+    if a.region_min_area is not None and not a.region_min_area >= 0.0:
+        ap.error(f"--region-min-area {a.region_min_area} is negative")
     for k in NEEDS.get(a.mode, ()):
         v = getattr(a, k)
         if v is None:
@@ -115,6 +138,13 @@ def main(argv=None):
            "ranking": [{"id": int(k), "similarity": s} for k, s in rank], "top": [int(k) for k in top]}
     with open(os.path.join(a.out, "query.json"), "w") as fh:
         json.dump(doc, fh, indent=1)
+    if a.regions:
+        from . import map_regions
+        pos = [mq.keys.index(k) for k in top]
+        reg = mq.part_regions(q["part_query"], objects=pos, frac=0.75 if a.region_frac is None else a.region_frac,
+                              min_cos=a.region_min_cos, min_area=a.region_min_area or 0.0)
+        map_regions.write_regions(a.out, mq, reg, pos)
+        print(f"{len(reg)} regions on {len(pos)} objects -> {os.path.join(a.out, 'regions.json')}")
     print(f"{len(visible)} objects -> {a.out}")
     return doc
 

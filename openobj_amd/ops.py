@@ -2613,3 +2613,79 @@ def volume_paths(label, dist2, cost, dims, r2: int, goals: torch.Tensor, cap: in
                                      cap, _ptr(out) if cap and G else None, _ptr(ln) if G else None, _stream()),
           "objnerf_volume_paths")
     return out, ln
+
+
+# ---------------------------------------------------------------------------------------------------
+# part regions: connected patches of a part query on the map's meshes (objnerf_mapregions.hip; query.MapQuery.part_regions
+# and map_regions.py drive these).  The rules stand in include/objnerf_hip.h.
+REGION_ROW = 32                         # OBJNERF_REGION_ROW
+REGION_MAX_Q = 16
+REGION_STATUS_BAD_ID, REGION_STATUS_CROSS, REGION_STATUS_NONFINITE = 1, 2, 4
+
+
+def regions_workspace_bytes(V: int, F: int, S: int) -> int:
+    """0 for sizes out of range (V in [1, 2^31), F in [0, 2^31), S in [1, 65535])."""
+    if not (-2 ** 63 <= V < 2 ** 63 and -2 ** 63 <= F < 2 ** 63 and -2 ** 31 <= S < 2 ** 31):
+        return 0
+    return int(lib().objnerf_regions_workspace_bytes(int(V), int(F), int(S)))
+
+
+def _regions_mesh(vert_off, face_off, faces, sims):
+    vert_off, face_off = _req(vert_off, torch.int64, "vert_off"), _req(face_off, torch.int64, "face_off")
+    faces, sims = _req(faces, torch.int32, "faces"), _req(sims, torch.float32, "sims")
+    S = int(vert_off.shape[0]) - 1
+    if vert_off.dim() != 1 or S < 1 or tuple(face_off.shape) != (S + 1,):
+        raise ObjnerfError("part regions: vert_off, face_off int64 [S + 1], S >= 1")
+    if sims.dim() != 2 or faces.dim() != 2 or int(faces.shape[1]) != 3:
+        raise ObjnerfError("part regions: sims [V, Q], faces [F, 3]")
+    if any(t.device != sims.device for t in (vert_off, face_off, faces)):
+        raise ObjnerfError(f"part regions: every tensor on {sims.device}")
+    return vert_off, face_off, faces, sims, S
+
+
+def regions_label(vert_off: torch.Tensor, face_off: torch.Tensor, faces: torch.Tensor, sims: torch.Tensor, q: int,
+                  thr: torch.Tensor, vmax: Optional[int] = None, status: Optional[torch.Tensor] = None,
+                  ws: Optional[torch.Tensor] = None):
+    """-> (root int32 [V], label int32 [V], reg_off int64 [S + 1], status int32 [1]), all on the device: nothing is read
+    back.  vmax: the largest vertex count of an object (None: read from vert_off, which synchronises).  ws: a uint8 buffer
+    of regions_workspace_bytes(V, F, S), else one is made."""
+    vert_off, face_off, faces, sims, S = _regions_mesh(vert_off, face_off, faces, sims)
+    thr = _req(thr, torch.float32, "thr")
+    V, Q, F, dev = int(sims.shape[0]), int(sims.shape[1]), int(faces.shape[0]), sims.device
+    if tuple(thr.shape) != (S,) or thr.device != dev:
+        raise ObjnerfError(f"regions_label: thr fp32 [{S}] on {dev}")
+    if vmax is None:
+        vmax = int((vert_off[1:] - vert_off[:-1]).max())
+    if ws is None:
+        ws = torch.empty(max(regions_workspace_bytes(V, F, S), 1), dtype=torch.uint8, device=dev)
+    ws = _req(ws, torch.uint8, "ws")
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = _req(status, torch.int32, "status")
+    root = torch.empty(max(V, 1), dtype=torch.int32, device=dev)[:V]
+    label = torch.empty(max(V, 1), dtype=torch.int32, device=dev)[:V]
+    reg_off = torch.empty(S + 1, dtype=torch.int64, device=dev)
+    check(lib().objnerf_regions_label(V, F, S, int(vmax), Q, int(q), _ptr(vert_off), _ptr(face_off),
+                                      _ptr(faces) if F else None, _ptr(sims), _ptr(thr), _ptr(ws), int(ws.numel()),
+                                      _ptr(root), _ptr(label), _ptr(reg_off), _ptr(status), _stream()),
+          "objnerf_regions_label")
+    return root, label, reg_off, status
+
+
+def regions_table(vert_off: torch.Tensor, face_off: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
+                  sims: torch.Tensor, q: int, root: torch.Tensor, label: torch.Tensor, R: int,
+                  status: torch.Tensor) -> torch.Tensor:
+    """-> table int64 [R, REGION_ROW] on the device (the columns: include/objnerf_hip.h); status is OR-ed into."""
+    vert_off, face_off, faces, sims, S = _regions_mesh(vert_off, face_off, faces, sims)
+    verts = _req(verts, torch.float64, "verts")
+    root, label, status = _req(root, torch.int32, "root"), _req(label, torch.int32, "label"), _req(status, torch.int32, "status")
+    V, Q, F, dev, R = int(sims.shape[0]), int(sims.shape[1]), int(faces.shape[0]), sims.device, int(R)
+    if tuple(verts.shape) != (V, 3) or tuple(root.shape) != (V,) or tuple(label.shape) != (V,) or status.numel() < 1:
+        raise ObjnerfError(f"regions_table: verts fp64 [{V}, 3], root, label int32 [{V}], status int32 [1]")
+    if any(t.device != dev for t in (verts, root, label, status)):
+        raise ObjnerfError(f"regions_table: every tensor on {dev}")
+    table = torch.empty(max(R, 0), REGION_ROW, dtype=torch.int64, device=dev)
+    check(lib().objnerf_regions_table(V, F, S, Q, int(q), _ptr(vert_off), _ptr(face_off), _ptr(verts),
+                                      _ptr(faces) if F else None, _ptr(sims), _ptr(root), _ptr(label), R,
+                                      _ptr(table) if R > 0 else None, _ptr(status), _stream()), "objnerf_regions_table")
+    return table

@@ -16,6 +16,8 @@ Every colouring returns device colours [V_total, 3] fp32 in that packed order; M
                          and the colours on the GPU
   color_by_rgb / color_by_class / color_by_instance (:263-306)
   hidden_sets            the ceiling / "most" index lists and the axis-aligned boxes (:146-190)
+  part_regions           beyond the viewer: the connected surface patches a part query selects, with area, centroid,
+                         normal, axes and peak (objnerf_mapregions.hip, map_regions.py)
 
 A compact map (map_vis.export(compact=True): part_rows [V, H + 1] and part_head [C, H + 1] per object instead of
 part_feat, the unit feature being part_head . part_rows[v]) is taken the same way and answers
@@ -385,6 +387,74 @@ class MapQuery:
         modes[top] = _lib.COLOR_RAINBOW
         return self._colors(modes, factor=np.full(self.S, DARK), column=np.zeros(self.S, np.int32), proj=proj,
                             minmax=mm)
+
+    # -------------------------------------------------------------------------------------------- part regions
+    _mesh_dev = None                # the packed meshes on the device, built by the first part_regions call
+
+    def mesh_buffers(self):
+        """-> (verts fp64 [V, 3] in packed map order, faces int32 [F, 3] of packed vertex ids, face_off int64 [S + 1],
+        anchors fp64 numpy [S, 3]: the first vertex of every object), on the device, from all_obj[k]["mesh"].  Built on
+        first use and kept: constructing a MapQuery uploads none of it."""
+        if self._mesh_dev is not None:
+            return self._mesh_dev
+        vs, fs, foff, anchors = [], [], [0], np.zeros((self.S, 3))
+        for s, k in enumerate(self.keys):
+            m = self.all_obj[k]["mesh"]
+            v = np.asarray(m.vertices, np.float64).reshape(-1, 3)
+            f = np.asarray(m.faces, np.int64).reshape(-1, 3)
+            n = int(self.seg_host[s + 1] - self.seg_host[s])
+            if len(v) != n:
+                raise ValueError(f"MapQuery: object {k}: the mesh has {len(v)} vertices, the part features {n}")
+            if len(f) and (f.min() < 0 or f.max() >= n):
+                raise ValueError(f"MapQuery: object {k}: a face names a vertex outside the mesh")
+            if n:
+                anchors[s] = v[0]
+            vs.append(v)
+            fs.append(f + int(self.seg_host[s]))
+            foff.append(foff[-1] + len(f))
+        if self.V > 0x7fffffff or foff[-1] > 0x7fffffff:
+            raise ValueError("MapQuery: more than 2^31 - 1 vertices or faces")
+        verts = torch.from_numpy(np.ascontiguousarray(np.concatenate(vs) if vs else np.zeros((0, 3)))).to(self.dev)
+        faces = torch.from_numpy(np.ascontiguousarray((np.concatenate(fs) if fs else np.zeros((0, 3))).astype(np.int32)))
+        self._mesh_dev = (verts, faces.to(self.dev), torch.tensor(foff, dtype=torch.int64, device=self.dev), anchors)
+        return self._mesh_dev
+
+    def part_regions(self, part_q, objects: Optional[Sequence[int]] = None, frac: float = 0.75,
+                     min_cos: Optional[float] = None, min_area: float = 0.0, min_vertices: int = 1):
+        """The connected surface patches of a part query -> map_regions.PartRegions.  A vertex of object s is selected
+        iff its cosine with part_q is >= thr[s]; two selected vertices are connected iff a face of the mesh names both.
+        thr[s] = fp32(mn + fp32(frac * fp32(mx - mn))) over the object's own minimum and maximum, i.e. the vertices the
+        rainbow colouring shows at or above frac; with min_cos given, thr[s] = min_cos.  frac = 0.75 is an ASSUMED
+        default, not a measured one.  objects: positions in the map's order (None: all); the others select nothing.
+        min_area [m^2] / min_vertices drop small regions on the host; label is remapped to the rows that stay.
+        Labelling, the compaction of the roots and the integer table run on the device (ops.regions_label /
+        regions_table); R is read back once, then the table."""
+        from . import map_regions as mr
+        if min_cos is None and not 0.0 <= float(frac) <= 1.0:
+            raise ValueError(f"part_regions: frac {frac} outside [0, 1]")
+        if objects is not None:
+            objects = [int(p) for p in objects]
+            if any(not 0 <= p < self.S for p in objects):
+                raise ValueError(f"part_regions: objects {objects}: positions in [0, {self.S})")
+        pq = self._query(part_q, self.D, "part query")
+        empty = mr.regions_from_table(np.zeros((0, mr.ROW), np.int64), np.zeros((max(self.S, 1), 3)), self.keys)
+        if self.V == 0 or self.S == 0:
+            return mr.PartRegions(torch.full((self.V,), -1, dtype=torch.int32, device=self.dev), empty,
+                                  np.full(self.S, np.nan, np.float32))
+        sims, mm = self.part_similarity(pq[None], objects=objects)
+        thr = mr.thresholds(mm[:, 0].cpu().numpy(), frac, min_cos, objects)
+        verts, faces, face_off, anchors = self.mesh_buffers()
+        root, label, reg_off, status = ops.regions_label(self.seg_off, face_off, faces, sims, 0,
+                                                         torch.from_numpy(thr).to(self.dev),
+                                                         vmax=max(int(np.diff(self.seg_host).max()), 1))
+        R = int(reg_off[-1])                                               # the one read-back before the table
+        table = ops.regions_table(self.seg_off, face_off, verts, faces, sims, 0, root, label, R, status)
+        fields = mr.regions_from_table(table.cpu().numpy(), anchors, self.keys)
+        keep, remap = mr.filter_rows(fields["area"], fields["n_vertices"], min_area, min_vertices)
+        if len(keep) != R:
+            fields = {f: v[keep] for f, v in fields.items()}
+            label = torch.from_numpy(remap).to(self.dev)[label.long()]     # (-1 indexes remap's last entry, -1)
+        return mr.PartRegions(label, fields, thr, int(status.item()))
 
     # -------------------------------------------------------------------------------------------- the compact map
     def _columns(self, run, cols) -> torch.Tensor:
