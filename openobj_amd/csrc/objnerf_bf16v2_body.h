@@ -45,6 +45,7 @@
 #define OBJ_HW_SINCOS 1      // embedding sin / cos on the transcendental unit (see objnerf_device.h)
 #include <utility>
 #include "objnerf_bf16_common.h"
+#include "objnerf_ray_loss.h"
 #include "../../include/objnerf_hip.h"
 
 namespace objtrain {
@@ -423,8 +424,8 @@ __global__ __launch_bounds__(NTHR) void V2_KERNEL(const TrainDev a) {
   const float n1 = (float)a.counts[2 * k], n2 = (float)a.counts[2 * k + 1];
   int bflag0, bflag1;
   batch_flags(a, bflag0, bflag1);
-  const float inv1 = bflag0 ? 0.0f : 1.0f / (n1 + 1e-10f);
-  const float inv2 = bflag1 ? 0.0f : 1.0f / (n2 + 1e-10f);
+  const float inv1 = bflag0 ? 0.0f : rayloss::mean_norm(n1);
+  const float inv2 = bflag1 ? 0.0f : rayloss::mean_norm(n2);
 
   WAcc acc;
 #pragma unroll
@@ -689,31 +690,22 @@ __global__ __launch_bounds__(NTHR) void V2_KERNEL(const TrainDev a) {
       const float C2 = sg.total_add(wgt * c2, pos);
       const float dz = zz - D;
       const float V = sg.total_add(wgt * (dz * dz), pos);
-      const float m1 = (pf_lab == 1) ? 1.0f : 0.0f;
-      const float m2 = (pf_lab != 2) ? 1.0f : 0.0f;
-      const float tgt = (pf_lab != 0) ? 1.0f : 0.0f;
-      const float info = 1.0f / (sqrtf(V) + 1e-4f);
-      const float rd = D - pf_gtd, r0 = C0 - pf_gr, r1 = C1 - pf_gg, r2 = C2 - pf_gb, ro = O - tgt;
-      auto sgn = [](float x) { return x > 0.f ? 1.0f : (x < 0.f ? -1.0f : 0.0f); };
-      const float gD = m1 * sgn(rd) * info * inv1;
-      const float gC0 = a.color_scaling * m1 * sgn(r0) * inv1;
-      const float gC1 = a.color_scaling * m1 * sgn(r1) * inv1;
-      const float gC2 = a.color_scaling * m1 * sgn(r2) * inv1;
-      const float gO = a.opacity_scaling * m2 * sgn(ro) * inv2;
+      const rayloss::Resid res = rayloss::residuals(D, O, C0, C1, C2, V, pf_gtd, pf_gr, pf_gg, pf_gb, pf_lab);
+      const rayloss::Seeds sd = rayloss::seeds(res, a.color_scaling, a.opacity_scaling, inv1, inv2);
       if (on && pos == 0) {
-        l_d += m1 * fabsf(rd) * info * inv1;
-        l_c += m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-        l_o += m2 * fabsf(ro) * inv2;
+        l_d += rayloss::term_depth(res, inv1);
+        l_c += rayloss::term_colour(res, inv1);
+        l_o += rayloss::term_opacity(res, inv2);
       }
-      const float dw = gD * zz + gO + gC0 * c0 + gC1 * c1 + gC2 * c2;
+      const float dw = rayloss::sample_dw(sd, zz, c0, c1, c2);
       const float qv = dw * wgt;
       const float suf = sg.rscan_add(qv, pos) - qv;
-      const float docc = dw * T - suf / fr;
+      const float docc = rayloss::d_occ(dw, T, suf, fr);
       if (on) {
-        s_alpha[sl] = 10.0f * (docc * occ * (1.0f - occ));
-        s_col[sl] = gC0 * wgt * c0 * (1.0f - c0);
-        s_col[TS + sl] = gC1 * wgt * c1 * (1.0f - c1);
-        s_col[2 * TS + sl] = gC2 * wgt * c2 * (1.0f - c2);
+        s_alpha[sl] = 10.0f * rayloss::d_alpha(docc, occ);
+        s_col[sl] = rayloss::d_raw_colour(sd.gC0, wgt, c0);
+        s_col[TS + sl] = rayloss::d_raw_colour(sd.gC1, wgt, c1);
+        s_col[2 * TS + sl] = rayloss::d_raw_colour(sd.gC2, wgt, c2);
       }
     }
 #if defined(V2_NO_WGRAD) || ((V2_ABL) & 8)
@@ -760,24 +752,16 @@ __global__ __launch_bounds__(NTHR) void V2_KERNEL(const TrainDev a) {
       const float C2 = sg.total_add(cw_wgt * cw_c2, pos);
       const float dz = zz - D;
       const float V = sg.total_add(cw_wgt * (dz * dz), pos);
-      const float m1 = (pf_lab == 1) ? 1.0f : 0.0f;
-      const float m2 = (pf_lab != 2) ? 1.0f : 0.0f;
-      const float tgt = (pf_lab != 0) ? 1.0f : 0.0f;
-      const float info = 1.0f / (sqrtf(V) + 1e-4f);
-      const float rd = D - pf_gtd, r0 = C0 - pf_gr, r1 = C1 - pf_gg, r2 = C2 - pf_gb, ro = O - tgt;
-      auto sgn = [](float x) { return x > 0.f ? 1.0f : (x < 0.f ? -1.0f : 0.0f); };
-      const float gD = m1 * sgn(rd) * info * inv1;
-      cw_g0 = a.color_scaling * m1 * sgn(r0) * inv1;
-      cw_g1 = a.color_scaling * m1 * sgn(r1) * inv1;
-      cw_g2 = a.color_scaling * m1 * sgn(r2) * inv1;
-      const float gO = a.opacity_scaling * m2 * sgn(ro) * inv2;
+      const rayloss::Resid res = rayloss::residuals(D, O, C0, C1, C2, V, pf_gtd, pf_gr, pf_gg, pf_gb, pf_lab);
+      const rayloss::Seeds sd = rayloss::seeds(res, a.color_scaling, a.opacity_scaling, inv1, inv2);
+      cw_g0 = sd.gC0; cw_g1 = sd.gC1; cw_g2 = sd.gC2;
       if (on && pos == 0) {
-        l_d += m1 * fabsf(rd) * info * inv1;
-        l_c += m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-        l_o += m2 * fabsf(ro) * inv2;
+        l_d += rayloss::term_depth(res, inv1);
+        l_c += rayloss::term_colour(res, inv1);
+        l_o += rayloss::term_opacity(res, inv2);
         s_gof[2 + w] = O;
       }
-      cw_dw = gD * zz + gO + cw_g0 * cw_c0 + cw_g1 * cw_c1 + cw_g2 * cw_c2;
+      cw_dw = rayloss::sample_dw(sd, zz, cw_c0, cw_c1, cw_c2);
       if (on) s_w[sl] = cw_wgt;
     } else if (have_prev) {
       switch (w) {
@@ -832,20 +816,17 @@ __global__ __launch_bounds__(NTHR) void V2_KERNEL(const TrainDev a) {
       const float uh = pf_uh, beta = pf_beta, ngv = pf_ngv;
       const float O2 = valid ? s_gof[2 + q] : 0.f;
       const float fu = wave_sum32(fh * uh), fGf = wave_sum32(fh * Gfh), fwb = wave_sum32(fh * wbh);
-      const float dotFg = fu + O2 * beta;
-      const float nF2 = fmaxf(fGf + 2.0f * O2 * fwb + O2 * O2 * bbv, 0.0f);
-      const float nF = fmaxf(__builtin_amdgcn_sqrtf(nF2), 1e-8f), ngc = fmaxf(ngv, 1e-8f);
-      const float rnn = __builtin_amdgcn_rcpf(nF * ngc);       // (bf16 mode: 1-ulp hardware reciprocals)
-      const float cosv = dotFg * rnn;
       const float mm1 = (pf_lab2 == 1) ? 1.0f : 0.0f;
-      const float gam = -a.feat_scaling * mm1 * inv1;
-      const float ar = gam * rnn, cr = -gam * cosv * __builtin_amdgcn_rcpf(nF * nF);
-      const float gfh = ar * uh + cr * (Gfh + O2 * wbh);
-      const float gof = ar * beta + cr * (fwb + O2 * bbv);
+      // (bf16 mode: 1-ulp hardware reciprocals)
+      const rayloss::FeatCos fc = rayloss::feat_cos<rayloss::Rcp::hardware>(fu, fGf, fwb, O2, beta, ngv, bbv, mm1,
+                                                                           a.feat_scaling, inv1);
+      const float ar = fc.ar, cr = fc.cr;
+      const float gfh = rayloss::gfh(ar, cr, uh, Gfh, O2, wbh);
+      const float gof = rayloss::gof(ar, cr, beta, fwb, O2, bbv);
       if (valid && (w & 3) == 0 && half == 0) {
         const long rr2 = (long)k * R + ray0 + q;
         if (hh == 0) {
-          l_f += mm1 * (1.0f - cosv) * inv1;
+          l_f += rayloss::term_feature(fc.cosv, mm1, inv1);
           a.rayfeat[rr2 * RAYFEAT + 32] = O2;
           a.rayfeat[rr2 * RAYFEAT + 33] = ar;
           a.rayfeat[rr2 * RAYFEAT + 34] = cr;
@@ -874,12 +855,12 @@ __global__ __launch_bounds__(NTHR) void V2_KERNEL(const TrainDev a) {
       if (on) cw_dw += s_dwf[sl];
       const float qv = cw_dw * cw_wgt;
       const float suf = sg.rscan_add(qv, pos) - qv;
-      const float docc = cw_dw * cw_T - suf / cw_fr;
+      const float docc = rayloss::d_occ(cw_dw, cw_T, suf, cw_fr);
       if (on) {
-        s_alpha[sl] = 10.0f * (docc * cw_occ * (1.0f - cw_occ));
-        s_col[sl] = cw_g0 * cw_wgt * cw_c0 * (1.0f - cw_c0);
-        s_col[TS + sl] = cw_g1 * cw_wgt * cw_c1 * (1.0f - cw_c1);
-        s_col[2 * TS + sl] = cw_g2 * cw_wgt * cw_c2 * (1.0f - cw_c2);
+        s_alpha[sl] = 10.0f * rayloss::d_alpha(docc, cw_occ);
+        s_col[sl] = rayloss::d_raw_colour(cw_g0, cw_wgt, cw_c0);
+        s_col[TS + sl] = rayloss::d_raw_colour(cw_g1, cw_wgt, cw_c1);
+        s_col[2 * TS + sl] = rayloss::d_raw_colour(cw_g2, cw_wgt, cw_c2);
       }
     } else if (have_prev) {
       switch (w) {

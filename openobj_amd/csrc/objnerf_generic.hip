@@ -10,6 +10,7 @@
 #include "objnerf_generic.h"
 #include "objnerf_gemm.h"
 #include "objnerf_step_tail.h"
+#include "objnerf_ray_loss.h"
 
 namespace objgen {
 

@@ -7,11 +7,10 @@
 #include "objnerf_wg.h"
 #include "objnerf_generic.h"
 #include "objnerf_step_tail.h"
+#include "objnerf_ray_loss.h"
 #include "objnerf_boxray.h"
 
 namespace {
-
-__device__ __forceinline__ float sgnf(float x) { return x > 0.f ? 1.0f : (x < 0.f ? -1.0f : 0.0f); }
 
 // ------------------------------------------------------------------------------------------------
 // composite: one wave per ray, samples on lanes in chunks of 64 with carries.
@@ -202,8 +201,8 @@ __global__ __launch_bounds__(1024) void loss_kernel(const LossDev a) {
   const long rr = (long)blockIdx.x * nw + w;
   const int k = (int)(rr / a.R);
   const float n1 = (float)a.counts[2 * k], n2 = (float)a.counts[2 * k + 1];
-  const float inv1 = a.flags[0] ? 0.0f : 1.0f / (n1 + 1e-10f);
-  const float inv2 = a.flags[1] ? 0.0f : 1.0f / (n2 + 1e-10f);
+  const float inv1 = a.flags[0] ? 0.0f : rayloss::mean_norm(n1);
+  const float inv2 = a.flags[1] ? 0.0f : rayloss::mean_norm(n2);
   const int lab = a.labels[rr];
   const float m1 = (lab == 1) ? 1.f : 0.f, m2 = (lab != 2) ? 1.f : 0.f, tgt = (lab != 0) ? 1.f : 0.f;
   float carry = 1.0f, D = 0.f, O = 0.f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
@@ -232,13 +231,12 @@ __global__ __launch_bounds__(1024) void loss_kernel(const LossDev a) {
     const float dz = on ? a.z[rr * S + s] - D : 0.f;
     Vv += wave_sum64(on ? wv[s] * (dz * dz) : 0.f);
   }
-  const float info = 1.0f / (sqrtf(Vv) + 1e-4f);
+  const float info = rayloss::depth_weight(Vv);
   const float rd = D - a.gt_depth[rr];
   const float r0 = C0 - a.gt_rgb[rr * 3], r1 = C1 - a.gt_rgb[rr * 3 + 1], r2 = C2 - a.gt_rgb[rr * 3 + 2];
   const float ro = O - tgt;
-  const float gD = m1 * sgnf(rd) * info * inv1;
-  const float gC0 = a.cs * m1 * sgnf(r0) * inv1, gC1 = a.cs * m1 * sgnf(r1) * inv1, gC2 = a.cs * m1 * sgnf(r2) * inv1;
-  const float gO = a.os * m2 * sgnf(ro) * inv2;
+  const rayloss::Resid res{m1, m2, info, rd, r0, r1, r2, ro};
+  const rayloss::Seeds sd = rayloss::seeds(res, a.cs, a.os, inv1, inv2);
   float lf = 0.f;
   // feature term (loss.py:82-99): F = sum_s w_s f_s ; 1 - cos(F, g)
   if (a.pred_feat && a.gt_feat) {
@@ -253,7 +251,7 @@ __global__ __launch_bounds__(1024) void loss_kernel(const LossDev a) {
     dotFg = wave_sum64(dotFg); nF2 = wave_sum64(nF2); ng2 = wave_sum64(ng2);
     const float nF = fmaxf(sqrtf(nF2), 1e-8f), ng = fmaxf(sqrtf(ng2), 1e-8f);
     const float cosv = dotFg / (nF * ng);
-    lf = m1 * (1.0f - cosv) * inv1;
+    lf = rayloss::term_feature(cosv, m1, inv1);
     const float gs = -a.fs * m1 * inv1;      // d total / d cos
     for (int cc = lane; cc < C; cc += 64) {
       float F = 0.f;
@@ -294,18 +292,14 @@ __global__ __launch_bounds__(1024) void loss_kernel(const LossDev a) {
     }
     fu = wave_sum64(fu); fGf = wave_sum64(fGf); fwb = wave_sum64(fwb);
     const float beta = rin[Hh], ngv = rin[Hh + 1];
-    const float dotFg = fu + O * beta;
-    const float nF2 = fmaxf(fGf + 2.0f * O * fwb + O * O * bb, 0.0f);
-    const float nF = fmaxf(sqrtf(nF2), 1e-8f), ngc = fmaxf(ngv, 1e-8f);
-    const float cosv = dotFg / (nF * ngc);
-    lf = m1 * (1.0f - cosv) * inv1;
-    const float gam = -a.fs * m1 * inv1;                 // d total / d cos
-    const float ar = gam / (nF * ngc), cr = -gam * cosv / (nF * nF);
-    const float gof = ar * beta + cr * (fwb + O * bb);   // d total / d opacity (feature part)
+    const rayloss::FeatCos fc = rayloss::feat_cos<rayloss::Rcp::exact>(fu, fGf, fwb, O, beta, ngv, bb, m1, a.fs, inv1);
+    lf = rayloss::term_feature(fc.cosv, m1, inv1);
+    const float ar = fc.ar, cr = fc.cr;
+    const float gof = rayloss::gof(ar, cr, beta, fwb, O, bb);
     float* rf = a.rayfeat + rr * (long)(Hh + 3);
     for (int h = lane; h < Hh; h += 64) {
       rf[h] = sfh[h];
-      sfh[h] = ar * rin[h] + cr * (sgf[h] + O * wb[h]);  // d total / d fh
+      sfh[h] = rayloss::gfh(ar, cr, rin[h], sgf[h], O, wb[h]);
     }
     if (lane == 0) { rf[Hh] = O; rf[Hh + 1] = ar; rf[Hh + 2] = cr; }
     __builtin_amdgcn_wave_barrier();
@@ -326,9 +320,9 @@ __global__ __launch_bounds__(1024) void loss_kernel(const LossDev a) {
   // per-object loss terms: the block's rays are combined in LDS first -- thousands of float atomics on ONE address
   // (a single object, e.g. the background network) serialise in L2 and were 65 us of a 600 us step
   if (lane == 0) {
-    s_red[w][0] = m1 * fabsf(rd) * info * inv1;
-    s_red[w][1] = m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-    s_red[w][2] = m2 * fabsf(ro) * inv2;
+    s_red[w][0] = rayloss::term_depth(res, inv1);
+    s_red[w][1] = rayloss::term_colour(res, inv1);
+    s_red[w][2] = rayloss::term_opacity(res, inv2);
     s_red[w][3] = lf;
   }
   __syncthreads();
@@ -348,7 +342,7 @@ __global__ __launch_bounds__(1024) void loss_kernel(const LossDev a) {
     const float c0 = cp[0], c1 = cp[1], c2 = cp[2];
     const float wt = on ? wv[s] : 0.f, T = on ? tv[s] : 0.f;
     const float zz = on ? a.z[rr * S + s] : 0.f;
-    const float dw = on ? gD * zz + gO + gC0 * c0 + gC1 * c1 + gC2 * c2 + dwv[s] : 0.f;
+    const float dw = on ? rayloss::sample_dw(sd, zz, c0, c1, c2) + dwv[s] : 0.f;
     const float qv = dw * wt;
     const float inc = SegRows::make(64, lane).rscan_add(qv, lane);
     const float suf = inc - qv + sufc;
@@ -356,12 +350,12 @@ __global__ __launch_bounds__(1024) void loss_kernel(const LossDev a) {
     if (on) {
       const float occ = sigmoid_acc(a.alpha[rr * S + s]);
       const float fr = (1.0f - occ) + 1e-10f;
-      const float docc = dw * T - suf / fr;
-      if (a.d_alpha) a.d_alpha[rr * S + s] = docc * occ * (1.0f - occ);
-      if (a.d_color) {
-        a.d_color[(rr * S + s) * 3] = gC0 * wt;
-        a.d_color[(rr * S + s) * 3 + 1] = gC1 * wt;
-        a.d_color[(rr * S + s) * 3 + 2] = gC2 * wt;
+      const float docc = rayloss::d_occ(dw, T, suf, fr);
+      if (a.d_alpha) a.d_alpha[rr * S + s] = rayloss::d_alpha(docc, occ);
+      if (a.d_color) {                  // (by the colour itself: this path's sigmoid is differentiated by its caller)
+        a.d_color[(rr * S + s) * 3] = sd.gC0 * wt;
+        a.d_color[(rr * S + s) * 3 + 1] = sd.gC1 * wt;
+        a.d_color[(rr * S + s) * 3 + 2] = sd.gC2 * wt;
       }
     }
   }

@@ -65,8 +65,6 @@ __host__ __device__ inline int sf_rays_per_wg(int S, bool feat) {
   return rpw;
 }
 
-__device__ __forceinline__ float sf_sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
-
 template <int RT, bool BF, bool FEAT>
 __global__ __launch_bounds__(512) void train_small_kernel(const SmallFused a) {
   constexpr int BM = 16 * RT, H = FS_H, PT = FS_P, PW = BS_PW;
@@ -417,8 +415,8 @@ __global__ __launch_bounds__(512) void train_small_kernel(const SmallFused a) {
   // With the feature branch the pass runs twice: FIRST without the feature term's d loss / d weight (it yields the ray
   // weights, the loss terms, the rays' opacity and the colour head's gradients, none of which depend on it), and again
   // once that term is known (s_wt then holds it), for d alpha alone.
-  const float inv1 = fl0 ? 0.0f : 1.0f / ((float)n1i + 1e-10f);
-  const float inv2 = fl1 ? 0.0f : 1.0f / ((float)n2i + 1e-10f);
+  const float inv1 = fl0 ? 0.0f : rayloss::mean_norm((float)n1i);
+  const float inv2 = fl1 ? 0.0f : rayloss::mean_norm((float)n2i);
   float lt0 = 0.f, lt1 = 0.f, lt2 = 0.f, lt3 = 0.f;
   auto composite = [&](const bool first, const bool with_dwv) {
     const bool on = lane < S;
@@ -442,37 +440,38 @@ __global__ __launch_bounds__(512) void train_small_kernel(const SmallFused a) {
       const float C2 = wave_sum64(on ? wt * c2 : 0.f);
       const float dz = on ? zz - D : 0.f;
       const float Vv = wave_sum64(on ? wt * (dz * dz) : 0.f);
-      const float info = 1.0f / (sqrtf(Vv) + 1e-4f);
+      // (the masks and the residuals are spelt out where they always stood: with the label's compares and the loads of
+      // gt_depth / gt_rgb inside rayloss::residuals the compiler moves them against the wave reductions)
+      const float info = rayloss::depth_weight(Vv);
       const float rd = D - a.gt_depth[rr];
       const float r0 = C0 - a.gt_rgb[rr * 3], r1 = C1 - a.gt_rgb[rr * 3 + 1], r2 = C2 - a.gt_rgb[rr * 3 + 2];
       const float ro = O - tgt;
-      const float gD = m1 * sf_sgn(rd) * info * inv1;
-      const float gC0 = a.cs * m1 * sf_sgn(r0) * inv1, gC1 = a.cs * m1 * sf_sgn(r1) * inv1, gC2 = a.cs * m1 * sf_sgn(r2) * inv1;
-      const float gO = a.os * m2 * sf_sgn(ro) * inv2;
+      const rayloss::Resid res{m1, m2, info, rd, r0, r1, r2, ro};
+      const rayloss::Seeds sd = rayloss::seeds(res, a.cs, a.os, inv1, inv2);
       if (first) {
-        lt0 += m1 * fabsf(rd) * info * inv1;
-        lt1 += m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-        lt2 += m2 * fabsf(ro) * inv2;
+        lt0 += rayloss::term_depth(res, inv1);
+        lt1 += rayloss::term_colour(res, inv1);
+        lt2 += rayloss::term_opacity(res, inv2);
       }
       const float dwf = (with_dwv && on) ? s_wt[m] : 0.0f;        // (second pass: the feature term's d loss / d weight)
-      const float dw = on ? gD * zz + gO + gC0 * c0 + gC1 * c1 + gC2 * c2 + dwf : 0.f;
+      const float dw = on ? rayloss::sample_dw(sd, zz, c0, c1, c2) + dwf : 0.f;
       const float qv = dw * wt;
       const float inc = SegRows::make(64, lane).rscan_add(qv, lane);
       const float suf = inc - qv;
       if (on) {
-        const float docc = dw * T - suf / fr;
-        const float da = docc * occ * (1.0f - occ);
+        const float docc = rayloss::d_occ(dw, T, suf, fr);
+        const float da = rayloss::d_alpha(docc, occ);
         float* dh = s_dh + 4 * m;                 // heads_bwd_kernel: dhead = (10 d_alpha, d_colour * c (1 - c))
         dh[0] = 10.0f * da;
         if (first) {
-          dh[1] = (gC0 * wt) * c0 * (1.0f - c0);
-          dh[2] = (gC1 * wt) * c1 * (1.0f - c1);
-          dh[3] = (gC2 * wt) * c2 * (1.0f - c2);
+          dh[1] = rayloss::d_raw_colour(sd.gC0, wt, c0);
+          dh[2] = rayloss::d_raw_colour(sd.gC1, wt, c1);
+          dh[3] = rayloss::d_raw_colour(sd.gC2, wt, c2);
         }
       }
       if (FEAT && first) {
         if (on) s_wt[m] = wt;
-        if (lane == 0) { s_rayf[4 * lr] = O; s_rayf[4 * lr + 1] = m1; }
+        if (lane == 0) { s_rayf[4 * lr] = O; s_rayf[4 * lr + 1] = res.m1; }
       }
     }
   };
@@ -559,14 +558,10 @@ __global__ __launch_bounds__(512) void train_small_kernel(const SmallFused a) {
         const float fwb = wave_sum64(fmaf(f1, wb1, f0 * wb0));
         const float O = s_rayf[4 * lr], m1 = s_rayf[4 * lr + 1];
         const float beta = rin[H], ngv = rin[H + 1];
-        const float dotFg = fu + O * beta;
-        const float nF2 = fmaxf(fGf + 2.0f * O * fwb + O * O * bb, 0.0f);
-        const float nF = fmaxf(sqrtf(nF2), 1e-8f), ngc = fmaxf(ngv, 1e-8f);
-        const float cosv = dotFg / (nF * ngc);
-        lt3 += m1 * (1.0f - cosv) * inv1;
-        const float gam = -a.fs * m1 * inv1;                 // d total / d cos
-        const float ar = gam / (nF * ngc), cr = -gam * cosv / (nF * nF);
-        const float gof = ar * beta + cr * (fwb + O * bb);   // d total / d opacity (feature part)
+        const rayloss::FeatCos fc = rayloss::feat_cos<rayloss::Rcp::exact>(fu, fGf, fwb, O, beta, ngv, bb, m1, a.fs, inv1);
+        lt3 += rayloss::term_feature(fc.cosv, m1, inv1);
+        const float ar = fc.ar, cr = fc.cr;
+        const float gof = rayloss::gof(ar, cr, beta, fwb, O, bb);
         float* rf = a.rayfeat + rr * (H + 3);
         float* x1o = a.X1 + rr * (H + 1);
         float* x2o = a.X2 + rr * (H + 1);
@@ -578,8 +573,8 @@ __global__ __launch_bounds__(512) void train_small_kernel(const SmallFused a) {
           x1o[H] = ar * O; x2o[H] = cr * O;
           s_rayf[4 * lr + 2] = gof;
         }
-        s_dfh[lr * H + lane] = ar * u0 + cr * (gf0 + O * wb0);   // d total / d fh
-        s_dfh[lr * H + lane + 64] = ar * u1 + cr * (gf1 + O * wb1);
+        s_dfh[lr * H + lane] = rayloss::gfh(ar, cr, u0, gf0, O, wb0);
+        s_dfh[lr * H + lane + 64] = rayloss::gfh(ar, cr, u1, gf1, O, wb1);
       }
     }
     __syncthreads();

@@ -35,6 +35,7 @@
 #include "objnerf_device.h"
 #include "objnerf_generic.h"
 #include "objnerf_step_tail.h"
+#include "objnerf_ray_loss.h"
 
 namespace obj256 {
 
@@ -776,8 +777,8 @@ __global__ __launch_bounds__(NW * 64) void fwd256_kernel(const FwdArgs a) {
       l_d = l_c = l_o = l_f = 0.f;
       scale = a.scale[k];
       const float n1 = (float)a.counts[2 * k], n2 = (float)a.counts[2 * k + 1];
-      inv1 = a.flags[0] ? 0.0f : 1.0f / (n1 + 1e-10f);         // render_rays.py:89-94 early return / :103 mean
-      inv2 = a.flags[1] ? 0.0f : 1.0f / (n2 + 1e-10f);
+      inv1 = a.flags[0] ? 0.0f : rayloss::mean_norm(n1);       // render_rays.py:89-94 early return / :103 mean
+      inv2 = a.flags[1] ? 0.0f : rayloss::mean_norm(n2);
     }
     __syncthreads();                                            // ring prologue / tables visible; previous tile done
     ba = s_small[64]; boc0 = s_small[65]; boc1 = s_small[66]; boc2 = s_small[67];
@@ -1128,31 +1129,33 @@ __global__ __launch_bounds__(NW * 64) void fwd256_kernel(const FwdArgs a) {
 #pragma unroll
         for (int e = 0; e < SPL; ++e) { const float dz = zz[e] - D; Vl += wgt[e] * (dz * dz); }
         const float Vv = seg_sum<LPR>(Vl);                               // loss.py:32-33
-        const float m1 = (lab == 1) ? 1.0f : 0.0f, m2 = (lab != 2) ? 1.0f : 0.0f, tgt = (lab != 0) ? 1.0f : 0.0f;
-        const float info = 1.0f / (sqrtf(Vv) + 1e-4f);                   // render_rays.py:96-100
-        const float rd = D - gtd, r0 = C0 - gr, r1 = C1 - gg, r2 = C2 - gb, ro = Oo - tgt;
+        const rayloss::Resid res = rayloss::residuals(D, Oo, C0, C1, C2, Vv, gtd, gr, gg, gb, lab);
+        // (the seeds are written out at this site: through rayloss::seeds the two 32-sample feature instantiations of this
+        // kernel get another order of LDS reads and waits in the compositing -- profiles/ray_loss_refactor.txt)
+        const float m1 = res.m1, m2 = res.m2, info = res.info, rd = res.rd, r0 = res.r0, r1 = res.r1, r2 = res.r2, ro = res.ro;
         auto sgn = [](float x) { return x > 0.f ? 1.0f : (x < 0.f ? -1.0f : 0.0f); };
         const float gD = m1 * sgn(rd) * info * inv1;
         const float gC0 = a.color_scaling * m1 * sgn(r0) * inv1;
         const float gC1 = a.color_scaling * m1 * sgn(r1) * inv1;
         const float gC2 = a.color_scaling * m1 * sgn(r2) * inv1;
         const float gO = a.opacity_scaling * m2 * sgn(ro) * inv2;
+        const rayloss::Seeds sd{gD, gC0, gC1, gC2, gO};
         if (PASS != 2 && on && li == 0) {
-          l_d += m1 * fabsf(rd) * info * inv1;
-          l_c += m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-          l_o += m2 * fabsf(ro) * inv2;
+          l_d += rayloss::term_depth(res, inv1);
+          l_c += rayloss::term_colour(res, inv1);
+          l_o += rayloss::term_opacity(res, inv2);
         }
         if constexpr (PASS == 1) {                                      // ray weights / opacity for the feature step
 #pragma unroll
           for (int e = 0; e < SPL; ++e)
             if (qq < TR) fx[FX_W + qq * S + li * SPL + e] = on ? wgt[e] : 0.0f;
-          if (qq < TR && li == 0) { fx[FX_RQ + 8 * qq] = on ? Oo : 0.0f; fx[FX_RQ + 8 * qq + 1] = on ? m1 : 0.0f; }
+          if (qq < TR && li == 0) { fx[FX_RQ + 8 * qq] = on ? Oo : 0.0f; fx[FX_RQ + 8 * qq + 1] = on ? res.m1 : 0.0f; }
           continue;
         }
         float dw[SPL], qv[SPL], ql_sum = 0.f;
 #pragma unroll
         for (int e = 0; e < SPL; ++e) {
-          dw[e] = gD * zz[e] + gO + gC0 * c0[e] + gC1 * c1[e] + gC2 * c2[e];
+          dw[e] = rayloss::sample_dw(sd, zz[e], c0[e], c1[e], c2[e]);
           if constexpr (PASS == 2) dw[e] += on ? fx[FX_DWV + qq * S + li * SPL + e] : 0.0f;      // the feature term's part
           qv[e] = dw[e] * wgt[e];
           ql_sum += qv[e];
@@ -1164,14 +1167,14 @@ __global__ __launch_bounds__(NW * 64) void fwd256_kernel(const FwdArgs a) {
         float after = sinc - ql_sum;                                   // sum over later lanes
 #pragma unroll
         for (int e = SPL - 1; e >= 0; --e) {
-          const float docc = dw[e] * Tn[e] - after / fr[e];
+          const float docc = rayloss::d_occ(dw[e], Tn[e], after, fr[e]);
           after += qv[e];
           if (on) {
             const int sl = qq * S + li * SPL + e;
-            s_raw[sl] = 10.0f * (docc * occ[e] * (1.0f - occ[e]));     // d / d raw (model.py:88)
-            s_col[sl] = gC0 * wgt[e] * c0[e] * (1.0f - c0[e]);         // d / d colour pre-activation
-            s_col[TSAMP + sl] = gC1 * wgt[e] * c1[e] * (1.0f - c1[e]);
-            s_col[2 * TSAMP + sl] = gC2 * wgt[e] * c2[e] * (1.0f - c2[e]);
+            s_raw[sl] = 10.0f * rayloss::d_alpha(docc, occ[e]);        // d / d raw (model.py:88)
+            s_col[sl] = rayloss::d_raw_colour(sd.gC0, wgt[e], c0[e]);
+            s_col[TSAMP + sl] = rayloss::d_raw_colour(sd.gC1, wgt[e], c1[e]);
+            s_col[2 * TSAMP + sl] = rayloss::d_raw_colour(sd.gC2, wgt[e], c2[e]);
           }
         }
       }
@@ -1284,13 +1287,10 @@ __global__ __launch_bounds__(NW * 64) void fwd256_kernel(const FwdArgs a) {
         for (int ww = 0; ww < NW; ++ww) { fu += fx[FX_RED + 4 * ww]; fGf += fx[FX_RED + 4 * ww + 1]; fwb += fx[FX_RED + 4 * ww + 2]; }
         const float Oq = fx[FX_RQ + 8 * q2], m1 = fx[FX_RQ + 8 * q2 + 1];
         const float bb = wbv[HID], beta = rin[HID], ngv = rin[HID + 1];
-        const float dotFg = fu + Oq * beta;
-        const float nF2 = fmaxf(fGf + 2.0f * Oq * fwb + Oq * Oq * bb, 0.0f);
-        const float nF = fmaxf(sqrtf(nF2), 1e-8f), ngc = fmaxf(ngv, 1e-8f);
-        const float cosv = dotFg / (nF * ngc);
-        const float gam = -a.feat_scaling * m1 * inv1;                    // d total / d cos
-        const float ar = gam / (nF * ngc), cr = -gam * cosv / (nF * nF);
-        fx[FX_DFH + q2 * HID + tid] = ar * uu + cr * (gf + Oq * wbf);      // d total / d fh
+        const rayloss::FeatCos fc = rayloss::feat_cos<rayloss::Rcp::exact>(fu, fGf, fwb, Oq, beta, ngv, bb, m1,
+                                                                          a.feat_scaling, inv1);
+        const float ar = fc.ar, cr = fc.cr;
+        fx[FX_DFH + q2 * HID + tid] = rayloss::gfh(ar, cr, uu, gf, Oq, wbf);
         a.rayfeat[rr * (HID + 3) + tid] = fhv;
         a.X1[rr * (HID + 1) + tid] = ar * fhv;
         a.X2[rr * (HID + 1) + tid] = cr * fhv;
@@ -1299,8 +1299,8 @@ __global__ __launch_bounds__(NW * 64) void fwd256_kernel(const FwdArgs a) {
           rf[HID] = Oq; rf[HID + 1] = ar; rf[HID + 2] = cr;
           a.X1[rr * (HID + 1) + HID] = ar * Oq;
           a.X2[rr * (HID + 1) + HID] = cr * Oq;
-          fx[FX_RQ + 8 * q2 + 2] = ar * beta + cr * (fwb + Oq * bb);       // d total / d opacity (feature part)
-          l_f += m1 * (1.0f - cosv) * inv1;
+          fx[FX_RQ + 8 * q2 + 2] = rayloss::gof(ar, cr, beta, fwb, Oq, bb);
+          l_f += rayloss::term_feature(fc.cosv, m1, inv1);
         }
         __syncthreads();
       }

@@ -223,8 +223,8 @@ __global__ __launch_bounds__(256) void fwdr256_kernel(const FwdArgs a) {
       l_d = l_c = l_o = 0.f;
       scale = rfl(a.scale[k]);
       const float n1 = (float)a.counts[2 * k], n2 = (float)a.counts[2 * k + 1];
-      inv1 = rfl(a.flags[0] ? 0.0f : 1.0f / (n1 + 1e-10f));    // render_rays.py:89-94 early return / :103 mean
-      inv2 = rfl(a.flags[1] ? 0.0f : 1.0f / (n2 + 1e-10f));
+      inv1 = rfl(a.flags[0] ? 0.0f : rayloss::mean_norm(n1));  // render_rays.py:89-94 early return / :103 mean
+      inv2 = rfl(a.flags[1] ? 0.0f : rayloss::mean_norm(n2));
     }
     RSYNC();                                            // tables visible; previous tile done with every buffer
     ba = rfl(s_small[64]); boc0 = rfl(s_small[65]); boc1 = rfl(s_small[66]); boc2 = rfl(s_small[67]);
@@ -612,24 +612,17 @@ __global__ __launch_bounds__(256) void fwdr256_kernel(const FwdArgs a) {
 #pragma unroll
         for (int e = 0; e < SPL; ++e) { const float dz = zz[e] - D; Vl += wgt[e] * (dz * dz); }
         const float Vv = seg_sum<LPR>(Vl);                               // loss.py:32-33
-        const float m1 = (lab == 1) ? 1.0f : 0.0f, m2 = (lab != 2) ? 1.0f : 0.0f, tgt = (lab != 0) ? 1.0f : 0.0f;
-        const float info = 1.0f / (sqrtf(Vv) + 1e-4f);                   // render_rays.py:96-100
-        const float rd = D - gtd, r0 = C0 - gr, r1 = C1 - gg, r2 = C2 - gb, ro = Oo - tgt;
-        auto sgn = [](float x) { return x > 0.f ? 1.0f : (x < 0.f ? -1.0f : 0.0f); };
-        const float gD = m1 * sgn(rd) * info * inv1;
-        const float gC0 = a.color_scaling * m1 * sgn(r0) * inv1;
-        const float gC1 = a.color_scaling * m1 * sgn(r1) * inv1;
-        const float gC2 = a.color_scaling * m1 * sgn(r2) * inv1;
-        const float gO = a.opacity_scaling * m2 * sgn(ro) * inv2;
+        const rayloss::Resid res = rayloss::residuals(D, Oo, C0, C1, C2, Vv, gtd, gr, gg, gb, lab);
+        const rayloss::Seeds sd = rayloss::seeds(res, a.color_scaling, a.opacity_scaling, inv1, inv2);
         if (on && li == 0) {
-          l_d += m1 * fabsf(rd) * info * inv1;
-          l_c += m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-          l_o += m2 * fabsf(ro) * inv2;
+          l_d += rayloss::term_depth(res, inv1);
+          l_c += rayloss::term_colour(res, inv1);
+          l_o += rayloss::term_opacity(res, inv2);
         }
         float dw[SPL], qv[SPL], ql_sum = 0.f;
 #pragma unroll
         for (int e = 0; e < SPL; ++e) {
-          dw[e] = gD * zz[e] + gO + gC0 * c0[e] + gC1 * c1[e] + gC2 * c2[e];
+          dw[e] = rayloss::sample_dw(sd, zz[e], c0[e], c1[e], c2[e]);
           qv[e] = dw[e] * wgt[e];
           ql_sum += qv[e];
         }
@@ -639,14 +632,14 @@ __global__ __launch_bounds__(256) void fwdr256_kernel(const FwdArgs a) {
         float after = sinc - ql_sum;                                   // sum over later lanes
 #pragma unroll
         for (int e = SPL - 1; e >= 0; --e) {
-          const float docc = dw[e] * Tn[e] - after / fr[e];
+          const float docc = rayloss::d_occ(dw[e], Tn[e], after, fr[e]);
           after += qv[e];
           if (on) {
             const int sl = qq * S + li * SPL + e;
-            s_raw[sl] = 10.0f * (docc * occ[e] * (1.0f - occ[e]));     // d / d raw (model.py:88)
-            s_col[sl] = gC0 * wgt[e] * c0[e] * (1.0f - c0[e]);         // d / d colour pre-activation
-            s_col[TSAMP + sl] = gC1 * wgt[e] * c1[e] * (1.0f - c1[e]);
-            s_col[2 * TSAMP + sl] = gC2 * wgt[e] * c2[e] * (1.0f - c2[e]);
+            s_raw[sl] = 10.0f * rayloss::d_alpha(docc, occ[e]);        // d / d raw (model.py:88)
+            s_col[sl] = rayloss::d_raw_colour(sd.gC0, wgt[e], c0[e]);
+            s_col[TSAMP + sl] = rayloss::d_raw_colour(sd.gC1, wgt[e], c1[e]);
+            s_col[2 * TSAMP + sl] = rayloss::d_raw_colour(sd.gC2, wgt[e], c2[e]);
           }
         }
       }

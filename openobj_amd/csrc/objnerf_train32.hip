@@ -12,6 +12,7 @@
 #define OBJ32_PIN 1        // this unit pins the MFMA issue order of mma_f16 and wg_pair (objnerf_mlp32.h)
 #include "objnerf_mlp32.h"
 #include "objnerf_train_common.h"
+#include "objnerf_ray_loss.h"
 #include "../../include/objnerf_hip.h"
 
 using namespace obj32n;
@@ -289,8 +290,8 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
   const float n1 = (float)a.counts[2 * k], n2 = (float)a.counts[2 * k + 1];
   int bflag0, bflag1;
   batch_flags(a, bflag0, bflag1);
-  float inv1 = bflag0 ? 0.0f : 1.0f / (n1 + 1e-10f);
-  float inv2 = bflag1 ? 0.0f : 1.0f / (n2 + 1e-10f);
+  float inv1 = bflag0 ? 0.0f : rayloss::mean_norm(n1);
+  float inv2 = bflag1 ? 0.0f : rayloss::mean_norm(n2);
   if (SKIP) {      // wave-uniform, but the division leaves them in vector registers, which the tile loop then kept in scratch
     inv1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, inv1)));
     inv2 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, inv2)));
@@ -611,27 +612,28 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         const float C2 = sg.total_add(wgt * c2, pos);
         const float dz = zz - D;
         const float V = sg.total_add(wgt * (dz * dz), pos);  // loss.py:32-33
-        const float m1 = (lab == 1) ? 1.0f : 0.0f;                   // mask_sem & mask_obj
-        const float m2 = (lab != 2) ? 1.0f : 0.0f;                   // mask_sem
-        const float tgt = (lab != 0) ? 1.0f : 0.0f;                  // mask_obj.float()
-        const float info = 1.0f / (sqrtf(V) + 1e-4f);                // render_rays.py:96-100
-        const float rd = D - gtd, r0 = C0 - gr, r1 = C1 - gg, r2 = C2 - gb, ro = O - tgt;
+        const rayloss::Resid res = rayloss::residuals(D, O, C0, C1, C2, V, gtd, gr, gg, gb, lab);
+        // In this pass loop the seeds, d_occ / d_alpha and the feature cosine stay written out (the definitions are
+        // rayloss::seeds, d_occ, d_alpha, feat_cos, gof, gfh, term_feature, which the 64-sample path below calls): through
+        // the header the any-S instantiations get other waits and another order of LDS reads and MFMAs
+        // (profiles/ray_loss_refactor.txt).
+        const float m1 = res.m1, m2 = res.m2, info = res.info, rd = res.rd, r0 = res.r0, r1 = res.r1, r2 = res.r2, ro = res.ro;
         auto sgn = [](float x) { return x > 0.f ? 1.0f : (x < 0.f ? -1.0f : 0.0f); };
         const float gD = m1 * sgn(rd) * info * inv1;
         const float gC0 = a.color_scaling * m1 * sgn(r0) * inv1;
         const float gC1 = a.color_scaling * m1 * sgn(r1) * inv1;
         const float gC2 = a.color_scaling * m1 * sgn(r2) * inv1;
         const float gO = a.opacity_scaling * m2 * sgn(ro) * inv2;
+        const rayloss::Seeds sd{gD, gC0, gC1, gC2, gO};
         if (on && pos == 0) {
-          l_d += m1 * fabsf(rd) * info * inv1;
-          l_c += m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-          l_o += m2 * fabsf(ro) * inv2;
+          l_d += rayloss::term_depth(res, inv1);
+          l_c += rayloss::term_colour(res, inv1);
+          l_o += rayloss::term_opacity(res, inv2);
         }
-        float dw = gD * zz + gO + gC0 * c0 + gC1 * c1 + gC2 * c2;
+        float dw = rayloss::sample_dw(sd, zz, c0, c1, c2);
         if (FEAT) {
-          // ---- feature-distillation term (loss.py:82-99) with the linear 512-d head hoisted past the
-          // compositing: F = W_of fh + b_of O,  fh = sum_s w_s hf_s.  cos(F, g) only needs
-          //   F.g = fh.u + O beta,   |F|^2 = fh^T G fh + 2 O wb.fh + O^2 bb     (u, beta, G, wb, bb precomputed)
+          // ---- feature-distillation term (loss.py:82-99) in its hoisted form (the arithmetic of rayloss::feat_cos,
+          // spelt out): fh = sum_s w_s hf_s, then fh . u, fh^T G fh and fh . wb per ray
           float* s_w = stg + F_SW;
           float* s_gfh = stg + F_GFH;
           float* s_gof = stg + F_GOF;
@@ -716,9 +718,9 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         const float docc = dw * T - suf / fr;
         if (on) {                                                    // in place: this lane owns slot sl
           s_alpha[sl] = 10.0f * (docc * occ * (1.0f - occ));         // d / d raw alpha (model.py:88)
-          s_col[sl] = gC0 * wgt * c0 * (1.0f - c0);                  // d / d raw colour (pre-sigmoid)
-          s_col[TS + sl] = gC1 * wgt * c1 * (1.0f - c1);
-          s_col[2 * TS + sl] = gC2 * wgt * c2 * (1.0f - c2);
+          s_col[sl] = rayloss::d_raw_colour(gC0, wgt, c0);
+          s_col[TS + sl] = rayloss::d_raw_colour(gC1, wgt, c1);
+          s_col[2 * TS + sl] = rayloss::d_raw_colour(gC2, wgt, c2);
         }
       }
     };
@@ -754,24 +756,16 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         const float C2 = sg.total_add(wgt * c2, pos);
         const float dz = zz - D;
         const float V = sg.total_add(wgt * (dz * dz), pos);
-        const float m1 = (pf_lab == 1) ? 1.0f : 0.0f;
-        const float m2 = (pf_lab != 2) ? 1.0f : 0.0f;
-        const float tgt = (pf_lab != 0) ? 1.0f : 0.0f;
-        const float info = 1.0f / (sqrtf(V) + 1e-4f);
-        const float rd = D - pf_gtd, r0 = C0 - pf_gr, r1 = C1 - pf_gg, r2 = C2 - pf_gb, ro = O - tgt;
-        auto sgn = [](float x) { return x > 0.f ? 1.0f : (x < 0.f ? -1.0f : 0.0f); };
-        const float gD = m1 * sgn(rd) * info * inv1;
-        gC0 = a.color_scaling * m1 * sgn(r0) * inv1;
-        gC1 = a.color_scaling * m1 * sgn(r1) * inv1;
-        gC2 = a.color_scaling * m1 * sgn(r2) * inv1;
-        const float gO = a.opacity_scaling * m2 * sgn(ro) * inv2;
+        const rayloss::Resid res = rayloss::residuals(D, O, C0, C1, C2, V, pf_gtd, pf_gr, pf_gg, pf_gb, pf_lab);
+        const rayloss::Seeds sd = rayloss::seeds(res, a.color_scaling, a.opacity_scaling, inv1, inv2);
+        gC0 = sd.gC0; gC1 = sd.gC1; gC2 = sd.gC2;
         if (on && pos == 0) {
-          l_d += m1 * fabsf(rd) * info * inv1;
-          l_c += m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-          l_o += m2 * fabsf(ro) * inv2;
+          l_d += rayloss::term_depth(res, inv1);
+          l_c += rayloss::term_colour(res, inv1);
+          l_o += rayloss::term_opacity(res, inv2);
           s_gof[16 + w] = O;
         }
-        dw = gD * zz + gO + gC0 * c0 + gC1 * c1 + gC2 * c2;
+        dw = rayloss::sample_dw(sd, zz, c0, c1, c2);
         if (on) s_w[sl] = wgt;
       }
       TILE_SYNC();
@@ -804,19 +798,16 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         const float uh = pf_uh, beta = pf_beta, ngv = pf_ngv;
         const float O2 = valid ? s_gof[16 + q] : 0.f;
         const float fu = wave_sum32(fh * uh), fGf = wave_sum32(fh * Gfh), fwb = wave_sum32(fh * wbh);
-        const float dotFg = fu + O2 * beta;
-        const float nF2 = fmaxf(fGf + 2.0f * O2 * fwb + O2 * O2 * bb, 0.0f);
-        const float nF = fmaxf(sqrtf(nF2), 1e-8f), ngc = fmaxf(ngv, 1e-8f);
-        const float cosv = dotFg / (nF * ngc);
         const float mm1 = (pf_lab2 == 1) ? 1.0f : 0.0f;
-        const float gam = -a.feat_scaling * mm1 * inv1;
-        const float ar = gam / (nF * ngc), cr = -gam * cosv / (nF * nF);
-        const float gfh = ar * uh + cr * (Gfh + O2 * wbh);
-        const float gof = ar * beta + cr * (fwb + O2 * bb);
+        const rayloss::FeatCos fc = rayloss::feat_cos<rayloss::Rcp::exact>(fu, fGf, fwb, O2, beta, ngv, bb, mm1,
+                                                                          a.feat_scaling, inv1);
+        const float ar = fc.ar, cr = fc.cr;
+        const float gfh = rayloss::gfh(ar, cr, uh, Gfh, O2, wbh);
+        const float gof = rayloss::gof(ar, cr, beta, fwb, O2, bb);
         if (valid && (w & 3) == 0 && half == 0) {
           const long rr2 = (long)k * R + ray;
           if (hh == 0) {
-            l_f += mm1 * (1.0f - cosv) * inv1;
+            l_f += rayloss::term_feature(fc.cosv, mm1, inv1);
             a.rayfeat[rr2 * RAYFEAT + 32] = O2;
             a.rayfeat[rr2 * RAYFEAT + 33] = ar;
             a.rayfeat[rr2 * RAYFEAT + 34] = cr;
@@ -841,12 +832,12 @@ __global__ __launch_bounds__(NTHR) void train_fused32_kernel(const TrainDev a) {
         if (on) dw += s_dwf[sl];
         const float qv = dw * wgt;
         const float suf = sg.rscan_add(qv, pos) - qv;
-        const float docc = dw * T - suf / fr;
+        const float docc = rayloss::d_occ(dw, T, suf, fr);
         if (on) {
-          s_alpha[sl] = 10.0f * (docc * occ * (1.0f - occ));
-          s_col[sl] = gC0 * wgt * c0 * (1.0f - c0);
-          s_col[TS + sl] = gC1 * wgt * c1 * (1.0f - c1);
-          s_col[2 * TS + sl] = gC2 * wgt * c2 * (1.0f - c2);
+          s_alpha[sl] = 10.0f * rayloss::d_alpha(docc, occ);
+          s_col[sl] = rayloss::d_raw_colour(gC0, wgt, c0);
+          s_col[TS + sl] = rayloss::d_raw_colour(gC1, wgt, c1);
+          s_col[2 * TS + sl] = rayloss::d_raw_colour(gC2, wgt, c2);
         }
       }
     } else if ((OBJ32_ABL) & 1) { /* ablation: no compositing */

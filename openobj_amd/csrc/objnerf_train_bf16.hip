@@ -16,6 +16,7 @@
 // cross-group sum on the matrix core, no fp32 table in LDS) and d B accumulates in 18 registers.  Only octave 0 gets
 // // its own ... (placeholder)
 #include "objnerf_bf16_common.h"
+#include "objnerf_ray_loss.h"
 #include "../../include/objnerf_hip.h"
 
 namespace objtrain {
@@ -144,8 +145,8 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
   const float n1 = (float)a.counts[2 * k], n2 = (float)a.counts[2 * k + 1];
   int bflag0, bflag1;
   batch_flags(a, bflag0, bflag1);
-  const float inv1 = bflag0 ? 0.0f : 1.0f / (n1 + 1e-10f);
-  const float inv2 = bflag1 ? 0.0f : 1.0f / (n2 + 1e-10f);
+  const float inv1 = bflag0 ? 0.0f : rayloss::mean_norm(n1);
+  const float inv2 = bflag1 ? 0.0f : rayloss::mean_norm(n2);
 
   f32x4 accA0 = zero4(), accA1 = zero4(), accB0 = zero4(), accB1 = zero4(), accC0 = zero4(), accC1 = zero4();
   // Row sums over the samples (head weights, mid1 / mid2 biases): transposing DPP butterflies into slot registers per
@@ -351,15 +352,7 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
     };
     float pf_uh = 0.f, pf_beta = 0.f, pf_ngv = 1.f;
     int pf_lab2 = 2;
-    if (FEAT && S == 64) {
-      if (valid) {        // every wave takes part in its ray's feature term (below)
-        const long rr2_ = (long)k * R + ray;
-        pf_uh = a.rayin[rr2_ * RAYIN + (lane_l & 31)];
-        pf_beta = a.rayin[rr2_ * RAYIN + 32];
-        pf_ngv = a.rayin[rr2_ * RAYIN + 33];
-        pf_lab2 = (int)a.labels[rr2_];
-      }
-    } else if (FEAT && w * (64 / S) < TR) feat_inputs(w, 0, pf_uh, pf_beta, pf_ngv, pf_lab2);
+    if (FEAT && w * (64 / S) < TR) feat_inputs(w, 0, pf_uh, pf_beta, pf_ngv, pf_lab2);
     __syncthreads();
     RELAUNDER();
     // ---------------------------------------------------------------- 2. composite + loss (fp32, as objnerf_train32.hip)
@@ -390,23 +383,14 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
         const float C2 = sg.total_add(wgt * c2, pos);
         const float dz = zz - D;
         const float V = sg.total_add(wgt * (dz * dz), pos);
-        const float m1 = (lab == 1) ? 1.0f : 0.0f;
-        const float m2 = (lab != 2) ? 1.0f : 0.0f;
-        const float tgt = (lab != 0) ? 1.0f : 0.0f;
-        const float info = 1.0f / (sqrtf(V) + 1e-4f);
-        const float rd = D - gtd, r0 = C0 - gr, r1 = C1 - gg, r2 = C2 - gb, ro = O - tgt;
-        auto sgn = [](float x) { return x > 0.f ? 1.0f : (x < 0.f ? -1.0f : 0.0f); };
-        const float gD = m1 * sgn(rd) * info * inv1;
-        const float gC0 = a.color_scaling * m1 * sgn(r0) * inv1;
-        const float gC1 = a.color_scaling * m1 * sgn(r1) * inv1;
-        const float gC2 = a.color_scaling * m1 * sgn(r2) * inv1;
-        const float gO = a.opacity_scaling * m2 * sgn(ro) * inv2;
+        const rayloss::Resid res = rayloss::residuals(D, O, C0, C1, C2, V, gtd, gr, gg, gb, lab);
+        const rayloss::Seeds sd = rayloss::seeds(res, a.color_scaling, a.opacity_scaling, inv1, inv2);
         if (on && pos == 0) {
-          l_d += m1 * fabsf(rd) * info * inv1;
-          l_c += m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-          l_o += m2 * fabsf(ro) * inv2;
+          l_d += rayloss::term_depth(res, inv1);
+          l_c += rayloss::term_colour(res, inv1);
+          l_o += rayloss::term_opacity(res, inv2);
         }
-        float dw = gD * zz + gO + gC0 * c0 + gC1 * c1 + gC2 * c2;
+        float dw = rayloss::sample_dw(sd, zz, c0, c1, c2);
         if (FEAT) {
           // feature-distillation term with the 512-d head hoisted past the compositing (objnerf_train32.hip, 4.3 of
           // DESIGN.md): fp32 throughout, only the hidden feature itself came out of bf16 MFMAs
@@ -457,22 +441,19 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
             if (ps != w || qb != 0) feat_inputs(ps, qb, uh, beta, ngv, lab2);
             const float O2 = on2 ? s_gof[16 + qq2] : 0.f;
             const float fu = wave_sum32(fh * uh), fGf = wave_sum32(fh * Gfh), fwb = wave_sum32(fh * wbh);
-            const float dotFg = fu + O2 * beta;
-            const float nF2 = fmaxf(fGf + 2.0f * O2 * fwb + O2 * O2 * bb, 0.0f);
-            const float nF = fmaxf(sqrtf(nF2), 1e-8f), ngc = fmaxf(ngv, 1e-8f);
-            const float cosv = dotFg / (nF * ngc);
             const float mm1 = (lab2 == 1) ? 1.0f : 0.0f;
-            const float gam = -a.feat_scaling * mm1 * inv1;
-            const float ar = gam / (nF * ngc), cr = -gam * cosv / (nF * nF);
+            const rayloss::FeatCos fc = rayloss::feat_cos<rayloss::Rcp::exact>(fu, fGf, fwb, O2, beta, ngv, bb, mm1,
+                                                                              a.feat_scaling, inv1);
+            const float ar = fc.ar, cr = fc.cr;
             if (on2) {
               if (hh == 0) {
-                l_f += mm1 * (1.0f - cosv) * inv1;
-                s_gof[qq2] = ar * beta + cr * (fwb + O2 * bb);
+                l_f += rayloss::term_feature(fc.cosv, mm1, inv1);
+                s_gof[qq2] = rayloss::gof(ar, cr, beta, fwb, O2, bb);
                 a.rayfeat[rr2 * RAYFEAT + 32] = O2;
                 a.rayfeat[rr2 * RAYFEAT + 33] = ar;
                 a.rayfeat[rr2 * RAYFEAT + 34] = cr;
               }
-              s_gfh[qq2 * 32 + hh] = ar * uh + cr * (Gfh + O2 * wbh);
+              s_gfh[qq2 * 32 + hh] = rayloss::gfh(ar, cr, uh, Gfh, O2, wbh);
               a.rayfeat[rr2 * RAYFEAT + hh] = fh;
             }
             __builtin_amdgcn_wave_barrier();
@@ -487,140 +468,16 @@ __global__ __launch_bounds__(NTHR) void train_fused_bf16_kernel(const TrainDev a
         }
         const float qv = dw * wgt;
         const float suf = sg.rscan_add(qv, pos) - qv;
-        const float docc = dw * T - suf / fr;
+        const float docc = rayloss::d_occ(dw, T, suf, fr);
         if (on) {
-          s_alpha[sl] = 10.0f * (docc * occ * (1.0f - occ));
-          s_col[sl] = gC0 * wgt * c0 * (1.0f - c0);
-          s_col[TS + sl] = gC1 * wgt * c1 * (1.0f - c1);
-          s_col[2 * TS + sl] = gC2 * wgt * c2 * (1.0f - c2);
+          s_alpha[sl] = 10.0f * rayloss::d_alpha(docc, occ);
+          s_col[sl] = rayloss::d_raw_colour(sd.gC0, wgt, c0);
+          s_col[TS + sl] = rayloss::d_raw_colour(sd.gC1, wgt, c1);
+          s_col[2 * TS + sl] = rayloss::d_raw_colour(sd.gC2, wgt, c2);
         }
       }
     };
-    if (FEAT && S == 64) {
-      // 64 samples per ray (the north-star shape): the feature term's reductions over samples and hidden features
-      // are spread over all 8 waves instead of running on the two compositing waves (3 extra barriers, ~5x shorter
-      // critical path).  Wave w holds samples 16w..16w+15 of ray w >> 2.
-      const SegRows& sg = seg_rows;
-      const int pos = lane_l;
-      const int sl = w * 64 + pos;
-      const bool on = (w < TR) && (ray0 + w < R);
-      float occ = 0.f, fr = 1.f, T = 1.f, wgt = 0.f, dw = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, gC0 = 0.f, gC1 = 0.f, gC2 = 0.f;
-      if (w < TR) {
-        const float zz = pf_zz;
-        float al = 0.f;
-        if (on) { al = s_alpha[sl]; c0 = s_col[sl]; c1 = s_col[TS + sl]; c2 = s_col[2 * TS + sl]; }
-        occ = on ? sigmoid_acc(al) : 0.0f;
-        fr = on ? (1.0f - occ) + 1e-10f : 1.0f;
-        const float Pinc = sg.scan_mul(fr, pos);
-        T = __shfl_up(Pinc, 1, 64);
-        if (pos == 0) T = 1.0f;
-        wgt = occ * T;
-        const float D = sg.total_add(wgt * zz, pos);
-        const float O = sg.total_add(wgt, pos);
-        const float C0 = sg.total_add(wgt * c0, pos);
-        const float C1 = sg.total_add(wgt * c1, pos);
-        const float C2 = sg.total_add(wgt * c2, pos);
-        const float dz = zz - D;
-        const float V = sg.total_add(wgt * (dz * dz), pos);
-        const float m1 = (pf_lab == 1) ? 1.0f : 0.0f;
-        const float m2 = (pf_lab != 2) ? 1.0f : 0.0f;
-        const float tgt = (pf_lab != 0) ? 1.0f : 0.0f;
-        const float info = 1.0f / (sqrtf(V) + 1e-4f);
-        const float rd = D - pf_gtd, r0 = C0 - pf_gr, r1 = C1 - pf_gg, r2 = C2 - pf_gb, ro = O - tgt;
-        auto sgn = [](float x) { return x > 0.f ? 1.0f : (x < 0.f ? -1.0f : 0.0f); };
-        const float gD = m1 * sgn(rd) * info * inv1;
-        gC0 = a.color_scaling * m1 * sgn(r0) * inv1;
-        gC1 = a.color_scaling * m1 * sgn(r1) * inv1;
-        gC2 = a.color_scaling * m1 * sgn(r2) * inv1;
-        const float gO = a.opacity_scaling * m2 * sgn(ro) * inv2;
-        if (on && pos == 0) {
-          l_d += m1 * fabsf(rd) * info * inv1;
-          l_c += m1 * (fabsf(r0) + fabsf(r1) + fabsf(r2)) * inv1;
-          l_o += m2 * fabsf(ro) * inv2;
-          s_gof[16 + w] = O;
-        }
-        dw = gD * zz + gO + gC0 * c0 + gC1 * c1 + gC2 * c2;
-        if (on) s_w[sl] = wgt;
-      }
-      __syncthreads();
-      float* s_part = s_gfh + 192;          // [NWAVE][32] partial composited features (s_gfh holds 2 rays here)
-      float* s_dwf = s_gfh + 64;            // [128]
-      {
-        const float wv = valid ? s_w[slot] : 0.0f;
-        float v8[8];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v8[4 * tt + r] = wv * stgf[FA_HF + slot * HF_LD + 16 * tt + 4 * g + r];
-        const float psum = slot_sums8(v8, c);
-        if (c < 8) s_part[w * 32 + 16 * ((c & 7) >> 2) + 4 * g + (c & 3)] = psum;
-      }
-      __syncthreads();
-      {
-        float* s_fhb = stgf + FA_FHB + 64 * w;
-        const float* Gb = stgf + FA_G;
-        const int half = lane_l >> 5, hh = lane_l & 31;
-        const int w0 = w & ~3;
-        const float fh = valid ? (s_part[w0 * 32 + hh] + s_part[(w0 + 1) * 32 + hh]) +
-                                 (s_part[(w0 + 2) * 32 + hh] + s_part[(w0 + 3) * 32 + hh]) : 0.0f;
-        if (half == 0) s_fhb[hh] = fh;
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("" ::: "memory");
-        float Gp = 0.f;
-#pragma unroll
-        for (int h2 = 0; h2 < 16; ++h2) Gp = fmaf(Gb[hh * 33 + 16 * half + h2], s_fhb[16 * half + h2], Gp);
-        const float Gfh = Gp + __shfl_xor(Gp, 32, 64);
-        const float wbh = Gb[32 * 33 + hh], bb = Gb[32 * 33 + 32];
-        const float uh = pf_uh, beta = pf_beta, ngv = pf_ngv;
-        const float O2 = valid ? s_gof[16 + q] : 0.f;
-        const float fu = wave_sum32(fh * uh), fGf = wave_sum32(fh * Gfh), fwb = wave_sum32(fh * wbh);
-        const float dotFg = fu + O2 * beta;
-        const float nF2 = fmaxf(fGf + 2.0f * O2 * fwb + O2 * O2 * bb, 0.0f);
-        const float nF = fmaxf(__builtin_amdgcn_sqrtf(nF2), 1e-8f), ngc = fmaxf(ngv, 1e-8f);
-        const float rnn = __builtin_amdgcn_rcpf(nF * ngc);       // (bf16 mode: 1-ulp hardware reciprocals)
-        const float cosv = dotFg * rnn;
-        const float mm1 = (pf_lab2 == 1) ? 1.0f : 0.0f;
-        const float gam = -a.feat_scaling * mm1 * inv1;
-        const float ar = gam * rnn, cr = -gam * cosv * __builtin_amdgcn_rcpf(nF * nF);
-        const float gfh = ar * uh + cr * (Gfh + O2 * wbh);
-        const float gof = ar * beta + cr * (fwb + O2 * bb);
-        if (valid && (w & 3) == 0 && half == 0) {
-          const long rr2 = (long)k * R + ray;
-          if (hh == 0) {
-            l_f += mm1 * (1.0f - cosv) * inv1;
-            a.rayfeat[rr2 * RAYFEAT + 32] = O2;
-            a.rayfeat[rr2 * RAYFEAT + 33] = ar;
-            a.rayfeat[rr2 * RAYFEAT + 34] = cr;
-          }
-          s_gfh[q * 32 + hh] = gfh;
-          a.rayfeat[rr2 * RAYFEAT + hh] = fh;
-        }
-        if (half == 0) s_fhb[32 + hh] = gfh;
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("" ::: "memory");
-        float dp = 0.f;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            dp = fmaf(s_fhb[32 + 16 * tt + 4 * g + r], stgf[FA_HF + slot * HF_LD + 16 * tt + 4 * g + r], dp);
-        const float dwf = xgroup_sum(dp) + gof;
-        if (g == 0 && valid) s_dwf[slot] = dwf;
-      }
-      __syncthreads();
-      if (w < TR) {
-        if (on) dw += s_dwf[sl];
-        const float qv = dw * wgt;
-        const float suf = sg.rscan_add(qv, pos) - qv;
-        const float docc = dw * T - suf / fr;
-        if (on) {
-          s_alpha[sl] = 10.0f * (docc * occ * (1.0f - occ));
-          s_col[sl] = gC0 * wgt * c0 * (1.0f - c0);
-          s_col[TS + sl] = gC1 * wgt * c1 * (1.0f - c1);
-          s_col[2 * TS + sl] = gC2 * wgt * c2 * (1.0f - c2);
-        }
-      }
-    } else if (rows_mode) composite_passes(seg_rows); else composite_passes(SegGeneric{S});
+    if (rows_mode) composite_passes(seg_rows); else composite_passes(SegGeneric{S});
     __syncthreads();
     RELAUNDER();
     // ---------------------------------------------------------------- 3. backward
@@ -897,7 +754,7 @@ void launch_train_bf16(const TrainDev& d, void* stream, bool feat) {
     (void)hipFuncSetAttribute((const void*)train_fused_bf16_kernel<false>, at, LDS_BYTES);
     (void)hipFuncSetAttribute((const void*)train_fused_bf16_kernel<true>, at, LDS_BYTES);
   });
-  if (d.S == 64) {
+  if (d.S == 64) {      // (this is the only launcher: train_fused_bf16_kernel holds no code for 64 samples per ray)
     if (feat) launch_train_bf16_v2f(d, stream); else launch_train_bf16_v2(d, stream);
     return;
   }
