@@ -1309,6 +1309,70 @@ int objnerf_regions_table(int64_t V, int64_t F, int32_t S, int32_t Q, int32_t q,
                           const int32_t* root, const int32_t* label, int64_t R, int64_t* table, int32_t* status,
                           void* stream);
 
+/* A rasteriser for the map's meshes: one view of the exported map, whatever colours its vertices carry
+ * (objnerf_mapraster.hip; openobj_amd/map_raster.py).  Added under ABI 14: the entries below are purely
+ * additive, so OBJNERF_ABI_VERSION stays 14.  The map as the part regions take it: verts fp64 [V][3], faces int32 [F][3]
+ * of PACKED vertex ids, face_off int64 [S + 1] (face f belongs to the object whose range holds f), plus hide uint8 [S],
+ * ids int32 [S] (the value of the mask-id image), t_cw fp64 [3][4] on the device = the upper rows of inverse(T_WC),
+ * inverted by the caller in fp64.  Images are [W][H], w-major (p = w H + h).  0 <= V, F <= 2^31 - 1, 0 <= S <= 65535
+ * (F > 0 needs V, S >= 1), 1 <= W, H <= 65536, W H <= 2^31 - 1, z_near > 0; EINVAL otherwise, for a null pointer and for
+ * a short workspace, before any launch.  Nothing is allocated.  The result is THESE BYTES, whatever the kernels do:
+ *
+ * VERTEX p, in fp64, every operation rounded once, M = t_cw:
+ *    xc = ((M[0] px + M[1] py) + M[2] pz) + M[3]            (yc: M[4..7], zc: M[8..11]; objnerf_vertex_views' sequence)
+ *    u = (fx xc) / zc + cx,   v = (fy yc) / zc + cy
+ *    X = floor(u 256 + 0.5),  Y = floor(v 256 + 0.5)
+ *    ok = zc >= z_near and |X| <= 2^25 and |Y| <= 2^25     (compared as doubles, before any conversion; a NaN: not ok)
+ *    iz = 1 / zc
+ * A vertex that fails zc >= z_near is dropped "by z_near", one that passes it and fails the bound "by the bound".  The
+ * sample point of pixel (i, j) is (256 i, 256 j).
+ * FACE f of object s is drawn iff its three ids lie in [0, V) (else status bit 0 is raised and nothing is read through
+ * them), hide[s] == 0, its three vertices are ok (no near-plane clipping), and
+ *    A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) != 0                                                          (int64)
+ * If A < 0, corners 1 and 2 are swapped (both sides are drawn) and A = -A.  With E(a, b, P) = (bx - ax)(Py - ay) -
+ * (by - ay)(Px - ax):  w0 = E(v1, v2, P), w1 = E(v2, v0, P), w2 = E(v0, v1, P); pixel P is covered iff w0, w1, w2 >= 0
+ * (no top-left rule: a pixel on a shared edge is covered by both faces and the key decides).  Every w is below 2^53, so
+ * (double) w is exact.
+ *    q = ((w0 iz0) + (w1 iz1)) + (w2 iz2),   z = (double) A / q,   d = (float) z
+ *    key = (uint64(bits(d)) << 32) | f
+ * key [W][H] holds the minimum key per pixel, all ones where nothing is drawn: the nearest face, the lowest face id at
+ * equal fp32 depth.
+ * stats int64 [8]: every face adds one to exactly one counter, the first of this list that applies:
+ *    6 a bad index   7 hidden   3 a corner dropped by z_near   4 a corner dropped by the bound   5 degenerate (A = 0)
+ *    2 without any sample (the box of the face, clipped to the screen, holds no sample point)
+ *    0 drawn on the small path (the clipped box is at most small_box pixels wide and high)   1 drawn on the large path
+ * small_box: a private knob as the _workgroups arguments are (negative: the default, 4; 0: every face takes the large
+ * path; INT32_MAX: every face the small one): the images do not depend on it, only counters 0 and 1.
+ *
+ * objnerf_raster_visibility: ws [objnerf_raster_workspace_bytes(V, F)] (0: sizes out of range) -> key, stats (both
+ * cleared here) and status (one int32 the caller zeroes; bits are OR-ed in); ws then holds the vertex records that
+ * objnerf_raster_resolve reads.  Launches: vertices, faces (small faces in the thread; the others appended to a list),
+ * the list (its length read on the device by a fixed grid).  64-bit integer atomicMin / atomicAdd only.
+ * passes: 0 for a caller.  DIAGNOSTIC, for tools/raster_bench.py: a bit mask of the launches to run on what an earlier
+ * whole call left in ws (1: vertices; 2: the clears and the faces; 4: the list), so that each can be timed.
+ *
+ * objnerf_raster_resolve (same V, F, S, W, H, verts, faces, face_off, ws, key): per pixel with a key, face = the low
+ * 32 bits, winner = s, maskid = ids[s], depth = d, and with t_k = w_k iz_k (the products of q)
+ *    vertex = the packed id of the corner with the largest t_k (fp64; a tie: the first corner in the swapped order)
+ *    b_k = t_k / q,   c = ((b0 c0) + (b1 c1)) + (b2 c2)    per channel, c_k = (double) colors[corner k] (fp32 [V][3])
+ *    shading = 1:  c = c shade,  shade = ambient + (1 - ambient) (|n . g| / (|n| |g|)),  e1 = p1 - p0, e2 = p2 - p0,
+ *                  n = e1 x e2 (each component two products, one difference), g = ((p0 + p1) + p2) / 3 - cam,
+ *                  n . g = (nx gx + ny gy) + nz gz, |x| = sqrt((xx xx + xy xy) + xz xz); the corners in the face's OWN
+ *                  order, world coordinates; shade = 1 where |n| |g| is not > 0
+ *    rgb = floor(clamp(c, 0, 1) 255 + 0.5)                  (a NaN counts as 0)
+ * A pixel without a key: winner -1, maskid 0, depth 100, face -1, vertex -1, rgb = background (0xRRGGBB).
+ * counts int64 [S] (cleared here): the pixels each object wins, integer adds.  0 <= ambient <= 1. */
+size_t objnerf_raster_workspace_bytes(int64_t V, int64_t F);
+int objnerf_raster_visibility(int64_t V, int64_t F, int32_t S, int32_t W, int32_t H, const double* verts,
+                              const int32_t* faces, const int64_t* face_off, const uint8_t* hide, const double* t_cw,
+                              double fx, double fy, double cx, double cy, double z_near, int32_t small_box,
+                              int32_t passes, void* ws, size_t ws_bytes, uint64_t* key, int64_t* stats, int32_t* status, void* stream);
+int objnerf_raster_resolve(int64_t V, int64_t F, int32_t S, int32_t W, int32_t H, const double* verts,
+                           const int32_t* faces, const int64_t* face_off, const int32_t* ids, const float* colors,
+                           const void* ws, size_t ws_bytes, const uint64_t* key, double cam_x, double cam_y, double cam_z,
+                           double ambient, int32_t shading, int32_t background, uint8_t* rgb, int32_t* maskid, float* depth,
+                           int32_t* winner, int32_t* face, int32_t* vertex, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,10 +45,10 @@ def _width(all_obj, key):
     return None
 
 
-def _parse(argv):
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+def add_map_arguments(ap, extra_modes=()) -> None:
+    """The arguments that name the map, the colouring and its queries (shared with map_raster's CLI)."""
     ap.add_argument("--logdir", required=True)
-    ap.add_argument("--mode", required=True, choices=MODES)
+    ap.add_argument("--mode", required=True, choices=MODES + tuple(extra_modes))
     ap.add_argument("--clip-query")
     ap.add_argument("--sbert-query")
     ap.add_argument("--part-query")
@@ -59,6 +59,11 @@ def _parse(argv):
     ap.add_argument("--out", required=True)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--compact", action="store_true", help="read map_vis_compact.pkl.gz")
+
+
+def _parse(argv):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    add_map_arguments(ap)
     ap.add_argument("--regions", action="store_true", help="--mode part: also write regions.json and obj_<id>_regions.ply")
     ap.add_argument("--region-frac", type=float, default=None)
     ap.add_argument("--region-min-cos", type=float, default=None)
@@ -77,6 +82,13 @@ def _parse(argv):
         ap.error(f"--region-min-cos {a.region_min_cos} outside [-1, 1]")
     if a.region_min_area is not None and not a.region_min_area >= 0.0:
         ap.error(f"--region-min-area {a.region_min_area} is negative")
+    all_obj, queries = check_map_arguments(ap, a)
+    return a, all_obj, queries
+
+
+def check_map_arguments(ap, a):
+    """The checks of add_map_arguments' values (ap.error on the first that fails) -> (all_obj: the map file's dict,
+    queries: name -> fp32 vector, the ones the mode needs); a.map_file is set."""
     for k in NEEDS.get(a.mode, ()):
         v = getattr(a, k)
         if v is None:
@@ -101,7 +113,24 @@ def _parse(argv):
         if w is None or q.size != w:
             ap.error(f"--{k.replace('_', '-')}: width {q.size} does not match the map's {feat} width {w}")
         queries[k] = q
-    return a, all_obj, queries
+    return all_obj, queries
+
+
+def colors_for_mode(mq, mode: str, q, top=None, color_yaml=None):
+    """The mode -> colours dispatch of the CLIs: -> [V, 3] on the device.  q: check_map_arguments' queries."""
+    if mode == "rgb":
+        return mq.color_by_rgb()
+    if mode == "class":
+        return mq.color_by_class(color_yaml)
+    if mode == "instance":
+        return mq.color_by_instance()
+    if mode in ("partpca", "partfeat"):                     # (map_raster's CLI takes either name)
+        return mq.color_by_partfeat()
+    if mode == "object":
+        return mq.color_by_object_query(q["clip_query"], q["sbert_query"], 0 if top is None else top)
+    if mode == "part":
+        return mq.color_by_part_query(q["clip_query"], q["sbert_query"], q["part_query"], 1 if top is None else top)
+    raise ValueError(f"colors_for_mode: mode {mode!r}: one of {MODES}")
 
 
 def main(argv=None):
@@ -109,18 +138,7 @@ def main(argv=None):
     from . import mesh as omesh
     from . import query as oquery
     mq = oquery.MapQuery(all_obj, a.device)
-    if a.mode == "rgb":
-        col = mq.color_by_rgb()
-    elif a.mode == "class":
-        col = mq.color_by_class(a.color_yaml)
-    elif a.mode == "instance":
-        col = mq.color_by_instance()
-    elif a.mode == "partpca":
-        col = mq.color_by_partfeat()
-    elif a.mode == "object":
-        col = mq.color_by_object_query(q["clip_query"], q["sbert_query"], 0 if a.top is None else a.top)
-    else:
-        col = mq.color_by_part_query(q["clip_query"], q["sbert_query"], q["part_query"], 1 if a.top is None else a.top)
+    col = colors_for_mode(mq, a.mode, q, a.top, a.color_yaml)
     hidden = set(mq.hidden_sets(a.dataset, a.scene)["hidden"]) if a.dataset else set()
     os.makedirs(a.out, exist_ok=True)
     visible = []

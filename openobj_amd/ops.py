@@ -2689,3 +2689,109 @@ def regions_table(vert_off: torch.Tensor, face_off: torch.Tensor, verts: torch.T
                                       _ptr(faces) if F else None, _ptr(sims), _ptr(root), _ptr(label), R,
                                       _ptr(table) if R > 0 else None, _ptr(status), _stream()), "objnerf_regions_table")
     return table
+
+
+# ---------------------------------------------------------------------------------------------------
+# a rasteriser for the map's meshes (objnerf_mapraster.hip; map_raster.MapRaster drives these).  The rules stand in
+# include/objnerf_hip.h.
+RASTER_STATS = ("small", "large", "no_sample", "z_near", "bound", "degenerate", "bad_index", "hidden")
+RASTER_STATUS_BAD_ID = 1
+RASTER_SMALL_MAX = 0x7fffffff           # _small_box: every face takes the small path (0: every face the large one)
+RASTER_MAX_SIDE = 65536
+
+
+def raster_workspace_bytes(V: int, F: int) -> int:
+    """0 for sizes out of range (V, F in [0, 2^31))."""
+    if not (-2 ** 63 <= V < 2 ** 63 and -2 ** 63 <= F < 2 ** 63):
+        return 0
+    return int(lib().objnerf_raster_workspace_bytes(int(V), int(F)))
+
+
+def _raster_mesh(verts, faces, face_off, W, H, what):
+    verts, faces = _req(verts, torch.float64, f"{what}: verts"), _req(faces, torch.int32, f"{what}: faces")
+    face_off = _req(face_off, torch.int64, f"{what}: face_off")
+    if verts.dim() != 2 or int(verts.shape[1]) != 3 or faces.dim() != 2 or int(faces.shape[1]) != 3:
+        raise ObjnerfError(f"{what}: verts fp64 [V, 3], faces int32 [F, 3]")
+    S = int(face_off.shape[0]) - 1
+    if face_off.dim() != 1 or S < 0 or S > 65535:
+        raise ObjnerfError(f"{what}: face_off int64 [S + 1], 0 <= S <= 65535")
+    V, F, W, H = int(verts.shape[0]), int(faces.shape[0]), int(W), int(H)
+    if F > 0 and (S < 1 or V < 1):
+        raise ObjnerfError(f"{what}: {F} faces need at least one object and one vertex")
+    if not (1 <= W <= RASTER_MAX_SIDE and 1 <= H <= RASTER_MAX_SIDE and W * H <= 0x7fffffff):
+        raise ObjnerfError(f"{what}: W, H in [1, {RASTER_MAX_SIDE}], got {W} x {H}")
+    if faces.device != verts.device or face_off.device != verts.device:
+        raise ObjnerfError(f"{what}: every tensor on {verts.device}")
+    return verts, faces, face_off, V, F, S, W, H
+
+
+def raster_visibility(verts: torch.Tensor, faces: torch.Tensor, face_off: torch.Tensor, hide: torch.Tensor,
+                      T_CW: torch.Tensor, intrinsics, W: int, H: int, z_near: float = 0.05,
+                      status: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None, _small_box: int = -1,
+                      _passes: int = 0):
+    """objnerf_raster_visibility -> (key int64 [W, H]: the bits of the unsigned keys, -1 = nothing drawn; stats int64 [8]
+    (RASTER_STATS); status int32 [1]; ws: the workspace, which raster_resolve reads), all on the device.  verts fp64
+    [V, 3], faces int32 [F, 3], face_off int64 [S + 1], hide uint8 [S], T_CW fp64 [3, 4] = inverse(T_WC)[:3] on the
+    device, intrinsics (fx, fy, cx, cy).  _small_box, _passes: see the header (negative / 0: the default)."""
+    verts, faces, face_off, V, F, S, W, H = _raster_mesh(verts, faces, face_off, W, H, "raster_visibility")
+    hide, T_CW = _req(hide, torch.uint8, "raster_visibility: hide"), _req(T_CW, torch.float64, "raster_visibility: T_CW")
+    dev = verts.device
+    if tuple(hide.shape) != (S,) or tuple(T_CW.shape) != (3, 4) or hide.device != dev or T_CW.device != dev:
+        raise ObjnerfError(f"raster_visibility: hide uint8 [{S}], T_CW fp64 [3, 4] on {dev}")
+    fx, fy, cx, cy = (float(x) for x in intrinsics)
+    if not float(z_near) > 0.0:
+        raise ObjnerfError(f"raster_visibility: z_near {z_near} must be positive")
+    if not -2 ** 31 <= int(_small_box) <= RASTER_SMALL_MAX:
+        raise ObjnerfError(f"raster_visibility: _small_box {_small_box}")
+    need = raster_workspace_bytes(V, F)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _req(ws, torch.uint8, "raster_visibility: ws")
+    if ws.numel() < need or ws.device != dev:
+        raise ObjnerfError(f"raster_visibility: ws: {need} bytes on {dev}")
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = _req(status, torch.int32, "raster_visibility: status")
+    key = torch.empty(W, H, dtype=torch.int64, device=dev)
+    stats = torch.empty(len(RASTER_STATS), dtype=torch.int64, device=dev)
+    check(lib().objnerf_raster_visibility(V, F, S, W, H, _ptr(verts) if V else None, _ptr(faces) if F else None,
+                                          _ptr(face_off), _ptr(hide) if S else None, _ptr(T_CW), fx, fy, cx, cy,
+                                          float(z_near), int(_small_box), int(_passes), _ptr(ws), int(ws.numel()), _ptr(key), _ptr(stats),
+                                          _ptr(status), _stream()), "objnerf_raster_visibility")
+    return key, stats, status, ws
+
+
+def raster_resolve(verts: torch.Tensor, faces: torch.Tensor, face_off: torch.Tensor, ids: torch.Tensor,
+                   colors: torch.Tensor, ws: torch.Tensor, key: torch.Tensor, cam, ambient: float = 0.35,
+                   shading: bool = True, background=(255, 255, 255)) -> Dict[str, torch.Tensor]:
+    """objnerf_raster_resolve over the keys and the workspace of raster_visibility (same mesh) -> dict(rgb uint8
+    [W, H, 3], maskid int32 [W, H], depth fp32 [W, H], winner, face, vertex int32 [W, H], counts int64 [S]) on the device.
+    ids int32 [S], colors fp32 [V, 3], cam: the camera centre (T_WC[:3, 3]) as three numbers, background: (r, g, b)."""
+    key = _req(key, torch.int64, "raster_resolve: key")
+    if key.dim() != 2:
+        raise ObjnerfError("raster_resolve: key int64 [W, H]")
+    verts, faces, face_off, V, F, S, W, H = _raster_mesh(verts, faces, face_off, key.shape[0], key.shape[1], "raster_resolve")
+    ids, colors = _req(ids, torch.int32, "raster_resolve: ids"), _req(colors, torch.float32, "raster_resolve: colors")
+    ws = _req(ws, torch.uint8, "raster_resolve: ws")
+    dev = verts.device
+    if tuple(ids.shape) != (S,) or tuple(colors.shape) != (V, 3):
+        raise ObjnerfError(f"raster_resolve: ids int32 [{S}], colors fp32 [{V}, 3]")
+    if any(t.device != dev for t in (ids, colors, ws, key)):
+        raise ObjnerfError(f"raster_resolve: every tensor on {dev}")
+    if ws.numel() < raster_workspace_bytes(V, F):
+        raise ObjnerfError("raster_resolve: ws is not the workspace of raster_visibility for this mesh")
+    cam = [float(x) for x in cam]
+    bg = [int(x) for x in background]
+    if len(cam) != 3 or len(bg) != 3 or any(not 0 <= b <= 255 for b in bg) or not 0.0 <= float(ambient) <= 1.0:
+        raise ObjnerfError("raster_resolve: cam [3], background three values in 0..255, ambient in [0, 1]")
+    out = dict(rgb=torch.empty(W, H, 3, dtype=torch.uint8, device=dev), maskid=torch.empty(W, H, dtype=torch.int32, device=dev),
+               depth=torch.empty(W, H, dtype=torch.float32, device=dev), winner=torch.empty(W, H, dtype=torch.int32, device=dev),
+               face=torch.empty(W, H, dtype=torch.int32, device=dev), vertex=torch.empty(W, H, dtype=torch.int32, device=dev),
+               counts=torch.empty(S, dtype=torch.int64, device=dev))
+    check(lib().objnerf_raster_resolve(V, F, S, W, H, _ptr(verts) if V else None, _ptr(faces) if F else None, _ptr(face_off),
+                                       _ptr(ids) if S else None, _ptr(colors) if V else None, _ptr(ws), int(ws.numel()),
+                                       _ptr(key), cam[0], cam[1], cam[2], float(ambient), int(bool(shading)),
+                                       (bg[0] << 16) | (bg[1] << 8) | bg[2], _ptr(out["rgb"]), _ptr(out["maskid"]),
+                                       _ptr(out["depth"]), _ptr(out["winner"]), _ptr(out["face"]), _ptr(out["vertex"]),
+                                       _ptr(out["counts"]) if S else None, _stream()), "objnerf_raster_resolve")
+    return out
