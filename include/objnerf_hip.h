@@ -1373,6 +1373,74 @@ int objnerf_raster_resolve(int64_t V, int64_t F, int32_t S, int32_t W, int32_t H
                            double ambient, int32_t shading, int32_t background, uint8_t* rgb, int32_t* maskid, float* depth,
                            int32_t* winner, int32_t* face, int32_t* vertex, int64_t* counts, void* stream);
 
+/* Ray casting over the map's meshes: first hit and line of sight (objnerf_maprays.hip; openobj_amd/map_rays.py,
+ * DESIGN.md 4.32).  Added under ABI 14: the entries below are purely additive, so OBJNERF_ABI_VERSION stays 14.  The
+ * mesh as the rasteriser takes it (verts fp64 [V][3], faces int32 [F][3], face_off int64 [S + 1], hide uint8 [S], ids
+ * int32 [S]; the same size limits), rays o, d fp64 [N][3] (d is NOT normalised; t is in units of d), 0 <= N <= 2^31 - 1,
+ * a window t_min >= 0 and t_max (scalars, or one per ray where t_min_ray / t_max_ray are not null; a per-ray t_min is the
+ * caller's to keep >= 0), pad >= 0 fp64, leaf >= 1 (negative: the default, 4; an ASSUMED value).  EINVAL for sizes out of
+ * range, a null pointer and a short workspace, before any launch.  Nothing is allocated.
+ *
+ * THE RESULT IS DEFINED WITHOUT THE HIERARCHY.  Every operation rounds once in fp64 (no contraction); a dot product is
+ * (a0 b0 + a1 b1) + a2 b2; a cross product a x b has the components a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0 (two
+ * products, one difference).
+ * RAY:   inv_k = 1 / d_k; axis k is PARALLEL iff inv_k is not finite.  A ray with a component of o or d that is not
+ *        finite, or with d = 0, hits nothing, raises status bit 1 and is counted.
+ * SLAB TEST of a box [lo, hi]: tn = -inf, tf = +inf; on a parallel axis the box passes iff lo_k <= o_k <= hi_k; on
+ *        another a = (lo_k - o_k) inv_k, b = (hi_k - o_k) inv_k, tn = max(tn, min(a, b)), tf = min(tf, max(a, b)).  The
+ *        box passes iff tn <= tf, tf >= t_min and tn <= t_max.
+ * FACE f of object s IS HIT iff
+ *    (a) its three ids lie in [0, V) (else it is never hit and status bit 0 is raised), its three corners are finite,
+ *        and hide[s] == 0;
+ *    (b) its own box passes the slab test, lo = min of the corners - pad, hi = max of the corners + pad, giving tn_f;
+ *    (c) e1 = p1 - p0, e2 = p2 - p0, pv = d x e2, det = e1 . pv, det == 0 or NaN: a miss; tv = o - p0, qv = tv x e1,
+ *        U = tv . pv, Vv = d . qv, T = e2 . qv; if det < 0 all four are negated (both sides are hit); accepted iff
+ *        U >= 0, Vv >= 0 and U + Vv <= det;
+ *    (d) t = T / det + 0.0 (the sum turns -0 into +0) satisfies t_min <= t <= t_max and tn_f <= t.
+ * KEY:   key = (uint64(bits((float) t)) << 32) | f; a ray's result is the MINIMUM key over the hit faces, all ones where
+ *        there is none: the nearest face and, at equal fp32 t, the lowest face id.
+ * Gates (b) and (d) make a hierarchy harmless by the monotonicity of IEEE rounding alone: a node's box contains its
+ * faces' boxes, so under the same sequence its tn is <= and its tf is >= theirs; a node that fails the slab test holds
+ * no hit, and one with (float) tn > (float) t of the best key so far (strictly, as fp32) holds no smaller key.  Node
+ * boxes are fp32, rounded outward.  Moeller-Trumbore in floating point is not watertight: a ray exactly through a shared
+ * edge may in principle miss both neighbours.
+ *
+ * objnerf_rays_workspace_bytes(F, leaf): 0 for sizes out of range.  The workspace holds, from its start, the nodes
+ * (32 bytes each: lo [3], hi [3] fp32, the split axis, 0; 2 P of them in heap order, children 2 n and 2 n + 1, node 0
+ * unused, P = the power of two >= ceil(F / leaf), leaf i = node P + i; rounded up to 256 bytes) and then one slot per
+ * sorted face {int32 face (-1: never hit), int32 object}.
+ * objnerf_rays_build, stage 1: codes int64 [F] = the 63-bit Morton code (21 bits an axis, x highest) of the centre of the
+ * face's padded box inside the scene box [lo, hi] the caller passes (any box: it only shapes the tree), INT64_MAX for a
+ * face that fails (a) but for hide.  The caller sorts the codes STABLY and passes the permutation as `order` to
+ * stage 2: the slots, the leaves' boxes and the levels above them, bottom up, one launch a level, no atomics; every byte
+ * of the nodes and the slots is written, the same bytes in every run.  status: one int32 the caller zeroes; bit 0 is
+ * OR-ed in by either stage.  hide takes no part: changing it needs no rebuild.
+ * objnerf_rays_cast (same V, F, S, leaf, verts, faces, pad as the build): mode bit 0 = ANY-HIT (hit uint8 [N] = whether
+ * a key exists; the walk stops at the first hit found; key may be null), else key uint64 [N] (hit may be null); mode
+ * bit 1 = visit the children in fixed order with the stackless successor (n + 1) >> ctz(n + 1) instead of the nearer
+ * child first (a 64-bit trail in registers): the results do not depend on it.  stats int64 [5] (cleared here): rays, hits,
+ * bad rays, node visits, face tests (the last two: diagnostics that depend on mode and leaf).  status: bit 1 is OR-ed in.
+ * objnerf_rays_resolve (same mesh and rays, the keys of a first-hit cast): per ray with a key, recomputed on the winning
+ * face: hit = 1, face, winner = the object (a search of face_off), maskid = ids[winner], t = the fp32 of the key,
+ *    bary = (u, v) = (U / det, Vv / det) fp64,   point_k = o_k + t d_k with the fp64 t of (d),
+ *    normal = e1 x e2, negated where det was negative (unnormalised, facing the origin of the ray),
+ *    vertex = the packed id of the corner with the largest of ((1 - u) - v, u, v), the first at a tie.
+ * Without a key: hit 0, face = winner = vertex = -1, maskid 0, t = +inf, bary, point and normal = NaN
+ * (0x7ff8000000000000). */
+size_t objnerf_rays_workspace_bytes(int64_t F, int32_t leaf);
+int objnerf_rays_build(int32_t stage, int64_t V, int64_t F, int32_t S, int32_t leaf, const double* verts, const int32_t* faces,
+                       const int64_t* face_off, double pad, double lo_x, double lo_y, double lo_z, double hi_x, double hi_y,
+                       double hi_z, int64_t* codes, const int64_t* order, void* ws, size_t ws_bytes, int32_t* status,
+                       void* stream);
+int objnerf_rays_cast(int32_t mode, int64_t V, int64_t F, int32_t S, int32_t leaf, int64_t N, const double* verts,
+                      const int32_t* faces, const uint8_t* hide, const void* ws, size_t ws_bytes, double pad, const double* o,
+                      const double* d, double t_min, double t_max, const double* t_min_ray, const double* t_max_ray,
+                      uint64_t* key, uint8_t* hit, int64_t* stats, int32_t* status, void* stream);
+int objnerf_rays_resolve(int64_t V, int64_t F, int32_t S, int64_t N, const double* verts, const int32_t* faces,
+                         const int64_t* face_off, const int32_t* ids, const double* o, const double* d, const uint64_t* key,
+                         uint8_t* hit, float* t, int32_t* face, int32_t* winner, int32_t* maskid, int32_t* vertex, double* bary,
+                         double* point, double* normal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

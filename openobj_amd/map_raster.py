@@ -91,6 +91,44 @@ def pick_points(corners, pixels, T_CW, intrinsics, z_near: float = Z_NEAR):
     return pts, b
 
 
+# ------------------------------------------------------------------ what the mask-id image holds; what is hidden
+def ids_of(mq, ids, who: str = "MapRaster") -> np.ndarray:
+    """"obj": the map's keys; "class": every object's class_id; else one value per object -> int32 [S].  (Shared with
+    map_rays.MapRays.)"""
+    if isinstance(ids, str):
+        if ids == "obj":
+            v = [int(k) for k in mq.keys]
+        elif ids == "class":
+            v = [int(mq.all_obj[k].get("class_id", 0)) for k in mq.keys]
+        else:
+            raise ValueError(f"{who}: ids {ids!r}: 'obj', 'class' or one value per object")
+    else:
+        v = [int(x) for x in ids]
+    if len(v) != mq.S:
+        raise ValueError(f"{who}: {len(v)} ids for {mq.S} objects")
+    return np.asarray(v, np.int32)
+
+
+def hide_mask(mq, hide, dataset_name=None, scene_name: str = "room_0", who: str = "MapRaster") -> np.ndarray:
+    """Positions, or names of MapQuery.hidden_sets() sets ("ceiling", "most", "hidden") -> uint8 [S]."""
+    S = mq.S
+    out = np.zeros(S, np.uint8)
+    sets = None
+    for h in ([hide] if isinstance(hide, (str, int, np.integer)) else list(hide)):
+        if isinstance(h, str) and not h.lstrip("-").isdigit():
+            if sets is None:
+                sets = mq.hidden_sets(dataset_name, scene_name)
+            if h not in ("ceiling", "most", "hidden"):
+                raise ValueError(f"{who}: hide {h!r}: a position or one of ceiling, most, hidden")
+            out[[int(p) for p in sets[h]]] = 1
+        else:
+            p = int(h)
+            if not 0 <= p < S:
+                raise ValueError(f"{who}: hide {p}: positions in [0, {S})")
+            out[p] = 1
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------- the device side
 class MapRaster:
     """Views of a MapQuery's meshes.  render() rasterises one view; pick() and visible() read the last one."""
@@ -108,38 +146,11 @@ class MapRaster:
     # ------------------------------------------------------------------------------------------------------------
     def ids_of(self, ids) -> np.ndarray:
         """"obj": the map's keys; "class": every object's class_id; else one value per object -> int32 [S]."""
-        mq = self.mq
-        if isinstance(ids, str):
-            if ids == "obj":
-                v = [int(k) for k in mq.keys]
-            elif ids == "class":
-                v = [int(mq.all_obj[k].get("class_id", 0)) for k in mq.keys]
-            else:
-                raise ValueError(f"MapRaster: ids {ids!r}: 'obj', 'class' or one value per object")
-        else:
-            v = [int(x) for x in ids]
-        if len(v) != mq.S:
-            raise ValueError(f"MapRaster: {len(v)} ids for {mq.S} objects")
-        return np.asarray(v, np.int32)
+        return ids_of(self.mq, ids)
 
     def hide_mask(self, hide) -> np.ndarray:
         """Positions, or names of MapQuery.hidden_sets() sets ("ceiling", "most", "hidden") -> uint8 [S]."""
-        S = self.mq.S
-        out = np.zeros(S, np.uint8)
-        sets = None
-        for h in ([hide] if isinstance(hide, (str, int, np.integer)) else list(hide)):
-            if isinstance(h, str) and not h.lstrip("-").isdigit():
-                if sets is None:
-                    sets = self.mq.hidden_sets(self.dataset_name, self.scene_name)
-                if h not in ("ceiling", "most", "hidden"):
-                    raise ValueError(f"MapRaster: hide {h!r}: a position or one of ceiling, most, hidden")
-                out[[int(p) for p in sets[h]]] = 1
-            else:
-                p = int(h)
-                if not 0 <= p < S:
-                    raise ValueError(f"MapRaster: hide {p}: positions in [0, {S})")
-                out[p] = 1
-        return out
+        return hide_mask(self.mq, hide, self.dataset_name, self.scene_name)
 
     def render(self, T_WC, intrinsics, W: int, H: int, colors=None, hide=(), ids="obj", shading: str = "headlight",
                background=(255, 255, 255), z_near: float = Z_NEAR, to_host: bool = True, ambient: float = AMBIENT,
@@ -315,7 +326,7 @@ def main(argv=None):
     return doc
 
 
-__all__ = ["MapRaster", "camera_rows", "project_vertices", "pick_points", "load_pose", "AMBIENT", "Z_NEAR", "SHADINGS"]
+__all__ = ["MapRaster", "ids_of", "hide_mask", "camera_rows", "project_vertices", "pick_points", "load_pose", "AMBIENT", "Z_NEAR", "SHADINGS"]
 
 if __name__ == "__main__":
     main()

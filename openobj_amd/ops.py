@@ -2795,3 +2795,198 @@ def raster_resolve(verts: torch.Tensor, faces: torch.Tensor, face_off: torch.Ten
                                        _ptr(out["depth"]), _ptr(out["winner"]), _ptr(out["face"]), _ptr(out["vertex"]),
                                        _ptr(out["counts"]) if S else None, _stream()), "objnerf_raster_resolve")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# ray casting over the map's meshes (objnerf_maprays.hip; map_rays.MapRays drives these).  The rules stand in
+# include/objnerf_hip.h.
+RAYS_STATS = ("rays", "hits", "bad_rays", "node_visits", "face_tests")
+RAYS_STATUS_BAD_ID = 1
+RAYS_STATUS_BAD_RAY = 2
+RAYS_LEAF_DEFAULT = 4                   # an ASSUMED default
+RAYS_EMPTY = -1                         # the bits of the all-ones key as int64
+RAYS_NODE_BYTES = 32
+
+
+def rays_workspace_bytes(F: int, leaf: int = -1) -> int:
+    """0 for sizes out of range (F in [0, 2^31), leaf >= 1 or negative for the default)."""
+    if not (-2 ** 63 <= F < 2 ** 63 and -2 ** 31 <= leaf < 2 ** 31):
+        return 0
+    return int(lib().objnerf_rays_workspace_bytes(int(F), int(leaf)))
+
+
+def rays_node_count(F: int, leaf: int = -1) -> int:
+    """2 P: the nodes at the start of the workspace (heap order, node 0 unused), 32 bytes each."""
+    leaf = RAYS_LEAF_DEFAULT if leaf < 0 else int(leaf)
+    n, P = max(-(-int(F) // leaf), 1), 1
+    while P < n:
+        P *= 2
+    return 2 * P
+
+
+def _rays_mesh(verts, faces, face_off, leaf, what):
+    verts, faces = _req(verts, torch.float64, f"{what}: verts"), _req(faces, torch.int32, f"{what}: faces")
+    face_off = _req(face_off, torch.int64, f"{what}: face_off")
+    if verts.dim() != 2 or int(verts.shape[1]) != 3 or faces.dim() != 2 or int(faces.shape[1]) != 3:
+        raise ObjnerfError(f"{what}: verts fp64 [V, 3], faces int32 [F, 3]")
+    S = int(face_off.shape[0]) - 1
+    if face_off.dim() != 1 or S < 0 or S > 65535:
+        raise ObjnerfError(f"{what}: face_off int64 [S + 1], 0 <= S <= 65535")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if F > 0 and (S < 1 or V < 1):
+        raise ObjnerfError(f"{what}: {F} faces need at least one object and one vertex")
+    if faces.device != verts.device or face_off.device != verts.device:
+        raise ObjnerfError(f"{what}: every tensor on {verts.device}")
+    leaf = int(leaf)
+    if not (leaf < 0 or 1 <= leaf <= 0x7fffffff):
+        raise ObjnerfError(f"{what}: leaf {leaf}: at least 1 (negative: the default)")
+    return verts, faces, face_off, V, F, S, leaf
+
+
+def _rays_pad(pad, what):
+    pad = float(pad)
+    if not (pad >= 0.0 and pad != float("inf")):
+        raise ObjnerfError(f"{what}: pad {pad} must be finite and not negative")
+    return pad
+
+
+def rays_scene_box(verts: torch.Tensor):
+    """The box of the finite coordinates of verts fp64 [V, 3] -> (lo [3], hi [3]) as Python floats; (0, 0) on an axis
+    without a finite value."""
+    big = torch.finfo(torch.float64).max
+    fin = torch.isfinite(verts)
+    if verts.shape[0] == 0:
+        return [0.0] * 3, [0.0] * 3
+    lo = torch.where(fin, verts, torch.full_like(verts, big)).amin(dim=0).tolist()
+    hi = torch.where(fin, verts, torch.full_like(verts, -big)).amax(dim=0).tolist()
+    for k in range(3):
+        if lo[k] > hi[k]:
+            lo[k] = hi[k] = 0.0
+    return lo, hi
+
+
+def rays_default_pad(verts: torch.Tensor) -> float:
+    """2^-20 times the largest finite extent of verts (an ASSUMED default)."""
+    lo, hi = rays_scene_box(verts)
+    return max(h - l for l, h in zip(lo, hi)) * 2.0 ** -20
+
+
+def rays_build(verts: torch.Tensor, faces: torch.Tensor, face_off: torch.Tensor, pad: float, leaf: int = -1,
+               ws: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None, box=None, _stage: int = 0,
+               _codes: Optional[torch.Tensor] = None, _order: Optional[torch.Tensor] = None):
+    """objnerf_rays_build, both stages with the stable sort of the codes between them -> (ws uint8: the hierarchy that
+    rays_cast walks, status int32 [1]: bit 0 = a face with an id outside [0, V)).  verts fp64 [V, 3], faces int32
+    [F, 3], face_off int64 [S + 1] on the device; box: (lo [3], hi [3]) of the scene (None: rays_scene_box(verts)).
+    _stage (tools/rays_bench.py): 1 -> the codes int64 [F] alone; 2 -> stage 2 alone on _order."""
+    verts, faces, face_off, V, F, S, leaf = _rays_mesh(verts, faces, face_off, leaf, "rays_build")
+    pad = _rays_pad(pad, "rays_build")
+    dev = verts.device
+    lo, hi = rays_scene_box(verts) if box is None else ([float(x) for x in box[0]], [float(x) for x in box[1]])
+    if len(lo) != 3 or len(hi) != 3:
+        raise ObjnerfError("rays_build: box (lo [3], hi [3])")
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = _req(status, torch.int32, "rays_build: status")
+    if _stage not in (0, 1, 2):
+        raise ObjnerfError(f"rays_build: _stage {_stage}")
+
+    def call(stage, codes, order, wsp):
+        check(lib().objnerf_rays_build(stage, V, F, S, leaf, _ptr(verts) if V else None, _ptr(faces) if F else None,
+                                       _ptr(face_off), pad, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], _ptr(codes),
+                                       _ptr(order), _ptr(wsp), int(wsp.numel()) if wsp is not None else 0, _ptr(status),
+                                       _stream()), "objnerf_rays_build")
+
+    if _stage in (0, 1):
+        codes = torch.empty(F, dtype=torch.int64, device=dev) if _codes is None else _req(_codes, torch.int64, "rays_build: codes")
+        if tuple(codes.shape) != (F,) or codes.device != dev:
+            raise ObjnerfError(f"rays_build: codes int64 [{F}] on {dev}")
+        call(1, codes if F else None, None, None)
+        if _stage == 1:
+            return codes
+        _order = torch.sort(codes, stable=True)[1]
+    order = _req(_order, torch.int64, "rays_build: order")
+    if tuple(order.shape) != (F,) or order.device != dev:
+        raise ObjnerfError(f"rays_build: order int64 [{F}] on {dev}")
+    need = rays_workspace_bytes(F, leaf)
+    if ws is None:
+        ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+    ws = _req(ws, torch.uint8, "rays_build: ws")
+    if need == 0 or ws.numel() < need or ws.device != dev:
+        raise ObjnerfError(f"rays_build: ws: {need} bytes on {dev}")
+    call(2, None, order if F else None, ws)
+    return ws, status
+
+
+def rays_cast(verts: torch.Tensor, faces: torch.Tensor, face_off: torch.Tensor, hide: torch.Tensor, ws: torch.Tensor,
+              pad: float, origins: torch.Tensor, dirs: torch.Tensor, t_min=0.0, t_max=float("inf"), leaf: int = -1,
+              any_hit: bool = False, status: Optional[torch.Tensor] = None, _fixed_order: bool = False):
+    """objnerf_rays_cast over the hierarchy of rays_build (same mesh, pad and leaf) -> (key int64 [N]: the bits of the
+    unsigned keys, -1 = no hit (any_hit: hit uint8 [N] instead); stats int64 [5] (RAYS_STATS); status int32 [1]: bits are
+    OR-ed in).  origins, dirs fp64 [N, 3]; t_min, t_max: numbers, or fp64 [N] device tensors; hide uint8 [S]."""
+    verts, faces, face_off, V, F, S, leaf = _rays_mesh(verts, faces, face_off, leaf, "rays_cast")
+    pad = _rays_pad(pad, "rays_cast")
+    dev = verts.device
+    hide, ws = _req(hide, torch.uint8, "rays_cast: hide"), _req(ws, torch.uint8, "rays_cast: ws")
+    o, d = _req(origins, torch.float64, "rays_cast: origins"), _req(dirs, torch.float64, "rays_cast: dirs")
+    if o.dim() != 2 or int(o.shape[1]) != 3 or o.shape != d.shape:
+        raise ObjnerfError("rays_cast: origins, dirs fp64 [N, 3]")
+    N = int(o.shape[0])
+    if N > 0x7fffffff:
+        raise ObjnerfError(f"rays_cast: {N} rays: at most 2^31 - 1")
+    need = rays_workspace_bytes(F, leaf)
+    if tuple(hide.shape) != (S,) or need == 0 or ws.numel() < need:
+        raise ObjnerfError(f"rays_cast: hide uint8 [{S}], ws: the {need} bytes of rays_build for this mesh and leaf")
+    win, per = [], []
+    for name, w in (("t_min", t_min), ("t_max", t_max)):
+        if isinstance(w, torch.Tensor):
+            w = _req(w, torch.float64, f"rays_cast: {name}")
+            if tuple(w.shape) != (N,) or w.device != dev:
+                raise ObjnerfError(f"rays_cast: {name}: a number or fp64 [{N}] on {dev}")
+            win.append(0.0 if name == "t_min" else float("inf"))
+            per.append(w)
+        else:
+            win.append(float(w))
+            per.append(None)
+    if not win[0] >= 0.0 or win[1] != win[1]:
+        raise ObjnerfError(f"rays_cast: t_min {win[0]} must not be negative, t_max {win[1]} not a NaN")
+    if any(t.device != dev for t in (hide, ws, o, d)):
+        raise ObjnerfError(f"rays_cast: every tensor on {dev}")
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = _req(status, torch.int32, "rays_cast: status")
+    out = torch.empty(N, dtype=torch.uint8 if any_hit else torch.int64, device=dev)
+    stats = torch.empty(len(RAYS_STATS), dtype=torch.int64, device=dev)
+    check(lib().objnerf_rays_cast((1 if any_hit else 0) | (2 if _fixed_order else 0), V, F, S, leaf, N,
+                                  _ptr(verts) if V else None, _ptr(faces) if F else None, _ptr(hide) if S else None, _ptr(ws),
+                                  int(ws.numel()), pad, _ptr(o) if N else None, _ptr(d) if N else None, win[0], win[1],
+                                  _ptr(per[0]), _ptr(per[1]), None if any_hit or not N else _ptr(out),
+                                  _ptr(out) if any_hit and N else None, _ptr(stats), _ptr(status), _stream()),
+          "objnerf_rays_cast")
+    return out, stats, status
+
+
+def rays_resolve(verts: torch.Tensor, faces: torch.Tensor, face_off: torch.Tensor, ids: torch.Tensor,
+                 origins: torch.Tensor, dirs: torch.Tensor, key: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """objnerf_rays_resolve over the keys of a first-hit rays_cast (same mesh and rays) -> dict(hit uint8 [N], t fp32 [N],
+    face, winner, maskid, vertex int32 [N], bary fp64 [N, 2], point, normal fp64 [N, 3]) on the device."""
+    verts, faces, face_off, V, F, S, _ = _rays_mesh(verts, faces, face_off, 1, "rays_resolve")
+    dev = verts.device
+    ids, key = _req(ids, torch.int32, "rays_resolve: ids"), _req(key, torch.int64, "rays_resolve: key")
+    o, d = _req(origins, torch.float64, "rays_resolve: origins"), _req(dirs, torch.float64, "rays_resolve: dirs")
+    if o.dim() != 2 or int(o.shape[1]) != 3 or o.shape != d.shape:
+        raise ObjnerfError("rays_resolve: origins, dirs fp64 [N, 3]")
+    N = int(o.shape[0])
+    if tuple(ids.shape) != (S,) or tuple(key.shape) != (N,) or N > 0x7fffffff:
+        raise ObjnerfError(f"rays_resolve: ids int32 [{S}], key int64 [{N}]")
+    if any(t.device != dev for t in (ids, key, o, d)):
+        raise ObjnerfError(f"rays_resolve: every tensor on {dev}")
+    e = lambda shape, dt: torch.empty(*shape, dtype=dt, device=dev)
+    out = dict(hit=e((N,), torch.uint8), t=e((N,), torch.float32), face=e((N,), torch.int32), winner=e((N,), torch.int32),
+               maskid=e((N,), torch.int32), vertex=e((N,), torch.int32), bary=e((N, 2), torch.float64),
+               point=e((N, 3), torch.float64), normal=e((N, 3), torch.float64))
+    p = (lambda t: _ptr(t)) if N else (lambda t: None)
+    check(lib().objnerf_rays_resolve(V, F, S, N, _ptr(verts) if V else None, _ptr(faces) if F else None, _ptr(face_off),
+                                     _ptr(ids) if S else None, p(o), p(d), p(key), p(out["hit"]), p(out["t"]), p(out["face"]),
+                                     p(out["winner"]), p(out["maskid"]), p(out["vertex"]), p(out["bary"]), p(out["point"]),
+                                     p(out["normal"]), _stream()), "objnerf_rays_resolve")
+    return out
